@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the exp(tA)v hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A timed "step" is one generator SpMV launch y = A x (FMATVEC, the dominant
 kernel of the path; with N > 1 ranks each launch is preceded by the RCCL
@@ -17,7 +17,8 @@ With --gpus N > 1 and no launcher (WORLD_SIZE unset) the script starts its N ran
 child processes of this same file, one per GPU, created BEFORE anything here touches the
 GPU; rank 0's JSON line is relayed.  Under torch.distributed.run it joins the ranks it is given.
 
-The same JSON line carries
+A plain run sets up, warms up, times the K steps and prints one JSON line (`ms_per_step` = wall
+milliseconds of one timed step).  Its line carries
   roofline      the SpMV kernel against the HBM roofline (HIP events on the
                 library's own stream, measured over the timed region): `achieved` / `frac`
                 count the bytes that really cross the HBM interface per launch - the
@@ -25,16 +26,27 @@ The same JSON line carries
                 where that is larger - so frac <= 1 by construction; `alg_GBps` keeps
                 the SURVEY 8(d) CSR model (what `value` reports), which the banded form
                 does not move (it stores no column indices)
-  spmv_1e7      (default run) the same product at 10^7 states per GPU - the size of the
+  self_check    the product that is timed, checked in this process against numpy on sampled
+                rows of every rank: with more than one rank (or --force-comm) always, since it
+                picks the exchange the timed product uses; on one rank with --full
+--dump-outputs DIR writes, after the timed steps, what a caller of the timed path receives: the
+product y = A x of this rank's rows (kfsp_spmv_w on the same context and source vector, the kernel
+the timed launches run with --variant 0), float64, as DIR/y.npy (DIR/y_rank<r>.npy with several
+ranks); where the ranks' outputs would exceed 64 MB together, a fixed, seeded sample of the rows.
+The inputs are seeded: the same arguments give the same inputs on every run.
+--full adds everything that is not the headline figure:
+  matrix_free   the same product with no stored generator (box workloads)
+  spmv_1e7      the same product at 10^7 states per GPU - the size of the
                 60 % target: c3x = repressilator box 216^3, generator written out ON THE
                 DEVICE from the propensity tables, stored and matrix-free, same fields
-  self_check    the product that is timed, checked in this process against numpy on sampled
-                rows of every rank (always, also on one GPU)
+  exchange      the exchange of the source vector alone (more than one rank or --force-comm)
+  expv_workload exp(tA)v on the workload's own generator (c3x, c4, c5s, c5)
   expv          the exp(tA)v half of the metric: BASELINE configs[1] (toggle box
                 10^6 states per GPU, Krylov m = 30, tau = 0.01, 10 steps) wall
                 time per step and its l1 error against the CPU path
   cpu_baseline  the oracle (plain-C port of the reference loops) on this host,
                 1 core, on a bounded sample of the same workload
+(--no-1e7, --no-expv and --no-cpu leave single blocks of --full out; --fsp adds the spmv_fsp block.)
 --workload c5 is BASELINE configs[4] at its stated size (22^6 = 1.13e8 states, 1.41e9 nnz):
 the whole generator on however many ranks there are, each rank's rows written out by its
 own device (no host arrays of that size exist); "scaling": "strong".
@@ -53,6 +65,22 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (guides/MI355X_MICROARCH.md)
+DUMP_BYTES = 64_000_000  # --dump-outputs: all ranks' files together stay below this
+DUMP_SEED = 2024
+
+
+def dump_output(out_dir, name, y, budget):
+    """y as out_dir/<name>.npy in float64.  An array of more than `budget` bytes (less room for the
+    .npy header) is written as a fixed, seeded sample of its entries, in index order: the same
+    entries on every run with the same arguments.  -> path written"""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    k = max(budget - 4096, 0) // y.itemsize
+    if y.size > k:
+        y = y[np.sort(np.random.default_rng(DUMP_SEED).choice(y.size, k, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, y)
+    return path
 
 
 def parse():
@@ -64,14 +92,19 @@ def parse():
     ap.add_argument("--device-build", action="store_true",
                     help="box workloads: the stored generator is written out by the device from the propensity tables "
                          "(kfsp_set_matrix_box, option box_store) instead of uploading gather rows made by numpy; always on for c5")
-    ap.add_argument("--no-1e7", action="store_true", help="skip the spmv_1e7 block (c3x, 10^7 states per GPU) of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the single-rank self-check, the matrix-free and 10^7-state products, the exchange "
+                         "alone, exp(tA)v and the CPU baseline (what a plain run leaves out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the product y = A x the timed path computes as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-1e7", action="store_true", help="skip the spmv_1e7 block (c3x, 10^7 states per GPU) of --full")
     ap.add_argument("--fsp", action="store_true",
                     help="add the spmv_fsp block: the generator product on a NON-BOX FSP of 1.0e7 states (Goutsias on an ellipsoid x 6 DNA "
                          "configurations, listed in search order; SELL-64 in the caller's order, in the internal order, with coded columns); "
                          "single GPU, ~40 s of input generation and upload")
     ap.add_argument("--variant", type=int, default=0, choices=[0, 2], help="SpMV kernel variant (0 auto: DIA/SELL, 2 SELL-64)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-expv", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg of --full")
+    ap.add_argument("--no-expv", action="store_true", help="skip the exp(tA)v legs of --full")
     ap.add_argument("--expv-steps", type=int, default=10)
     ap.add_argument("--opt", action="append", default=[], help="library option name=value")
     ap.add_argument("--matrix-free", action="store_true",
@@ -324,7 +357,9 @@ def main():
 
     from krylovfspssa_amd import host as _host
     exchange = "none (single rank)"
-    check_err, raised = product_check()
+    # the check picks the exchange of a partitioned product; one rank checks its product with --full only
+    checked = args.full or world > 1 or args.force_comm
+    check_err, raised = product_check() if checked else (None, False)
     if world > 1 or args.force_comm:
         exchange = "halo strips (banded generator), overlapped with the interior rows when the block is large"
         # never report a number from a wrong product: step down to the simpler exchanges.  A rank whose
@@ -344,7 +379,7 @@ def main():
         if raised:
             print(f"[bench] rank {rank}: the product raised in every exchange mode; aborting all ranks", file=sys.stderr)
             sys.exit(3)
-    check_ok = check_err < 1e-12
+    check_ok = not checked or check_err < 1e-12
     ctx.set_vector(x)
     ctx.begin_step()
 
@@ -357,9 +392,14 @@ def main():
     ms_events = max_over_ranks(ms_events)
     value = args.steps * b_alg_global / elapsed / 1e9
     kern_ms = ms_events / args.steps
+    if args.dump_outputs:
+        # y = A x as a caller receives it, from the context and source vector the timed launches used (a collective
+        # with several ranks: every rank takes part)
+        path = dump_output(args.dump_outputs, "y" if world == 1 else f"y_rank{rank}", ctx.spmv_w(), DUMP_BYTES // world)
+        print(f"[bench] rank {rank}: wrote {path}", file=sys.stderr)
     # the exchange of the source vector alone, per rank (what every product of the partition pays before its rows)
     exch = None
-    if world > 1 or args.force_comm:
+    if args.full and (world > 1 or args.force_comm):
         ex_ms, ex_bytes = ctx.exchange_bench(args.steps)
         ex_ms /= args.steps
         t = torch.tensor([ex_ms, float(ex_bytes)], dtype=torch.float64, device="cuda")
@@ -449,17 +489,18 @@ def main():
                                ("nothing stored" if args.matrix_free else "gather rows made by numpy, uploaded (kfsp_set_matrix_csr)"),
             "stored_slots_local": info["slots"],
         },
-        "self_check": {"ok": bool(check_ok), "max_rel_err": check_err,
-                       "what": "the timed product (same context, same exchange) vs numpy on 2.5k sampled rows per rank"},
         "roofline": roof,
         "exchange": exch,
         "input_generation_s": round(t_gen, 2),
     }
+    if checked:
+        out["self_check"] = {"ok": bool(check_ok), "max_rel_err": check_err,
+                             "what": "the timed product (same context, same exchange) vs numpy on 2.5k sampled rows per rank"}
 
     # ------------------------------------------- the same product, matrix-free
     # (box workloads with separable propensities: no stored generator, kfsp_set_matrix_box; reported
     # next to the headline number, which stays the stored generator every FSP can use)
-    if not args.matrix_free and getattr(mdl, "deps", None) is not None and args.variant == 0:
+    if args.full and not args.matrix_free and getattr(mdl, "deps", None) is not None and args.variant == 0:
         ctx.set_matrix_box(mdl, store=False)
         ctx.set_vector(x)
         ctx.begin_step()
@@ -497,7 +538,7 @@ def main():
     # ------------------------------------------- the 10^7-state product (the size of the 60 % target)
     # c3x: repressilator box 216 x 216 x (216 * ranks), 1.0e7 states per GPU, built on the device from the
     # propensity tables (no host arrays), stored (banded) and matrix-free, both byte counts
-    if args.workload == "c3" and not args.no_1e7 and not args.matrix_free and args.variant == 0:
+    if args.full and args.workload == "c3" and not args.no_1e7 and not args.matrix_free and args.variant == 0:
         big, _ = spmv_model("c3x", world)
         br0, bnr = ctx.row_block(big.n)
         xb = np.random.default_rng(54321 + rank).random(bnr)
@@ -577,7 +618,7 @@ def main():
     # ------------------------------------------- exp(tA)v on THIS workload's own generator (the large boxes)
     # fixed Krylov dimension m = 30 as in the c2 recipe; tau small enough that the FSP keeps its mass (the bench times the
     # kernels, not the physics); p0 = normalised Poisson product.  One GPU; c5 keeps its 33-column basis (m_max = 30).
-    if args.workload in ("c3x", "c4", "c5s", "c5") and not args.no_expv and world == 1 and args.variant == 0:
+    if args.full and args.workload in ("c3x", "c4", "c5s", "c5") and not args.no_expv and world == 1 and args.variant == 0:
         m_big, tau_big, n_big = 30, 1.0e-3, 4
         load_generator()
         lam = 8.0 if args.workload in ("c5", "c5s") else 20.0
@@ -615,7 +656,7 @@ def main():
         del pb
 
     # ---------------------------------------------------------------- expv
-    if not args.no_expv:
+    if args.full and not args.no_expv:
         ctx.set_option("m_max", 100)
         tg = synth.toggle(1000, 1000 * world) if args.workload != "tiny" else synth.toggle(100, 80 * world)
         r0, nr = ctx.row_block(tg.n)
@@ -661,7 +702,7 @@ def main():
         tg = None
 
     # ---------------------------------------------------------- CPU baseline
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import oracle as O
         O.lib()
         cpu_mdl, cpu_what = mdl, f"the same {args.workload} matrix"

@@ -8,9 +8,9 @@ B=$R/krylovfspssa_amd/fortran/_build
 mkdir -p $O
 (cd /tmp && /opt/rocm/lib/llvm/bin/flang -O3 -fopenmp -I$B $R/profiles/statespace_bench.f90 $B/libkfsp_fortran.a -L$R/krylovfspssa_amd/lib -lkfsp_hip -Wl,-rpath,$R/krylovfspssa_amd/lib -Wl,-rpath,/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib/llvm/lib -o /tmp/ssb)
 KFSP_HOST_THREADS=16 /tmp/ssb 2.0 38 /tmp/fsp.bin | tail -1
-python bench.py > $O/bench_c3_final.json 2> $O/bench_c3_final.err
+python bench.py --full > $O/bench_c3_final.json 2> $O/bench_c3_final.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o mf -- python3 $R/bench.py --workload c3x --matrix-free --no-expv --no-cpu > $O/bench_c3x_mf.json 2> $O/bench_c3x_mf.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o mf -- python3 $R/bench.py --full --workload c3x --matrix-free --no-expv --no-cpu > $O/bench_c3x_mf.json 2> $O/bench_c3x_mf.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/prof -o pf -- python3 $R/profiles/pmc_box_fsp.py > $O/pmc_box_fsp.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/prof -o pw -- python3 $R/profiles/pmc_box_fsp.py >> $O/pmc_box_fsp.log 2>&1
 cd $R

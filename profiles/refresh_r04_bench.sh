@@ -5,16 +5,16 @@ set -e
 R=$PWD
 O=$R/gpurun_out/r04
 mkdir -p $O
-python3 bench.py > $O/bench_c3.json 2> $O/bench_c3.err
+python3 bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_b2 -o b2 -- python3 $R/bench.py --no-1e7 > $O/bench_c3_no1e7_prof.json 2> $O/bench_c3_no1e7_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_b2 -o b2 -- python3 $R/bench.py --full --no-1e7 > $O/bench_c3_no1e7_prof.json 2> $O/bench_c3_no1e7_prof.err
 cd $R
 cp $(find /tmp/prof_b2 -name "b2_kernel_stats.csv" | head -1) $O/bench_c3_kernel_stats.csv
-python3 bench.py --workload c3x --no-1e7 --no-cpu > $O/bench_c3x.json 2> $O/bench_c3x.err
-python3 bench.py --workload c4 --no-cpu > $O/bench_c4.json 2> $O/bench_c4.err
-python3 bench.py --workload c5s --no-cpu > $O/bench_c5s.json 2> $O/bench_c5s.err
-python3 bench.py --workload c5 --steps 50 --warmup 5 --no-cpu > $O/bench_c5.json 2> $O/bench_c5.err
-python3 bench.py --workload c5 --matrix-free --steps 50 --warmup 5 --no-cpu > $O/bench_c5_mf.json 2> $O/bench_c5_mf.err
+python3 bench.py --full --workload c3x --no-1e7 --no-cpu > $O/bench_c3x.json 2> $O/bench_c3x.err
+python3 bench.py --full --workload c4 --no-cpu > $O/bench_c4.json 2> $O/bench_c4.err
+python3 bench.py --full --workload c5s --no-cpu > $O/bench_c5s.json 2> $O/bench_c5s.err
+python3 bench.py --full --workload c5 --steps 50 --warmup 5 --no-cpu > $O/bench_c5.json 2> $O/bench_c5.err
+python3 bench.py --full --workload c5 --matrix-free --steps 50 --warmup 5 --no-cpu > $O/bench_c5_mf.json 2> $O/bench_c5_mf.err
 python3 - <<'PY'
 import json, csv, os
 O = "gpurun_out/r04"
