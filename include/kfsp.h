@@ -441,6 +441,36 @@ typedef struct {
 int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_reactions,
                 const kfsp_fsp_ops *ops, kfsp_stats *stats);
 
+/* ---- several vectors at once ------------------------------------------- */
+/* exp(tA) W for k start vectors on ONE pass over the generator per product: transition probabilities from several
+ * observed states, several initial distributions of one model.  The generator must be a stored one (SELL-64, coded
+ * SELL, banded, masked banded): a matrix-free box (kernel formats 3, 4, 6, 7, 8; option box_store = 1 stores it) and a
+ * context with a communicator or a group head return -12.  A block lives beside w (w is never touched) until the
+ * generator changes: the next kfsp_set_matrix_* / kfsp_update_matrix_ell / kfsp_drop_compact / kfsp_expand_resident
+ * discards it, and kfsp_get_block then fails.  On the device a block holds kp = k rounded up to 2, 4, 8 or 16 doubles
+ * per row (zero padding columns); the basis of kfsp_expv_block takes (m + 2) kp rows-long columns. */
+/* k start vectors (1 <= k <= 16), W column-major host memory W[j*ldw + i], i in the caller's order (the internal state
+ * order is applied as in kfsp_set_vector); n = the number of states of the generator */
+int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W);
+/* the resident block back; k must be the k of kfsp_set_block.  -1 when no block is resident */
+int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W);
+/* Y = A X for k host columns X[j*ld + i] (ld >= n), Y alike; column j is BIT-IDENTICAL to kfsp_spmv of column j (every
+ * column of a row is summed in FMATVEC's order, KrylovSolver.f90:598-604).  Leaves the resident block alone. */
+int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y);
+/* W <- exp(t A) W for the resident block: EXPOKIT's step control of DGEXPV_FSP (KrylovSolver.f90:177-187, 280-345,
+ * 437, 540-548) with the Krylov dimension fixed at m (<= option m_max, capped at n - 1), ONE step size for all
+ * columns, accepted iff max_j ERR_LOC_j / (tol T_STEP) <= DELTA, the next one from the worst column.  Each column has
+ * its own IOP(2) basis, beta, H, happy breakdown (then its H is exact and it no longer limits the step) and AVNORM; a
+ * zero column stays exactly 0.  After each step every column is clamped at 0 (:447-449); wsum[k] = the l1 mass of each
+ * column at the end.  No FSP test, no drop / expand.  t > 0, tol > 0. */
+typedef struct {
+    int32_t nstep, nreject, nmult, n_breakdown_cols;   /* nmult: block products; n_breakdown_cols: columns that broke down */
+    double t_now, step_min, step_max, x_error, s_error;
+} kfsp_block_stats;
+int kfsp_expv_block(kfsp_ctx *ctx, double t, double tol, int32_t m, double *wsum, kfsp_block_stats *stats);
+/* reps block products Y = A X on the resident block, bracketed by HIP events (like kfsp_spmv_bench) */
+int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total);
+
 /* ---- lock-step diagnostics ---------------------------------------------- */
 /* The accept/reject decisions of DGEXPV_FSP hinge on quantities that amplify
  * rounding differences (the tail of exp(tau*H) after ~75 IOP columns), so two

@@ -1,0 +1,806 @@
+// Several start vectors at once: exp(tA) W for a block W of k <= 16 columns on one pass over the generator per
+// product (include/kfsp.h, "several vectors at once").
+//
+// Layout.  A block vector holds kp = k rounded up to 2, 4, 8 or 16 doubles per row, row-interleaved: row i of
+// column c at X[i * kp + c].  The padding columns are zero and stay zero.  Every block column carries 64 zero rows in
+// front and 64 behind its rows (the x clamp of the banded product reads row -1 and row n, like the guard words of
+// DevBuf and the column padding of the single-vector path).
+//
+// SpMM.  One lane per row, kp accumulators in registers, the x of an entry read as kp/2 16-byte loads: the generator
+// streams are read once per block.  Column c of a row is summed in EXACTLY the order of the single-vector kernel
+// (kfsp_kernels.hip: row_sell, row_sell_coded, rows_dia): -DIAG x first (one v_mul_f64), then one fused multiply-add
+// per entry in FMATVEC's order (KrylovSolver.f90:598-604).  The fused operations are written out below and the file
+// is compiled with contraction off, so no other fusion can creep in: column c of A X is bit-identical to kfsp_spmv of
+// column c (tests/test_gpu_block.py).  The banded rows take the operands the two-rows-per-lane kernel takes, clamp
+// included.
+//
+// Arnoldi.  k INDEPENDENT IOP(2) bases (not a block Krylov space): per column its own beta, H, breakdown and AVNORM.
+// Dot products and norms are block partials in a fixed layout, summed in a fixed order by one small finishing
+// launch: two runs give the same bits.  A column whose H(j+1,j) <= break_tol stops there (its coefficients become 0,
+// its H is exact); a column with beta = 0 is skipped from the start and stays exactly 0.
+#pragma clang fp contract(off)
+
+#include "kfsp_block.h"
+#include "kfsp_ctx.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+
+namespace kfsp {
+
+namespace {
+
+constexpr int K = kBlockMaxK;
+constexpr int kMargin = 64;   // zero rows in front of and behind every block column
+
+// per-column scalars of a pass (d_bscal), K entries each
+constexpr int kHB = 0;                          // [(kMMax + 2) * 3][K]: H(j-1,j), H(j,j), H(j+1,j) of column j
+constexpr int kNRM = kHB + (kMMax + 2) * 3 * K; // [kMMax + 3][K]: ||u_j||
+constexpr int kCO = kNRM + (kMMax + 3) * K;     // [3][K]: the update coefficients of the column in progress
+constexpr int kGG = kCO + 3 * K;                // [K]: v_j . v_{j-1}
+constexpr int kBRK = kGG + K;                   // [K]: 0 running, j broke down after column j, -1 skipped
+constexpr int kAVN = kBRK + K;                  // [K]
+constexpr int kWS = kAVN + K;                   // [K]
+constexpr int kCMB = kWS + K;                   // [kMMax + 3][K]: combine coefficients
+constexpr int kScal = kCMB + (kMMax + 3) * K;
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef int i2 __attribute__((ext_vector_type(2)));
+
+template <int KP>
+__device__ __forceinline__ void ld_row(const double *__restrict__ X, int64_t row, double (&x)[KP])
+{
+    const d2 *p = reinterpret_cast<const d2 *>(X + row * KP);
+#pragma unroll
+    for (int q = 0; q < KP / 2; ++q) {
+        const d2 t = p[q];
+        x[2 * q] = t.x;
+        x[2 * q + 1] = t.y;
+    }
+}
+
+template <int KP>
+__device__ __forceinline__ void st_row(double *__restrict__ Y, int64_t row, const double (&s)[KP])
+{
+    d2 *p = reinterpret_cast<d2 *>(Y + row * KP);
+#pragma unroll
+    for (int q = 0; q < KP / 2; ++q) p[q] = d2{s[2 * q], s[2 * q + 1]};
+}
+
+// s = -(diag x): the single-vector kernels' v_mul_f64 of DIAG and x with the sign folded in
+template <int KP>
+__device__ __forceinline__ void diag_row(double dg, const double (&x)[KP], double (&s)[KP])
+{
+#pragma unroll
+    for (int c = 0; c < KP; ++c) s[c] = -(dg * x[c]);
+}
+
+// s += v x as ONE rounding per column (the single-vector kernels' v_fmac_f64)
+template <int KP>
+__device__ __forceinline__ void fma_row(double v, const double (&x)[KP], double (&s)[KP])
+{
+#pragma unroll
+    for (int c = 0; c < KP; ++c) s[c] = __builtin_fma(v, x[c], s[c]);
+}
+
+// SELL-64 row (plain or dictionary-coded columns), the slot order and addresses of row_sell / row_sell_coded
+template <int KP, bool CODED>
+__device__ __forceinline__ void row_sell_blk(const SellDev &A, const double *__restrict__ X, int64_t c, int lane,
+                                             double (&s)[KP])
+{
+    const int64_t off = A.off[c];
+    const int w = (int)((A.off[c + 1] - off) >> 6);
+    const int w2 = w >> 1;
+    const int64_t r = (c << 6) + lane;
+    double x0[KP], x1[KP];
+    ld_row<KP>(X, r, x0);
+    diag_row<KP>(A.diag[r], x0, s);
+    const double *vp = A.val + off + 2 * lane;
+    const int dtl = CODED ? __builtin_amdgcn_readfirstlane(A.dtlen[c]) : 0;
+    if (CODED && dtl != 0) {
+        const int tab = lane < dtl ? A.dtab[(c << 6) + lane] : 0;
+        const unsigned long long *cp = A.code + A.codeoff[c] + lane;
+        unsigned long long cw = *cp;
+        int used = 0;
+        auto next = [&]() -> int64_t {
+            if (used == kSellCodePerWord) {
+                cp += 64;
+                cw = *cp;
+                used = 0;
+            }
+            const int d = __builtin_amdgcn_ds_bpermute((int)(cw & 63ull) << 2, tab);
+            cw >>= kSellCodeBits;
+            ++used;
+            return r + d;
+        };
+        for (int k = 0; k < w2; ++k) {
+            const d2 v = *reinterpret_cast<const d2 *>(vp + k * 128);
+            ld_row<KP>(X, next(), x0);
+            ld_row<KP>(X, next(), x1);
+            fma_row<KP>(v.x, x0, s);
+            fma_row<KP>(v.y, x1, s);
+        }
+        if (w & 1) {
+            ld_row<KP>(X, next(), x0);
+            fma_row<KP>(A.val[off + w2 * 128 + lane], x0, s);
+        }
+        return;
+    }
+    const int32_t *cp = A.col + off + 2 * lane;
+    for (int k = 0; k < w2; ++k) {
+        const i2 cc = *reinterpret_cast<const i2 *>(cp + k * 128);
+        const d2 v = *reinterpret_cast<const d2 *>(vp + k * 128);
+        ld_row<KP>(X, cc.x, x0);
+        ld_row<KP>(X, cc.y, x1);
+        fma_row<KP>(v.x, x0, s);
+        fma_row<KP>(v.y, x1, s);
+    }
+    if (w & 1) {
+        ld_row<KP>(X, A.col[off + w2 * 128 + lane], x0);
+        fma_row<KP>(A.val[off + w2 * 128 + lane], x0, s);
+    }
+}
+
+// Banded row r: the operands rows_dia gives the row as the .x (even r) or .y (odd r) half of its pair - the pair
+// start clamped to [-1, n - 1], an empty masked segment read as 0 against the row's own x.
+template <int KP, bool MASKED>
+__device__ __forceinline__ void row_dia_blk(const DiaDev &D, const double *__restrict__ X, int64_t r, unsigned m,
+                                            double (&s)[KP])
+{
+    const int64_t ge = r & ~(int64_t)1;
+    const int par = (int)(r & 1);
+    const int64_t last = D.n - 1;
+    auto xr = [&](int64_t p) -> int64_t { return (p < -1 ? -1 : (p > last ? last : p)) + par; };
+    double x0[KP], x1[KP];
+    ld_row<KP>(X, xr(ge), x0);
+    diag_row<KP>(D.diag[r], x0, s);
+    int d = 0;
+    for (; d + 2 <= D.nd; d += 2) {
+        const bool on0 = !MASKED || ((m >> d) & 1u), on1 = !MASKED || ((m >> (d + 1)) & 1u);
+        const double v0 = on0 ? D.val[(int64_t)d * D.ld + r] : 0.0;
+        const double v1 = on1 ? D.val[(int64_t)(d + 1) * D.ld + r] : 0.0;
+        ld_row<KP>(X, xr(ge + (on0 ? D.delta[d] : 0)), x0);
+        ld_row<KP>(X, xr(ge + (on1 ? D.delta[d + 1] : 0)), x1);
+        fma_row<KP>(v0, x0, s);
+        fma_row<KP>(v1, x1, s);
+    }
+    for (; d < D.nd; ++d) {
+        const bool on0 = !MASKED || ((m >> d) & 1u);
+        const double v0 = on0 ? D.val[(int64_t)d * D.ld + r] : 0.0;
+        ld_row<KP>(X, xr(ge + (on0 ? D.delta[d] : 0)), x0);
+        fma_row<KP>(v0, x0, s);
+    }
+}
+
+struct SpmmArgs {
+    SellDev A;
+    DiaDev D;
+    const double *X;
+    double *Y;
+    const double *ua, *ub;   // DOTS: partials of ua . Y (ua may be null) and ub . Y per column
+    double *part;            // [2][kMaxGrid][K]
+    int64_t trips;
+    const int32_t *trip_order;
+    int64_t rows_red;        // rows that enter the reductions
+};
+
+// per-column sums of the block: v[c] summed over the wavefront, then the four wavefronts in a fixed order
+template <int KP>
+__device__ __forceinline__ void block_sum_cols(double (&v)[KP], double *red, double *out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < KP; ++c)
+        for (int o = 32; o >= 1; o >>= 1) v[c] += __shfl_xor(v[c], o);
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < KP; ++c) red[wave * KP + c] = v[c];
+    __syncthreads();
+    if (threadIdx.x < KP) {
+        const int c = threadIdx.x;
+        out[c] = (red[c] + red[KP + c]) + (red[2 * KP + c] + red[3 * KP + c]);
+    }
+    __syncthreads();
+}
+
+// FMT: 0 SELL-64, 5 SELL-64 with coded columns, 1 banded, 2 banded with group masks.  XCD-aware trip mapping and
+// trip order of k_spmv; a banded trip is a 128-row group taken as two 64-row halves.
+template <int KP, int FMT, bool DOTS>
+__global__ __launch_bounds__(kBlock) void k_spmm(SpmmArgs a)
+{
+    constexpr bool DIA = FMT == 1 || FMT == 2;
+    __shared__ double red[4 * KP];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int xcd = blockIdx.x & 7;
+    const int slot = blockIdx.x >> 3;
+    const int bx = gridDim.x >> 3;
+    const int64_t cpx = (a.trips + 7) >> 3;
+    const int64_t cbeg = (int64_t)xcd * cpx;
+    const int64_t cend = (cbeg + cpx < a.trips) ? cbeg + cpx : a.trips;
+    const int64_t cstep = (int64_t)bx * 4;
+    double da[KP], db[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) da[c] = db[c] = 0.0;
+    for (int64_t t = cbeg + (int64_t)slot * 4 + wave; t < cend; t += cstep) {
+        const int64_t ct = a.trip_order ? (int64_t)__builtin_amdgcn_readfirstlane(a.trip_order[t]) : t;
+        const unsigned gm = FMT == 2 ? __builtin_amdgcn_readfirstlane(a.D.gmask[ct]) : 0xFFFFFFFFu;
+        for (int h = 0; h < (DIA ? 2 : 1); ++h) {
+            const int64_t r = DIA ? (ct << 7) + h * 64 + lane : (ct << 6) + lane;
+            double s[KP];
+            if (DIA) row_dia_blk<KP, FMT == 2>(a.D, a.X, r, gm, s);
+            else row_sell_blk<KP, FMT == 5>(a.A, a.X, ct, lane, s);
+            st_row<KP>(a.Y, r, s);
+            if (DOTS && r < a.rows_red) {
+                double u[KP];
+                if (a.ua) {
+                    ld_row<KP>(a.ua, r, u);
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) da[c] = __builtin_fma(u[c], s[c], da[c]);
+                }
+                ld_row<KP>(a.ub, r, u);
+#pragma unroll
+                for (int c = 0; c < KP; ++c) db[c] = __builtin_fma(u[c], s[c], db[c]);
+            }
+        }
+    }
+    if (DOTS) {
+        block_sum_cols<KP>(da, red, a.part + (size_t)blockIdx.x * K);
+        block_sum_cols<KP>(db, red, a.part + ((size_t)kMaxGrid + blockIdx.x) * K);
+    }
+}
+
+// ---- streaming kernels over the flat array of 16-byte pairs: the grid stride is a multiple of kp/2, so a thread
+// always holds the same two columns (2q, 2q+1) with q = thread id mod kp/2
+__device__ __forceinline__ void flat_sum(double a0, double a1, int half, double *red, double *out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 32; o >= half; o >>= 1) {
+        a0 += __shfl_xor(a0, o);
+        a1 += __shfl_xor(a1, o);
+    }
+    if (lane < half) {
+        red[wave * 2 * K + 2 * lane] = a0;
+        red[wave * 2 * K + 2 * lane + 1] = a1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * half) {
+        const int c = threadIdx.x;
+        out[c] = (red[c] + red[2 * K + c]) + (red[4 * K + c] + red[6 * K + c]);
+    }
+    __syncthreads();
+}
+
+// U = W, partial: ||W_c||^2
+__global__ __launch_bounds__(kBlock) void k_bcopy_nrm(int64_t npairs, int half, const d2 *__restrict__ w, d2 *__restrict__ u,
+                                                      double *__restrict__ part)
+{
+    __shared__ double red[8 * K];
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
+        const d2 v = w[i];
+        u[i] = v;
+        a0 = __builtin_fma(v.x, v.x, a0);
+        a1 = __builtin_fma(v.y, v.y, a1);
+    }
+    flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
+}
+
+// z <- cz z - c1 u1 - c2 u2 per column; partials ||z||^2 and z . u2
+__global__ __launch_bounds__(kBlock) void k_bortho(int64_t npairs, int half, d2 *__restrict__ z, const d2 *__restrict__ u1,
+                                                   const d2 *__restrict__ u2, const double *__restrict__ co,
+                                                   double *__restrict__ part)
+{
+    __shared__ double red[8 * K];
+    const int q = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) % half);
+    const d2 cz = {co[2 * q], co[2 * q + 1]};
+    const d2 c1 = {co[K + 2 * q], co[K + 2 * q + 1]};
+    const d2 c2 = {co[2 * K + 2 * q], co[2 * K + 2 * q + 1]};
+    double s0 = 0.0, s1 = 0.0, g0 = 0.0, g1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
+        const d2 b = u2[i];
+        d2 v = z[i];
+        v.x = cz.x * v.x;
+        v.y = cz.y * v.y;
+        if (u1) {
+            const d2 a = u1[i];
+            v.x = __builtin_fma(-c1.x, a.x, v.x);
+            v.y = __builtin_fma(-c1.y, a.y, v.y);
+        }
+        v.x = __builtin_fma(-c2.x, b.x, v.x);
+        v.y = __builtin_fma(-c2.y, b.y, v.y);
+        z[i] = v;
+        s0 = __builtin_fma(v.x, v.x, s0);
+        s1 = __builtin_fma(v.y, v.y, s1);
+        g0 = __builtin_fma(v.x, b.x, g0);
+        g1 = __builtin_fma(v.y, b.y, g1);
+    }
+    flat_sum(s0, s1, half, red, part + (size_t)blockIdx.x * K);
+    flat_sum(g0, g1, half, red, part + ((size_t)kMaxGrid + blockIdx.x) * K);
+}
+
+// partial: ||z_c||^2
+__global__ __launch_bounds__(kBlock) void k_bnorm(int64_t npairs, int half, const d2 *__restrict__ z, double *__restrict__ part)
+{
+    __shared__ double red[8 * K];
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
+        const d2 v = z[i];
+        a0 = __builtin_fma(v.x, v.x, a0);
+        a1 = __builtin_fma(v.y, v.y, a1);
+    }
+    flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
+}
+
+// W = max(sum_i coef_i u_i, 0) (DGEMV :444, clamp :447-449), partial: sum W (DASUM :450)
+__global__ __launch_bounds__(kBlock) void k_bcombine(int64_t npairs, int half, const double *__restrict__ U, int64_t ldc, int mx,
+                                                     const double *__restrict__ coef, d2 *__restrict__ w, double *__restrict__ part)
+{
+    __shared__ double red[8 * K];
+    const int q = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) % half);
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
+        d2 s = {0.0, 0.0};
+        for (int j = 0; j < mx; ++j) {
+            const d2 u = reinterpret_cast<const d2 *>(U + (size_t)j * ldc)[i];
+            s.x = __builtin_fma(coef[j * K + 2 * q], u.x, s.x);
+            s.y = __builtin_fma(coef[j * K + 2 * q + 1], u.y, s.y);
+        }
+        s.x = s.x > 0.0 ? s.x : 0.0;
+        s.y = s.y > 0.0 ? s.y : 0.0;
+        w[i] = s;
+        a0 += s.x;
+        a1 += s.y;
+    }
+    flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
+}
+
+// caller's column-major block (stage[c * n + i]) -> row-interleaved rows of the internal order, and back
+__global__ __launch_bounds__(kBlock) void k_bpack(int64_t n, int k, int kp, const double *__restrict__ stage,
+                                                  const int32_t *__restrict__ perm, double *__restrict__ X)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n * kp; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t r = i / kp;
+        const int c = (int)(i - r * kp);
+        X[i] = c < k ? stage[(int64_t)c * n + (perm ? perm[r] : r)] : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_bunpack(int64_t n, int k, int kp, const double *__restrict__ X,
+                                                    const int32_t *__restrict__ iperm, double *__restrict__ stage)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n * k; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = i / n, r = i - c * n;
+        stage[i] = X[(iperm ? (int64_t)iperm[r] : r) * kp + c];
+    }
+}
+
+enum { kFinBegin = 0, kFinDots = 1, kFinNorm = 2, kFinAvn = 3, kFinWsum = 4 };
+
+// The per-column scalar work of a pass, one workgroup: 256 / K threads per column sum the block partials of the
+// two quantities in a fixed order, then one thread per column applies the Arnoldi bookkeeping of `stage`.
+__global__ __launch_bounds__(kBlock) void k_bfinal(int stage, int j, int kp, int G, const double *__restrict__ part,
+                                                   double *__restrict__ sc, double break_tol)
+{
+    constexpr int T = kBlock / K;
+    const int c = threadIdx.x / T, i = threadIdx.x % T;
+    double s0 = 0.0, s1 = 0.0;
+    for (int g = i; g < G; g += T) {
+        s0 += part[(size_t)g * K + c];
+        s1 += part[((size_t)kMaxGrid + g) * K + c];
+    }
+    for (int o = T / 2; o >= 1; o >>= 1) {
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+    }
+    if (i != 0 || c >= kp) return;
+    double *hb = sc + kHB, *nrm = sc + kNRM, *co = sc + kCO;
+    double &brk = sc[kBRK + c], &gg = sc[kGG + c];
+    switch (stage) {
+    case kFinBegin: {
+        const double n1 = sqrt(s0);
+        nrm[K + c] = n1;
+        brk = n1 > 0.0 ? 0.0 : -1.0;
+        gg = 0.0;
+        break;
+    }
+    case kFinDots: {
+        double h1 = 0.0, h2 = 0.0, cz = 0.0, c1 = 0.0, c2 = 0.0;
+        if (brk == 0.0) {
+            const double nj = nrm[j * K + c];
+            if (j >= 2) {
+                const double np = nrm[(j - 1) * K + c];
+                h1 = s0 / np / nj;                       // v_{j-1} . A v_j
+                c1 = h1 / np;
+            }
+            h2 = s1 / nj / nj - h1 * gg;                 // v_j . (A v_j - h1 v_{j-1})
+            cz = 1.0 / nj;
+            c2 = h2 / nj;
+        }
+        hb[(j * 3 + 0) * K + c] = h1;
+        hb[(j * 3 + 1) * K + c] = h2;
+        co[c] = cz;
+        co[K + c] = c1;
+        co[2 * K + c] = c2;
+        break;
+    }
+    case kFinNorm: {
+        double n1 = 0.0;
+        if (brk == 0.0) {
+            n1 = sqrt(s0);
+            const double nj = nrm[j * K + c];
+            gg = n1 > 0.0 ? s1 / n1 / nj : 0.0;
+            if (!(n1 > break_tol)) brk = (double)j;     // happy breakdown :249, this column only
+        }
+        hb[(j * 3 + 2) * K + c] = n1;
+        nrm[(j + 1) * K + c] = n1;
+        break;
+    }
+    case kFinAvn:
+        sc[kAVN + c] = brk == 0.0 ? sqrt(s0) / nrm[j * K + c] : 0.0;
+        break;
+    default:
+        sc[kWS + c] = s0;
+        break;
+    }
+}
+
+// ---- host side
+int fail(kfsp_ctx *c, int code, const char *what)
+{
+    c->err = what;
+    return code;
+}
+
+int hip_fail(kfsp_ctx *c, hipError_t e, const char *where)
+{
+    c->err = std::string(where) + ": " + hipGetErrorString(e);
+    return 1000 + (int)e;
+}
+
+#define HIP_TRY(expr)                                          \
+    do {                                                       \
+        hipError_t e_ = (expr);                                \
+        if (e_ != hipSuccess) return hip_fail(ctx, e_, #expr); \
+    } while (0)
+
+struct PhaseTimer {
+    kfsp_ctx *c;
+    int phase;
+    std::chrono::steady_clock::time_point t0;
+    PhaseTimer(kfsp_ctx *c_, int p) : c(c_), phase(p), t0(std::chrono::steady_clock::now()) {}
+    ~PhaseTimer() { c->t_ms[phase] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+int kp_of(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)); }
+
+int spmm_fmt(const kfsp_ctx *c) { return c->use_dia ? (c->dia_masked ? 2 : 1) : (c->sell_coded ? 5 : 0); }
+int64_t spmm_trips(const kfsp_ctx *c) { return c->use_dia ? (c->nchunks + 1) / 2 : c->nchunks; }
+// rows a product writes, and rows of a block column (margins included)
+int64_t rows_act(const kfsp_ctx *c) { return spmm_trips(c) * (c->use_dia ? 128 : 64); }
+int64_t col_rows(const kfsp_ctx *c) { return rows_act(c) + 2 * kMargin; }
+// doubles of one block column, and its first row
+size_t col_len(const kfsp_ctx *c, int kp) { return (size_t)col_rows(c) * (size_t)kp; }
+double *bcol(double *base, const kfsp_ctx *c, int kp, int j) { return base + (size_t)j * col_len(c, kp) + (size_t)kMargin * kp; }
+// 16-byte pairs the streaming kernels cover: the rows of the SELL-padded block, like act_pairs
+int64_t red_pairs(const kfsp_ctx *c, int kp) { return c->nchunks * kChunk * (int64_t)kp / 2; }
+
+int spmm_grid(const kfsp_ctx *c)
+{
+    const int64_t t = spmm_trips(c);
+    int64_t g = round_up((t + 3) / 4, 8);
+    g = std::min<int64_t>(g, c->opt_grid > 0 ? std::min<int64_t>(round_up(c->opt_grid, 8), kMaxGrid) : 1024);
+    return (int)std::max<int64_t>(g, 8);
+}
+
+int flat_grid(const kfsp_ctx *c, int kp)
+{
+    int64_t g = (red_pairs(c, kp) + 4 * kBlock - 1) / (4 * kBlock);
+    g = std::min<int64_t>(g, c->opt_vgrid > 0 ? std::min<int64_t>(c->opt_vgrid, kMaxGrid) : 1024);
+    return (int)std::max<int64_t>(g, 1);
+}
+
+template <int KP>
+void launch_spmm_kp(int fmt, bool dots, int g, const SpmmArgs &a, hipStream_t st)
+{
+#define KFSP_SPMM(F)                                                                                   \
+    if (dots) hipLaunchKernelGGL((k_spmm<KP, F, true>), dim3(g), dim3(kBlock), 0, st, a);              \
+    else hipLaunchKernelGGL((k_spmm<KP, F, false>), dim3(g), dim3(kBlock), 0, st, a);
+    switch (fmt) {
+    case 1: KFSP_SPMM(1) break;
+    case 2: KFSP_SPMM(2) break;
+    case 5: KFSP_SPMM(5) break;
+    default: KFSP_SPMM(0) break;
+    }
+#undef KFSP_SPMM
+}
+
+// Y = A X (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
+int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
+{
+    SpmmArgs a;
+    a.A = SellDev{ctx->nloc, ctx->nchunks, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, ctx->d_diag.p,
+                  ctx->d_dtab.p, ctx->d_dtlen.p, ctx->d_code.p, ctx->d_codeoff.p};
+    a.D.nd = ctx->nd;
+    for (int d = 0; d < kMaxDiag; ++d) a.D.delta[d] = ctx->delta[d];
+    a.D.val = ctx->d_dia.p;
+    a.D.ld = ctx->dia_ld;
+    a.D.diag = ctx->d_diag.p;
+    a.D.nchunks = ctx->nchunks;
+    a.D.n = ctx->n;
+    a.D.gmask = ctx->dia_masked ? ctx->d_gmask.p : nullptr;
+    a.D.zero = ctx->d_zero.p;
+    a.X = X;
+    a.Y = Y;
+    a.ua = ua;
+    a.ub = ub;
+    a.part = ctx->d_bpart.p;
+    a.trips = spmm_trips(ctx);
+    a.trip_order = ctx->trip_order_n == a.trips ? ctx->d_trip_order.p : nullptr;
+    a.rows_red = ctx->nchunks * kChunk;
+    const int g = spmm_grid(ctx);
+    const int fmt = spmm_fmt(ctx);
+    switch (kp) {
+    case 2: launch_spmm_kp<2>(fmt, dots, g, a, ctx->stream); break;
+    case 4: launch_spmm_kp<4>(fmt, dots, g, a, ctx->stream); break;
+    case 8: launch_spmm_kp<8>(fmt, dots, g, a, ctx->stream); break;
+    default: launch_spmm_kp<16>(fmt, dots, g, a, ctx->stream); break;
+    }
+    return g;
+}
+
+void finalize(kfsp_ctx *ctx, int stage, int j, int kp, int G, double break_tol = 0.0)
+{
+    hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, G, ctx->d_bpart.p, ctx->d_bscal.p, break_tol);
+}
+
+// the scalar and partial buffers of the block path
+int ensure_scalars(kfsp_ctx *ctx)
+{
+    HIP_TRY(ctx->d_bscal.reserve(kScal, true));
+    HIP_TRY(ctx->d_bpart.reserve((size_t)2 * kMaxGrid * K, true));
+    return 0;
+}
+
+// ncols block columns of width kp in d_bv (zeroed whenever the width changes: margins must read 0)
+int ensure_basis(kfsp_ctx *ctx, int kp, int ncols)
+{
+    const size_t need = (size_t)ncols * col_len(ctx, kp);
+    if (need > ctx->d_bv.cap) {
+        ctx->d_bv.release();
+        HIP_TRY(ctx->d_bv.reserve(need, true));
+        ctx->bv_kp = kp;
+    }
+    if (ctx->bv_kp != kp) {
+        HIP_TRY(hipMemsetAsync(ctx->d_bv.p, 0, ctx->d_bv.cap * sizeof(double), ctx->stream));
+        ctx->bv_kp = kp;
+    }
+    return ensure_scalars(ctx);
+}
+
+// host column-major (caller's order) -> zeroed block column dst (width kp, internal order)
+int upload_block(kfsp_ctx *ctx, int k, int kp, int64_t ld, const double *W, double *col0)
+{
+    const int64_t n = ctx->n;
+    HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
+    HIP_TRY(hipMemsetAsync(col0 - (size_t)kMargin * kp, 0, col_len(ctx, kp) * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(ctx->d_bstage.p, (size_t)n * sizeof(double), W, (size_t)ld * sizeof(double), (size_t)n * sizeof(double),
+                             (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n * kp + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_bpack, dim3(g), dim3(kBlock), 0, ctx->stream, n, k, kp, ctx->d_bstage.p, ctx->perm_on ? ctx->d_perm.p : nullptr, col0);
+    return 0;
+}
+
+int download_block(kfsp_ctx *ctx, int k, int kp, const double *col0, int64_t ld, double *W)
+{
+    const int64_t n = ctx->n;
+    HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n * k + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_bunpack, dim3(g), dim3(kBlock), 0, ctx->stream, n, k, kp, col0, ctx->perm_on ? ctx->d_iperm.p : nullptr, ctx->d_bstage.p);
+    HIP_TRY(hipMemcpy2DAsync(W, (size_t)ld * sizeof(double), ctx->d_bstage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+                             (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+template <class F>
+int guarded(kfsp_ctx *ctx, F &&body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, 4001, "out of host memory");
+    } catch (...) {
+        return fail(ctx, 4000, "exception inside the block path");
+    }
+}
+
+}  // namespace
+
+void block_release(kfsp_ctx *ctx)
+{
+    ctx->d_blk.release();
+    ctx->d_bv.release();
+    ctx->d_bstage.release();
+    ctx->d_bscal.release();
+    ctx->d_bpart.release();
+    ctx->blk_k = ctx->blk_kp = ctx->bv_kp = 0;
+}
+
+int block_supported(kfsp_ctx *ctx)
+{
+    if (ctx->group || ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm)
+        return fail(ctx, -12, "several vectors at once: not with a row partition (communicator or group context)");
+    if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
+    if (ctx->use_box) return fail(ctx, -12, "several vectors at once: not for a matrix-free generator (option box_store = 1 stores it)");
+    if (!ctx->use_dia && !ctx->have_sell) return fail(ctx, -12, "several vectors at once: no stored generator");
+    return 0;
+}
+
+int block_shape(kfsp_ctx *ctx, int *k, int64_t *n)
+{
+    *k = ctx->blk_k;
+    *n = ctx->n;
+    return 0;
+}
+
+int block_mmax(kfsp_ctx *ctx) { return (int)(ctx->v_mmax ? std::min(ctx->v_mmax, ctx->opt_mmax) : ctx->opt_mmax); }
+
+int block_begin(kfsp_ctx *ctx, int m, double *beta)
+{
+    PhaseTimer timer(ctx, KFSP_T_BEGIN);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int kp = ctx->blk_kp;
+    if (int rc = ensure_basis(ctx, kp, m + 2)) return rc;
+    const int g = flat_grid(ctx, kp);
+    hipLaunchKernelGGL(k_bcopy_nrm, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2,
+                       reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)),
+                       ctx->d_bpart.p);
+    finalize(ctx, kFinBegin, 1, kp, g);
+    HIP_TRY(hipMemcpyAsync(beta, ctx->d_bscal.p + kNRM + K, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nrm, int *brk, double *avnorm)
+{
+    PhaseTimer timer(ctx, KFSP_T_ARNOLDI);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int kp = ctx->blk_kp;
+    if (int rc = ensure_basis(ctx, kp, m + 2)) return rc;
+    hipStream_t st = ctx->stream;
+    const int gv = flat_grid(ctx, kp);
+    const int64_t np = red_pairs(ctx, kp);
+    double *V = ctx->d_bv.p;
+    auto u = [&](int j) { return bcol(V, ctx, kp, j - 1); };   // u_j, 1-based
+    for (int j = 1; j <= m; ++j) {
+        const int g = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true);
+        finalize(ctx, kFinDots, j, kp, g);
+        hipLaunchKernelGGL(k_bortho, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
+                           reinterpret_cast<const d2 *>(j >= 2 ? u(j - 1) : nullptr), reinterpret_cast<const d2 *>(u(j)),
+                           ctx->d_bscal.p + kCO, ctx->d_bpart.p);
+        finalize(ctx, kFinNorm, j, kp, gv, break_tol);
+    }
+    // the extra product for AVNORM (:261-263) into the scratch column
+    spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false);
+    hipLaunchKernelGGL(k_bnorm, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p);
+    finalize(ctx, kFinAvn, m + 1, kp, gv);
+    std::vector<double> h((size_t)kScal);
+    HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_bscal.p, (size_t)kCMB * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memcpy(hb, h.data() + kHB, (size_t)(kMMax + 2) * 3 * K * sizeof(double));
+    std::memcpy(nrm, h.data() + kNRM, (size_t)(kMMax + 3) * K * sizeof(double));
+    std::memcpy(avnorm, h.data() + kAVN, K * sizeof(double));
+    for (int c = 0; c < K; ++c) brk[c] = (int)h[(size_t)kBRK + c];
+    return 0;
+}
+
+int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
+{
+    PhaseTimer timer(ctx, KFSP_T_COMBINE);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int kp = ctx->blk_kp;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->d_bscal.p + kCMB, coef, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
+    const int g = flat_grid(ctx, kp);
+    hipLaunchKernelGGL(k_bcombine, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
+                       (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
+                       ctx->d_bpart.p);
+    finalize(ctx, kFinWsum, 0, kp, g);
+    HIP_TRY(hipMemcpyAsync(wsum, ctx->d_bscal.p + kWS, K * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace kfsp
+
+using namespace kfsp;
+
+extern "C" {
+
+int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_supported(ctx)) return rc;
+        if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
+        if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
+        if (ldw < n) return fail(ctx, -4, "ldw < n");
+        if (!W) return fail(ctx, -5, "null W");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int kp = kp_of(k);
+        ctx->blk_k = 0;
+        if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
+            ctx->d_blk.release();
+            HIP_TRY(ctx->d_blk.reserve(col_len(ctx, kp), false));
+        }
+        ctx->blk_kp = kp;
+        if (int rc = upload_block(ctx, k, kp, ldw, W, bcol(ctx->d_blk.p, ctx, kp, 0))) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ctx->blk_k = k;
+        return 0;
+    });
+}
+
+int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_supported(ctx)) return rc;
+        if (ctx->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
+        if (k != ctx->blk_k) return fail(ctx, -2, "k is not the number of columns of the resident block");
+        if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
+        if (ldw < n) return fail(ctx, -4, "ldw < n");
+        if (!W) return fail(ctx, -5, "null W");
+        HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = download_block(ctx, k, ctx->blk_kp, bcol(ctx->d_blk.p, ctx, ctx->blk_kp, 0), ldw, W)) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return 0;
+    });
+}
+
+int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_supported(ctx)) return rc;
+        if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
+        if (ld < ctx->n) return fail(ctx, -3, "ld < n");
+        if (!X) return fail(ctx, -4, "null X");
+        if (!Y) return fail(ctx, -5, "null Y");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int kp = kp_of(k);
+        if (int rc = ensure_basis(ctx, kp, 2)) return rc;
+        double *x = bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
+        if (int rc = upload_block(ctx, k, kp, ld, X, x)) return rc;
+        spmm(ctx, kp, x, y, nullptr, nullptr, false);
+        if (int rc = download_block(ctx, k, kp, y, ld, Y)) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return 0;
+    });
+}
+
+int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_supported(ctx)) return rc;
+        if (ctx->blk_k == 0) return fail(ctx, -1, "no block resident");
+        if (reps < 1) return fail(ctx, -2, "reps < 1");
+        if (!ms_total) return fail(ctx, -3, "null ms_total");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int kp = ctx->blk_kp;
+        if (int rc = ensure_basis(ctx, kp, 1)) return rc;
+        const double *x = bcol(ctx->d_blk.p, ctx, kp, 0);
+        double *y = bcol(ctx->d_bv.p, ctx, kp, 0);
+        HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+        for (int r = 0; r < reps; ++r) spmm(ctx, kp, x, y, nullptr, nullptr, false);
+        HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+        HIP_TRY(hipEventSynchronize(ctx->ev1));
+        HIP_TRY(hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
+        return 0;
+    });
+}
+
+}  // extern "C"

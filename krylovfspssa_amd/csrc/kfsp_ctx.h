@@ -310,6 +310,12 @@ struct kfsp_ctx {
     DevBuf<double> d_wfull;  // n: the whole compacted w between kfsp_drop_compact and the next generator (communicator)
     DevBuf<uint8_t> d_flagloc;   // L * nranks: flags of the blocks in the internal order (communicator)
 
+    // several vectors at once (kfsp_block.hip): the resident block (kp doubles per row), the block basis / scratch
+    // columns, the caller-layout staging area, per-column scalars and partials; all released when the generator changes
+    DevBuf<double> d_blk, d_bv, d_bstage, d_bscal, d_bpart;
+    int blk_k = 0, blk_kp = 0;   // columns of the resident block (0: none) and its width
+    int bv_kp = 0;               // width d_bv is laid out for
+
     // scalars
     DevBuf<double> d_part;   // kNumPartial * kMaxGrid
     DevBuf<double> d_stage;  // kNumStage
@@ -471,4 +477,6 @@ int comm_gather_bytes(kfsp_ctx *ctx, const void *send, void *recv, size_t bytes,
 int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, int32_t nr, const int32_t *stoich,
                           int32_t max_count, int32_t cap, int64_t *n_out, int64_t *n_ssa);
 void launch_zero_pad(int64_t n0, int64_t n1, double *w, hipStream_t st);
+// several vectors at once (kfsp_block.hip): drop the resident block and its buffers
+void block_release(kfsp_ctx *ctx);
 }  // namespace kfsp

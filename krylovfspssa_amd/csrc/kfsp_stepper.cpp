@@ -9,10 +9,14 @@
 // new Krylov dimension, and the FSP mass criterion with its step shrinking and
 // the hand-over to the state-space code (drop / expand callbacks).
 //
+// kfsp_expv_block is the EXPOKIT part of the same loop for a block of start vectors (kfsp_block.hip): fixed Krylov
+// dimension, one step size for all columns, no FSP criterion.
+//
 // kfsp_dgexpv_replay runs the same loop in lock step with a recorded run: every
 // decision is computed here as usual, compared with the record, and the record's
 // choice is the one carried out; differences are reported as kfsp_fork entries.
 #include "../../include/kfsp.h"
+#include "kfsp_block.h"
 
 #include <algorithm>
 #include <chrono>
@@ -571,6 +575,177 @@ extern "C" int kfsp_dgexpv_replay(kfsp_ctx *ctx, double t, double fsptol, double
 try {
     if (!replay) return -8;
     return dgexpv_impl(ctx, t, fsptol, krytol, n_reactions, ops, stats, replay);
+} catch (...) {
+    return 4000;
+}
+
+namespace {
+
+constexpr int kBK = kfsp::kBlockMaxK;
+
+// EXPOKIT's step-size control of DGEXPV_FSP (no FSP test, no dimension change) over k independent columns: the first
+// step from the largest beta (:182-187), ERR_LOC per column (:280-305), the step accepted iff the worst column passes
+// (OMEGA :314 against DELTA), the next step size from the worst column (:316-324, :336-345, :437, :540-548).
+int expv_block_impl(kfsp_ctx *ctx, double t, double tol, int32_t m_in, double *wsum, kfsp_block_stats *stats)
+{
+    if (!ctx) return -1;
+    if (int rc = kfsp::block_supported(ctx)) return rc;
+    int k = 0;
+    int64_t n = 0;
+    kfsp::block_shape(ctx, &k, &n);
+    if (k == 0) return -1;                                    // no block resident
+    if (!(t > 0.0) || !std::isfinite(t)) return -2;
+    if (!(tol > 0.0)) return -3;
+    if (m_in < 1 || m_in > kMMax || m_in > kfsp::block_mmax(ctx)) return -4;
+    if (!wsum) return -5;
+    const int m = (int)std::min<int64_t>(m_in, std::max<int64_t>(n - 1, 1));   // :211
+
+    kfsp_block_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.step_min = t;
+    double eps;                                               // :166-171
+    {
+        volatile double a = 4.0 / 3.0, b, c;
+        do {
+            b = a - 1.0;
+            c = b + b + b;
+            eps = std::fabs(c - 1.0);
+        } while (eps == 0.0);
+    }
+    const double krytol = tol <= eps ? std::sqrt(eps) : tol;
+    const double rndoff = eps;
+
+    const int mh = m + 2;
+    std::vector<double> hb((size_t)(kMMax + 2) * 3 * kBK), nrm((size_t)(kMMax + 3) * kBK), avn(kBK), beta(kBK), ws(kBK, 0.0);
+    std::vector<double> H((size_t)mh * mh), E((size_t)k * mh * mh), coef((size_t)(m + 2) * kBK);
+    std::vector<int> brk(kBK), mbrk(k), k1(k);
+    int rc = 0;
+    unsigned broke = 0;
+
+    if ((rc = kfsp::block_begin(ctx, m, beta.data()))) return rc;
+    double bmax = 0.0;
+    for (int c = 0; c < k; ++c) bmax = std::max(bmax, beta[c]);
+    double t_new = 0.0;
+    if (bmax > 0.0) {
+        const double p1 = krytol * int_power((m + 1) / 2.72, m + 1) * std::sqrt(2.0 * 3.14 * (m + 1));
+        t_new = two_digits(std::pow(p1 / (4.0 * bmax), 1.0 / (double)m), 0.55);
+    }
+    double t_now = 0.0, t_old = 0.0, omega = 0.0, omega_old = 0.0, order = 0.0;
+    bool first = true;
+    int m_old = 0;
+    while (bmax > 0.0 && t_now < t) {
+        double t_step = std::min(t - t_now, t_new);
+        if (!first) {
+            if ((rc = kfsp::block_begin(ctx, m, beta.data()))) return rc;
+            bmax = 0.0;
+            for (int c = 0; c < k; ++c) bmax = std::max(bmax, beta[c]);
+            if (!(bmax > 0.0)) break;                         // every column is 0: nothing moves any more
+        }
+        first = false;
+        ++st.nstep;
+        if ((rc = kfsp::block_arnoldi(ctx, m, kBreakTol, hb.data(), nrm.data(), brk.data(), avn.data()))) return rc;
+        st.nmult += m + 1;
+        bool all_broke = true;
+        for (int c = 0; c < k; ++c) {
+            mbrk[c] = brk[c] > 0 ? brk[c] : m;
+            k1[c] = brk[c] > 0 ? 0 : 2;
+            if (brk[c] > 0) broke |= 1u << c;
+            if (brk[c] == 0) all_broke = false;
+        }
+        if (all_broke) t_step = t - t_now;                    // every basis is exact (:254)
+        int step_rejects = 0;
+        double err = 0.0;
+        for (;;) {
+            err = 0.0;
+            for (int c = 0; c < k; ++c) {
+                if (brk[c] < 0) continue;                     // beta = 0
+                const int mx = mbrk[c] + k1[c];
+                std::fill(H.begin(), H.end(), 0.0);
+                for (int j = 1; j <= mbrk[c]; ++j) {
+                    if (j >= 2) H[(size_t)(j - 1) * mh + (j - 2)] = hb[(size_t)(j * 3 + 0) * kBK + c];
+                    H[(size_t)(j - 1) * mh + (j - 1)] = hb[(size_t)(j * 3 + 1) * kBK + c];
+                    if (j < mbrk[c] || k1[c] != 0) H[(size_t)(j - 1) * mh + j] = hb[(size_t)(j * 3 + 2) * kBK + c];
+                }
+                H[(size_t)m * mh + (m + 1)] = 1.0;            // :266
+                double *Ec = E.data() + (size_t)c * mh * mh;
+                bool null_h = true;                           // A v_1 = 0 (an absorbing state): exp(t H) = I, which
+                for (int j = 0; j < mx && null_h; ++j)        // DGPADM refuses as 'null H' (dgpadm.f:84)
+                    for (int i = 0; i < mx; ++i) null_h = null_h && H[(size_t)j * mh + i] == 0.0;
+                if (null_h) {
+                    std::fill(Ec, Ec + (size_t)mx * mx, 0.0);
+                    for (int i = 0; i < mx; ++i) Ec[(size_t)i * mx + i] = 1.0;
+                    if (k1[c] == 0) continue;
+                }
+                int ns = 0;
+                double hnorm = 0.0;
+                const auto t0 = std::chrono::steady_clock::now();
+                rc = kfsp_padm(kIdeg, mx, t_step, H.data(), mh, Ec, &ns, &hnorm);
+                kfsp_add_timer(ctx, KFSP_T_HOST_PADE, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+                if (rc) return 3000 - rc;
+                if (k1[c] == 0) continue;                     // exact: no error
+                double e;
+                const double p1 = std::fabs(Ec[(size_t)m]) * beta[c];
+                const double p2 = std::fabs(Ec[(size_t)m + 1]) * beta[c] * avn[c];
+                if (p1 > 10.0 * p2) e = p2;
+                else if (p1 > p2) e = (p1 * p2) / (p1 - p2);
+                else e = p1;
+                if (std::isnan(e) || e > err) err = e;
+                if (std::isnan(err)) break;
+            }
+            if (std::isnan(err)) {                            // :307-310
+                t_step /= 5.0;
+                continue;
+            }
+            omega_old = omega;
+            omega = err / (krytol * t_step);
+            if (m == m_old && t_step != t_old && step_rejects >= 1) order = std::max(1.0, std::log(omega / omega_old) / std::log(t_step / t_old));
+            else order = (double)m / 4.0;
+            t_old = t_step;
+            m_old = m;
+            const double remaining = t - t_now;
+            t_new = two_digits(clamp_step(remaining, t_step, kGamma * t_step * std::pow(omega, -1.0 / order)), 0.0);
+            if (!all_broke && omega > kDelta) {               // :375-399
+                ++st.nreject;
+                ++step_rejects;
+                t_step = two_digits(clamp_step(remaining, t_step, t_new), 0.55);
+                continue;
+            }
+            break;
+        }
+        if (err < 1.0e-16) t_new = std::max(t_new, 2.0 * t_step);   // :437
+        // W_c = beta_c V_c y_c with y_c = the first column of exp(t_step H_c) over MBRKDWN + max(0, K1 - 1) rows (:444)
+        std::fill(coef.begin(), coef.end(), 0.0);
+        int mxc = 1;
+        for (int c = 0; c < k; ++c) {
+            if (brk[c] < 0) continue;
+            const int mx = mbrk[c] + std::max(0, k1[c] - 1);
+            mxc = std::max(mxc, mx);
+            const double *Ec = E.data() + (size_t)c * mh * mh;
+            for (int i = 0; i < mx; ++i) coef[(size_t)i * kBK + c] = beta[c] * Ec[i] / nrm[(size_t)(i + 1) * kBK + c];
+        }
+        if ((rc = kfsp::block_combine(ctx, mxc, coef.data(), ws.data()))) return rc;
+        t_now += t_step;
+        if (t_now >= t) break;                                // (STEP_MIN/MAX skip the last step, :506)
+        err = std::max(err, rndoff);
+        st.step_min = std::min(st.step_min, t_step);
+        st.step_max = std::max(st.step_max, t_step);
+        st.s_error += err;
+        st.x_error = std::max(st.x_error, err);
+        t_new = two_digits(t_new, 0.55);
+    }
+    if (!(bmax > 0.0)) t_now = t;                             // a zero block is its own solution
+    for (int c = 0; c < k; ++c) wsum[c] = ws[c];
+    for (int c = 0; c < k; ++c) st.n_breakdown_cols += (broke >> c) & 1u;
+    st.t_now = t_now;
+    if (stats) *stats = st;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int kfsp_expv_block(kfsp_ctx *ctx, double t, double tol, int32_t m, double *wsum, kfsp_block_stats *stats)
+try {
+    return expv_block_impl(ctx, t, tol, m, wsum, stats);
 } catch (...) {
     return 4000;
 }

@@ -96,6 +96,11 @@ def load_library():
         "kfsp_add_timer": [vp, C.c_int, dbl],
         "kfsp_get_timers": [vp, vp, C.c_int],
         "kfsp_set_option": [vp, C.c_char_p, i64],
+        "kfsp_set_block": [vp, i32, i64, i64, vp],
+        "kfsp_get_block": [vp, i32, i64, i64, vp],
+        "kfsp_spmm": [vp, i32, i64, vp, vp],
+        "kfsp_expv_block": [vp, dbl, dbl, i32, vp, vp],
+        "kfsp_spmm_bench": [vp, C.c_int, C.POINTER(C.c_float)],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -127,6 +132,26 @@ class SolveStats(C.Structure):
                                          "n_wsum", "n_expand", "n_drop_calls")] + \
                [(k, C.c_double) for k in ("step_min", "step_max", "x_error", "s_error", "tbrkdwn", "t_now",
                                           "hump", "beta")]
+
+
+class BlockStats(C.Structure):
+    """kfsp_block_stats (include/kfsp.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("nstep", "nreject", "nmult", "n_breakdown_cols")] + \
+               [(k, C.c_double) for k in ("t_now", "step_min", "step_max", "x_error", "s_error")]
+
+
+BLOCK_K_MAX = 16
+
+
+def _block_columns(W, n):
+    """W of shape (n, k) with 1 <= k <= 16 -> a column-major float64 copy; checked before any library call."""
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != n:
+        raise ValueError(f"block must have shape (n, k) with n = {n}, got {W.shape}")
+    k = W.shape[1]
+    if not 1 <= k <= BLOCK_K_MAX:
+        raise ValueError(f"block needs 1 <= k <= {BLOCK_K_MAX} columns, got {k}")
+    return np.asfortranarray(W), k
 
 
 def padm(H, t, ideg=6):
@@ -624,6 +649,44 @@ class KfspContext:
         t = np.zeros(len(T_NAMES))
         self._chk(self._lib.kfsp_get_timers(self._h, _p(t), int(reset)), "kfsp_get_timers")
         return dict(zip(T_NAMES, t.tolist()))
+
+    # -- several vectors at once
+    def set_block(self, W):
+        """k start vectors as the columns of W (shape n x k, 1 <= k <= 16), caller's state order."""
+        Wf, k = _block_columns(W, self.n)
+        self._chk(self._lib.kfsp_set_block(self._h, k, self.n, self.n, _p(Wf)), "kfsp_set_block")
+        self.block_k = k
+
+    def get_block(self):
+        k = getattr(self, "block_k", 0)
+        if not 1 <= k <= BLOCK_K_MAX:
+            raise KfspError("no block was set on this context")
+        W = np.empty((self.n, k), dtype=np.float64, order="F")
+        self._chk(self._lib.kfsp_get_block(self._h, k, self.n, self.n, _p(W)), "kfsp_get_block")
+        return W
+
+    def spmm(self, X):
+        """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j])."""
+        Xf, k = _block_columns(X, self.n)
+        Y = np.empty((self.n, k), dtype=np.float64, order="F")
+        self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm")
+        return Y
+
+    def expv_block(self, t, tol, m=30):
+        """W <- exp(t A) W for the resident block -> (wsum[k], BlockStats)."""
+        k = getattr(self, "block_k", 0)
+        if not 1 <= k <= BLOCK_K_MAX:
+            raise KfspError("no block was set on this context")
+        ws = np.zeros(BLOCK_K_MAX, dtype=np.float64)
+        st = BlockStats()
+        self._chk(self._lib.kfsp_expv_block(self._h, float(t), float(tol), int(m), _p(ws), C.byref(st)), "kfsp_expv_block")
+        return ws[:k].copy(), st
+
+    def spmm_bench(self, reps):
+        """ms for reps block products on the resident block"""
+        ms = C.c_float(0.0)
+        self._chk(self._lib.kfsp_spmm_bench(self._h, int(reps), C.byref(ms)), "kfsp_spmm_bench")
+        return ms.value
 
     def set_option(self, name, value):
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
