@@ -2,11 +2,12 @@
 column, bit for bit, on every stored format; the block solve matches dense exp(tA) column by column, its columns are
 independent, and nothing of the single-vector path changes.  Needs a real MI355X."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import scipy.linalg as sl
+
+from tests import block_generators
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,7 @@ def _ctx():
 
 
 def _golden_toggle(golden_dir):
-    return np.load(os.path.join(golden_dir, "assembly_toggle_k20.npz"))
+    return block_generators.golden_toggle(golden_dir)
 
 
 def _csr_of_box(mdl):
@@ -35,65 +36,18 @@ def _dense(ctx, n):
     return np.column_stack([ctx.spmv(np.eye(n)[:, i]) for i in range(n)])
 
 
-# ---- generators, each with the kernel format it must end up in (kfsp_layout_info v[0])
+# ---- generators (tests/block_generators.py), each with the kernel format it must end up in (kfsp_layout_info v[0])
 def _sell(ctx, golden_dir):
-    g = _golden_toggle(golden_dir)
-    ctx.set_option("format", 1)
-    ctx.set_option("sell_code", 0)
-    ctx.set_matrix_ell(g["adj"], g["offdiag"], g["diag"])
-    return 0
+    return block_generators.sell(ctx, golden_dir)[0]
 
 
-def _sell_coded(ctx, golden_dir):
-    from krylovfspssa_amd import synth
-    ctx.set_option("format", 1)
-    ctx.set_option("sell_code", 1)
-    ctx.set_matrix_ell(*synth.toggle(60, 50).ell())
-    return 5
-
-
-def _banded(ctx, golden_dir):
-    from krylovfspssa_amd import synth
-    mdl = synth.toggle(60, 50)
-    ctx.set_option("dia_mask", 0)
-    ctx.set_matrix_csr(mdl.n, *_csr_of_box(mdl))
-    return 1
-
-
-def _masked(ctx, golden_dir):
-    from krylovfspssa_amd import synth
-    mdl = synth.toggle(1000, 3)            # the +-1000 diagonals are empty on a third of the rows each
-    ctx.set_matrix_csr(mdl.n, *_csr_of_box(mdl))
-    return 2
-
-
-def _ordered(ctx, golden_dir):
-    """40 000 states handed over in a shuffled order with their coordinates: the internal state order takes over"""
-    from krylovfspssa_amd import synth
-    mdl = synth.toggle(200, 200)
-    adj, off, diag = mdl.ell()
-    perm = np.random.default_rng(11).permutation(mdl.n)          # caller's state i = box state perm[i]
-    inv = np.empty_like(perm)
-    inv[perm] = np.arange(mdl.n)
-    adj2 = adj[perm].copy()
-    ok = adj2 > 0
-    adj2[ok] = inv[adj2[ok] - 1] + 1
-    state = np.stack(mdl.coords(perm.astype(np.int64)), axis=1).astype(np.int32)
-    ctx.set_option("state_order_products", 0)
-    ctx.set_state_coords(state)
-    ctx.set_matrix_ell(adj2, off[perm], diag[perm])
-    assert ctx.state_order_active()
-    return None
-
-
-GENERATORS = {"sell": _sell, "sell_coded": _sell_coded, "banded": _banded, "masked_banded": _masked,
-              "state_order": _ordered}
+GENERATORS = block_generators.GENERATORS
 
 
 @pytest.mark.parametrize("kind", list(GENERATORS))
 def test_spmm_is_spmv_column_by_column_bit_for_bit(golden_dir, kind):
     with _ctx() as ctx:
-        fmt = GENERATORS[kind](ctx, golden_dir)
+        fmt, _ = GENERATORS[kind](ctx, golden_dir)
         if fmt is not None:
             assert ctx.layout_info()["format"] == fmt, (kind, ctx.layout_info())
         n = ctx.n

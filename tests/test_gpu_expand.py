@@ -5,48 +5,13 @@ the host walk, tests/test_gpu_onestep.py against the reference's assemblies) - g
 same states in the same order, the same links, the same propensity columns; the resident vector padded with zeros; the
 rebuilt generator's products bit-identical to those of a generator uploaded from the downloaded lists.  Then a whole
 cycle drop -> rebuild -> expand, all on the device."""
-import os
 
 import numpy as np
 import pytest
 
+from tests.expand_helpers import grown as _grown, mass_action as _mass_action
+
 pytestmark = pytest.mark.gpu
-
-
-def _stoich(a):
-    nr = a["adj"].shape[1]
-    nu = [None] * nr
-    for i, row in enumerate(a["adj"]):
-        for r, j in enumerate(row):
-            if j > 0 and nu[r] is None:
-                nu[r] = a["state"][j - 1] - a["state"][i]
-    assert all(v is not None for v in nu)
-    return np.array(nu, dtype=np.int32)
-
-
-def _mass_action(nu):
-    """a_k = c_k * prod of the species reaction k consumes (postfix code of kfsp_set_propensity_program; + - * / only:
-    the device's columns are the same bits wherever they are made)"""
-    nr, ns = nu.shape
-    MUL = 5
-    progs, params = [], []
-    for k in range(nr):
-        params.append(0.05 + 0.01 * k)
-        code = [100 + ns + 1 + k]
-        for s in range(ns):
-            if nu[k, s] < 0:
-                code += [100 + s + 1, MUL]
-        progs.append((code, []))
-    return np.array(params), progs
-
-
-def _grown(c, name, golden_dir, sweeps):
-    a = np.load(os.path.join(golden_dir, f"assembly_{name}.npz"))
-    nu = _stoich(a)
-    state, adj = a["state"], a["adj"]
-    for _ in range(sweeps):
-        state, adj = c.onestep(nu, state, adj)
-    return nu, state, adj
 
 
 def _host_composition(c, t, seed, nu, state, adj, off, diag):
