@@ -1,5 +1,6 @@
 """TEST HELPER - a grown FSP from a reference assembly and a mass-action propensity program for it (tests/test_gpu_expand.py,
-tests/test_gpu_block_reference.py)."""
+tests/test_gpu_block_reference.py), and the one-step sweep restated in plain Python (tests/test_gpu_onestep.py,
+tests/test_gpu_ssa_reference.py)."""
 import os
 
 import numpy as np
@@ -39,3 +40,35 @@ def grown(c, name, golden_dir, sweeps):
     for _ in range(sweeps):
         state, adj = c.onestep(nu, state, adj)
     return nu, state, adj
+
+
+def onestep_py(nu, state, adj, max_count):
+    """ONESTEP_EXTENDER restated in plain Python (StateSpace.f90:347-396 with ADD_STATE :136-246): the open links
+    of the listed states in (state, reaction) order, a target appended the first time it is named, then the
+    appended states' own columns"""
+    nr, ns = nu.shape
+    state = [tuple(int(v) for v in s) for s in state]
+    adj = [[int(v) for v in r] for r in adj]
+    idx = {s: i + 1 for i, s in enumerate(state)}
+    n0 = len(state)
+    for j in range(n0):
+        for k in range(nr):
+            if adj[j][k] != 0:
+                continue
+            y = tuple(state[j][s] + int(nu[k, s]) for s in range(ns))
+            if min(y) < 0:
+                adj[j][k] = -1
+            elif max(y) > max_count:
+                pass
+            elif y in idx:
+                adj[j][k] = idx[y]
+            else:
+                state.append(y)
+                idx[y] = len(state)
+                adj.append([0] * nr)
+                adj[j][k] = len(state)
+    for i in range(n0, len(state)):
+        for k in range(nr):
+            y = tuple(state[i][s] + int(nu[k, s]) for s in range(ns))
+            adj[i][k] = -1 if min(y) < 0 else (0 if max(y) > max_count else idx.get(y, 0))
+    return np.array(state, dtype=np.int32).reshape(-1, ns), np.array(adj, dtype=np.int32).reshape(-1, nr)

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.expand_helpers import onestep_py as _onestep_py
+
 pytestmark = pytest.mark.gpu
 
 CASES = [("toggle", 5, 10), ("toggle", 10, 20), ("repressilator", 5, 10), ("goutsias", 5, 10), ("goutsias", 10, 16)]
@@ -76,38 +78,6 @@ def test_columns_that_arrive_unlinked_are_completed(golden_dir, name, k0, k1):
         s_new, a_new = c.onestep(nu, state, open_adj)
     assert np.array_equal(s_new, s_ref)
     assert np.array_equal(a_new, a_ref)
-
-
-def _onestep_py(nu, state, adj, max_count):
-    """ONESTEP_EXTENDER restated in plain Python (StateSpace.f90:347-396 with ADD_STATE :136-246): the open links
-    of the listed states in (state, reaction) order, a target appended the first time it is named, then the
-    appended states' own columns"""
-    nr, ns = nu.shape
-    state = [tuple(int(v) for v in s) for s in state]
-    adj = [[int(v) for v in r] for r in adj]
-    idx = {s: i + 1 for i, s in enumerate(state)}
-    n0 = len(state)
-    for j in range(n0):
-        for k in range(nr):
-            if adj[j][k] != 0:
-                continue
-            y = tuple(state[j][s] + int(nu[k, s]) for s in range(ns))
-            if min(y) < 0:
-                adj[j][k] = -1
-            elif max(y) > max_count:
-                pass
-            elif y in idx:
-                adj[j][k] = idx[y]
-            else:
-                state.append(y)
-                idx[y] = len(state)
-                adj.append([0] * nr)
-                adj[j][k] = len(state)
-    for i in range(n0, len(state)):
-        for k in range(nr):
-            y = tuple(state[i][s] + int(nu[k, s]) for s in range(ns))
-            adj[i][k] = -1 if min(y) < 0 else (0 if max(y) > max_count else idx.get(y, 0))
-    return np.array(state, dtype=np.int32).reshape(-1, ns), np.array(adj, dtype=np.int32).reshape(-1, nr)
 
 
 def test_random_networks_against_the_plain_restatement():

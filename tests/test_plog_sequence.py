@@ -7,26 +7,7 @@ import math
 
 import numpy as np
 
-
-def plog(x):
-    m, e = math.frexp(x)                       # x = m 2^e, m in [0.5, 1)
-    if m < 0.70710678118654752440:
-        m = m + m
-        e = e - 1
-    f = m - 1.0
-    s = f / (2.0 + f)
-    z = s * s
-    p = 1.0 / 23.0
-    for k in range(21, 2, -2):
-        p = p * z
-        p = p + 1.0 / float(k)
-    p = p * z
-    two_s = s + s
-    r = two_s + two_s * p
-    de = float(e)
-    hi = de * 6.93147180369123816490e-01
-    lo = de * 1.90821492927058770002e-10
-    return hi + (lo + r)
+from tests.ssa_ref import plog
 
 
 def test_fixed_sequence_logarithm_is_a_logarithm():
