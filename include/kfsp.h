@@ -178,7 +178,8 @@ int kfsp_matrix_info(const kfsp_ctx *ctx, int64_t *nrows, int64_t *slots, int64_
  * offsets) + 24 B per row (DIAG, x once, y).  x re-fetches are not in it; the rocprofv3 counters
  * are.  force_sell = 1: the figure for kfsp_spmv_bench variant 2; 3: for variant 3 (plain columns).
  * SELL-64 with dictionary-coded columns (format 5): coded chunks count 8 B per entry + their code words + their
- * offset tables (in 64-byte lines) instead of 12 B per entry. */
+ * offset tables (in 64-byte lines) instead of 12 B per entry.  Banded with dictionary-coded values (kfsp_dia_code_info
+ * v[6] = 1): rows x (24 + record bytes) + the dictionaries. */
 int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes);
 /* what the device holds and how a partitioned product exchanges its source vector, v[8]:
  *   v[0] kernel format: 0 SELL-64, 1 banded, 2 banded with group masks, 3 / 4 matrix-free box (interpreted / fast path),
@@ -188,6 +189,20 @@ int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes);
  *   v[3] reach max |col - row| of the local SELL rows (-1: not a SELL generator)
  *   v[4] chunks with coded columns, v[5] chunks, v[6] 64-bit code words, v[7] internal state order active */
 int kfsp_layout_info(const kfsp_ctx *ctx, int64_t *v);
+/* The dictionary-coded image of a banded generator's values (option "dia_code", kernel format 9 inside the library;
+ * kfsp_layout_info keeps answering 1), v[24]:
+ *   v[0] bits per code, 8 or 16 (0: no coded image is resident), v[1] bytes per row record (8 / 16), v[2] record bytes one
+ *   product reads, v[3] bytes of all dictionaries, v[4] stored diagonals, v[5] microseconds the last build (or the attempt)
+ *   took, v[6] 1 when the product kernel reads the coded image (unmasked, no communicator), v[7] 0,
+ *   v[8 + d] distinct values of diagonal d (counting stops soon after 5120; 0: not counted).
+ * A group context answers for its first rank. */
+int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v);
+/* dictionary of diagonal d of that image, ascending as unsigned 64-bit patterns: *count entries, copied to dict (cap entries
+ * of room) unless dict is null */
+int kfsp_dia_code_dict(kfsp_ctx *ctx, int32_t d, int64_t cap, double *dict, int64_t *count);
+/* the rule that picks the code width (host only): distinct[nd] values per diagonal and the LDS bytes the dictionaries may
+ * take (< 0: the library's 40 KB) -> *width 8, 16 or 0 (no coded image) and the record bytes */
+int kfsp_dia_code_rule(int32_t nd, const int64_t *distinct, int64_t lds_bytes, int32_t *width, int32_t *rec_bytes);
 /* How the rebuilds of a RESIDENT FSP went (kfsp_expand_resident, kfsp_drop_rebuild; option "build_speculate"), v[6]:
  *   v[0] generators built without stopping for the link statistics and the slot count, v[1] of those (or of the speculative
  *   state orders before them) repeated the slow way because a check at the end failed - a coordinate range crossed a power of
@@ -594,7 +609,10 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * even when no state order is derived from them - kfsp_expand_resident needs them; default 0), "ssa_resident" (1: the caller vouches that the FSP arrays handed to kfsp_ssa_streams are the ones of its last
  * kfsp_update_matrix_ell / kfsp_set_state_coords: they are taken from the device's copies instead of being uploaded again; default 0),
  * "sell_code" (dictionary-coded SELL columns, DESIGN.md 4.1c: -1 auto = under the internal state order,
- * 0 never, 1 always try), "m_max" (largest Krylov dimension the basis is allocated for, default and maximum 100 = M_MAX of
+ * 0 never, 1 always try), "dia_code" (dictionary-coded values of a banded generator, DESIGN.md 4.1e: per diagonal the distinct
+ * doubles once, per row one 8- or 16-bit code per diagonal; bit-identical products from 8 or 16 B per row instead of 8 B per
+ * stored entry; -1, default: generators whose value streams exceed 192 MiB, single rank, unmasked; 0 never; 1 always try),
+ * "m_max" (largest Krylov dimension the basis is allocated for, default and maximum 100 = M_MAX of
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "box_pencil" (-1, default: a matrix-free box whose slowest species is

@@ -105,12 +105,16 @@ int vec_grid(const kfsp_ctx *c)
     return (int)std::max<int64_t>(g, 1);
 }
 
+// the product reads the dictionary-coded image of the banded values (kernel format 9): unmasked, single rank, stored
+bool dia_code_on(const kfsp_ctx *c) { return c->use_dia && !c->use_box && c->dia_coded && !c->dia_masked && !c->use_comm; }
+
 bool use_nt(const kfsp_ctx *c)
 {
     if (c->opt_nt >= 0) return c->opt_nt != 0;
     // stream the generator around the caches only when it cannot stay in the
     // 256 MiB Infinity Cache between two products anyway
-    const double bytes = c->use_dia ? (double)c->nd * c->dia_ld * 8.0 : (double)c->slots * 12.0;
+    const double bytes = dia_code_on(c) ? (double)c->dia_code_rec * c->dia_ld
+                                        : (c->use_dia ? (double)c->nd * c->dia_ld * 8.0 : (double)c->slots * 12.0);
     return bytes > 192.0 * 1024 * 1024;
 }
 
@@ -140,6 +144,11 @@ void set_matrix_args(const kfsp_ctx *c, SpmvArgs &a)
     a.D.n = c->n;
     a.D.gmask = c->dia_masked ? c->d_gmask.p : nullptr;
     a.D.zero = c->d_zero.p;
+    a.C.rec = c->d_dcode.p;
+    a.C.dict = c->d_ddict.p;
+    for (int d = 0; d <= kMaxDiag; ++d) a.C.doff[d] = c->dia_doff[d];
+    a.C.w = c->dia_code_w;
+    a.C.rec_bytes = c->dia_code_rec;
     if (c->use_box) a.B = c->box;
     else a.B.ns = a.B.nr = a.B.ntab = 0;
     a.box_tab = c->d_box.p;
@@ -303,7 +312,8 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     a.row0 = ctx->row0;
 
     const int fmt = (ctx->use_box && dia) ? (ctx->box_fast && !ctx->opt_box_generic ? 4 : 3)
-                                          : (dia ? (ctx->dia_masked ? 2 : 1) : (ctx->sell_coded && !force_plain_sell ? 5 : 0));
+                                          : (dia ? (dia_code_on(ctx) ? 9 : (ctx->dia_masked ? 2 : 1))
+                                                 : (ctx->sell_coded && !force_plain_sell ? 5 : 0));
     const int64_t H = ctx->halo, L = ctx->L;
     const int64_t trip_rows = dia ? 128 : 64;
     int64_t lo = 0, hi = 0;
@@ -634,6 +644,7 @@ int maybe_upload_dia(kfsp_ctx *ctx, const HostSell &S, const std::vector<int32_t
 {
     ctx->use_dia = false;
     ctx->dia_masked = false;
+    ctx->dia_coded = false;
     ctx->nd = 0;
     if (ctx->opt_format == 1 || ctx->nloc == 0) return 0;
     const int64_t nloc = ctx->nloc, row0 = ctx->row0;
@@ -676,7 +687,8 @@ int maybe_upload_dia(kfsp_ctx *ctx, const HostSell &S, const std::vector<int32_t
     ctx->dia_ld = ld;
     for (int d = 0; d < nd; ++d) ctx->delta[d] = (int32_t)delta[d];
     ctx->use_dia = true;
-    return kfsp::build_dia_mask(ctx);
+    if (int rc = kfsp::build_dia_mask(ctx)) return rc;
+    return kfsp::build_dia_code(ctx);
 }
 
 // ---- the caller's state order <-> what the device keeps ----------------------------------------------
@@ -919,6 +931,7 @@ int kfsp_destroy(kfsp_ctx *ctx)
     ctx->d_dtab.release(); ctx->d_dtlen.release(); ctx->d_code.release(); ctx->d_codeoff.release(); ctx->d_trip_order.release();
     ctx->d_part.release(); ctx->d_stage.release(); ctx->d_H.release(); ctx->d_sq.release();
     ctx->d_y.release(); ctx->d_flag.release(); ctx->d_g.release(); ctx->d_dia.release();
+    ctx->d_dcode.release(); ctx->d_dhash.release(); ctx->d_ddict.release();
     ctx->d_ell_adj.release(); ctx->d_ell_off.release(); ctx->d_ell_diag.release(); ctx->d_cnt.release();
     ctx->d_ticket.release(); ctx->d_slot.release(); ctx->d_scan.release(); ctx->d_strip.release();
     ctx->d_dropflag.release(); ctx->d_dropcnt.release(); ctx->d_box.release(); ctx->d_os1.release(); ctx->d_os2.release();
@@ -1450,6 +1463,7 @@ int kfsp_set_matrix_box(kfsp_ctx *ctx, int32_t ns, const int32_t *dims, int32_t 
         ctx->use_box = true;
         ctx->ell_cols = 0;
         ctx->dia_masked = false;
+        ctx->dia_coded = false;
         ctx->have_sell = false;
         ctx->sell_coded = false;
         ctx->nd = nr;
@@ -1464,6 +1478,7 @@ int kfsp_set_matrix_box(kfsp_ctx *ctx, int32_t ns, const int32_t *dims, int32_t 
             ctx->box_fast = false;
             ctx->box_lds_bytes = 0;
             if (int rc = kfsp::build_dia_mask(ctx)) return rc;
+            if (int rc = kfsp::build_dia_code(ctx)) return rc;
         }
         if (int rc = setup_exchange(ctx)) return rc;
         if (int rc = adopt_pending_vector(ctx)) return rc;
@@ -1541,6 +1556,9 @@ int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes)
     int64_t b = rows * 24;                                    // diag, x (once), y
     if (ctx->use_box && !force_sell) {
         b = rows * 16 + (int64_t)ctx->box_lds_bytes;          // x once, y; the tables are read once per workgroup from cache
+    } else if (dia_code_on(ctx) && !force_sell) {
+        // what the coded kernel moves: one record per row instead of nd doubles, the dictionaries once
+        b += rows * ctx->dia_code_rec + (int64_t)ctx->dia_doff[ctx->nd] * 8;
     } else if (ctx->use_dia && !force_sell) {
         b += (int64_t)ctx->nd * ctx->dia_ld * 8;
         if (ctx->dia_masked) b += (ctx->dia_ld >> 7) * 4 - ctx->dia_empty_segments * 128 * 8;
@@ -1569,6 +1587,49 @@ int kfsp_layout_info(const kfsp_ctx *ctx, int64_t *v)
     v[5] = ctx->nchunks;
     v[6] = ctx->sell_coded ? ctx->code_words : 0;
     v[7] = ctx->perm_on ? 1 : 0;
+    return 0;
+}
+
+int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v)
+{
+    if (!ctx) return -1;
+    if (!v) return -2;
+    if (ctx->group) ctx = kfsp::group_rank0(ctx);
+    const bool have = ctx->use_dia && !ctx->use_box && ctx->dia_coded;
+    v[0] = have ? ctx->dia_code_w : 0;
+    v[1] = have ? ctx->dia_code_rec : 0;
+    v[2] = have ? ctx->nchunks * kChunk * ctx->dia_code_rec : 0;
+    v[3] = have ? (int64_t)ctx->dia_doff[ctx->nd] * 8 : 0;
+    v[4] = ctx->use_dia && !ctx->use_box ? ctx->nd : 0;
+    v[5] = ctx->dia_code_us;
+    v[6] = dia_code_on(ctx) ? 1 : 0;
+    v[7] = 0;
+    for (int d = 0; d < kMaxDiag; ++d) v[8 + d] = ctx->use_dia && d < ctx->nd ? ctx->dia_distinct[d] : 0;
+    return 0;
+}
+
+int kfsp_dia_code_dict(kfsp_ctx *ctx, int32_t d, int64_t cap, double *dict, int64_t *count)
+{
+    if (!ctx) return -1;
+    if (!count) return -4;
+    if (ctx->group) ctx = kfsp::group_rank0(ctx);
+    if (!(ctx->use_dia && !ctx->use_box && ctx->dia_coded)) return fail(ctx, -1, "no coded banded image");
+    if (d < 0 || d >= ctx->nd) return fail(ctx, -2, "no such diagonal");
+    const int64_t n = ctx->dia_doff[d + 1] - ctx->dia_doff[d];
+    *count = n;
+    if (!dict) return 0;
+    if (cap < n) return fail(ctx, -3, "dictionary does not fit");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpy(dict, ctx->d_ddict.p + ctx->dia_doff[d], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int kfsp_dia_code_rule(int32_t nd, const int64_t *distinct, int64_t lds_bytes, int32_t *width, int32_t *rec_bytes)
+{
+    if (!distinct || !width || !rec_bytes) return -1;
+    int rec = 0;
+    *width = kfsp::dia_code_rule(nd, distinct, lds_bytes < 0 ? kfsp::kDiaCodeLds : lds_bytes, &rec);
+    *rec_bytes = *width ? rec : 0;
     return 0;
 }
 
@@ -2573,6 +2634,7 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "box_pencil") ctx->opt_box_pencil = value;
     else if (k == "box_slab_waves") ctx->opt_box_slab_waves = value;
     else if (k == "sell_code") ctx->opt_sell_code = value;
+    else if (k == "dia_code") ctx->opt_dia_code = value;
     else if (k == "ssa_resident") ctx->opt_ssa_resident = value;
     else if (k == "keep_coords") ctx->opt_keep_coords = value;
     else if (k == "ssa_general") ctx->opt_ssa_general = value;

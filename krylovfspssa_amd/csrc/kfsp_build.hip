@@ -621,6 +621,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
     if (spec) {
         ctx->use_dia = false;
         ctx->dia_masked = false;
+        ctx->dia_coded = false;
         ctx->nd = 0;
         ctx->have_sell = false;
         ctx->sell_coded = false;
@@ -665,6 +666,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
 
     ctx->use_dia = false;
     ctx->dia_masked = false;
+    ctx->dia_coded = false;
     ctx->nd = 0;
     ctx->have_sell = false;
     ctx->sell_coded = false;
@@ -695,7 +697,8 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         for (int d = 0; d < nd; ++d) ctx->delta[d] = D.delta[d];
         ctx->use_dia = true;
         ctx->slots = 0;
-        return build_dia_mask(ctx);
+        if (int rc = build_dia_mask(ctx)) return rc;
+        return build_dia_code(ctx);
     }
 
     // SELL-64
@@ -780,6 +783,192 @@ int build_dia_mask(kfsp_ctx *ctx)
     // the masked variant trades a little address arithmetic for the skipped bytes: worth it from ~3 % on
     ctx->dia_masked = (double)empty >= 0.03 * (double)ctx->nd * (double)ngroups;
     ctx->dia_empty_segments = (int64_t)empty;
+    return 0;
+}
+
+// ---- dictionary-coded values of the banded image (kernel format 9; DiaCodeDev in kfsp_internal.h) ------------------
+// 1. k_dia_dict_scan: every stored value (all ld rows of every diagonal, padding included) is looked up in, or inserted
+//    into, its diagonal's open-addressing table of 64-bit patterns.  A generator of propensities finds its few hundred
+//    patterns at once and the rest of the pass is cached reads.  A generator of arbitrary values passes the cap within
+//    the first few thousand rows: the stop flag ends the pass there - no sort, no second look at the matrix.
+// 2. k_dia_dict_sort: one workgroup per diagonal gathers the table's entries and ranks them as unsigned integers
+//    (<= kDictCap entries: a rank sort in place of a library call) - the dictionary does not depend on the insertion races.
+// 3. k_dia_encode: a lane per row finds every value's code by bisection of the dictionaries (in LDS) and writes the record.
+constexpr unsigned long long kDictEmpty = ~0ull;   // a free table slot; a matrix that STORES this NaN pattern is not coded
+constexpr int kDictSlots = 16384;                  // table slots per diagonal
+constexpr int kDictCap = kDiaCodeLds / 8;          // a diagonal with more distinct values cannot fit the LDS budget anyway
+struct DictCount {
+    unsigned int n[kMaxDiag];                      // distinct patterns per diagonal (counting stops beyond kDictCap)
+    unsigned int stop;
+};
+
+__global__ __launch_bounds__(kBlock) void k_dia_dict_scan(int64_t ld, int nd, const double *__restrict__ val,
+                                                          unsigned long long *__restrict__ table, DictCount *__restrict__ cnt)
+{
+    volatile unsigned int *stop = &cnt->stop;
+    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < ld; r += (int64_t)gridDim.x * kBlock) {
+        if (*stop) return;
+        for (int d = 0; d < nd; ++d) {
+            const unsigned long long v = (unsigned long long)__double_as_longlong(val[(int64_t)d * ld + r]);
+            if (v == kDictEmpty) {
+                *stop = 2u;
+                return;
+            }
+            unsigned long long *t = table + (size_t)d * kDictSlots;
+            unsigned int h = (unsigned int)((v * 0x9E3779B97F4A7C15ull) >> 40) & (kDictSlots - 1);
+            for (int probe = 0;; ++probe) {
+                unsigned long long cur = *(volatile unsigned long long *)(t + h);
+                if (cur == v) break;
+                if (cur == kDictEmpty) {
+                    if (*(volatile unsigned int *)&cnt->n[d] > (unsigned int)kDictCap) {
+                        *stop = 1u;
+                        return;
+                    }
+                    cur = atomicCAS(t + h, kDictEmpty, v);
+                    if (cur == kDictEmpty) {
+                        if (atomicAdd(&cnt->n[d], 1u) >= (unsigned int)kDictCap) *stop = 1u;
+                        break;
+                    }
+                    if (cur == v) break;
+                }
+                h = (h + 1) & (kDictSlots - 1);
+                if (probe >= kDictSlots || ((probe & 31) == 31 && *stop)) {
+                    *stop = 1u;
+                    return;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_dia_dict_sort(const unsigned long long *__restrict__ table, unsigned long long *__restrict__ tmp,
+                                                          DiaCodeDev C, unsigned long long *__restrict__ dict)
+{
+    __shared__ int cnt;
+    const int d = blockIdx.x;
+    const unsigned long long *t = table + (size_t)d * kDictSlots;
+    unsigned long long *list = tmp + (size_t)d * kDictSlots;
+    const int n = C.doff[d + 1] - C.doff[d];
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < kDictSlots; i += kBlock) {
+        const unsigned long long v = t[i];
+        if (v != kDictEmpty) {
+            const int k = atomicAdd(&cnt, 1);
+            if (k < n) list[k] = v;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += kBlock) {
+        const unsigned long long v = list[i];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += list[j] < v;
+        dict[C.doff[d] + rank] = v;
+    }
+}
+
+extern __shared__ unsigned long long dict_lds[];
+template <int W, int REC>
+__global__ __launch_bounds__(kBlock) void k_dia_encode(int64_t ld, int nd, const double *__restrict__ val, DiaCodeDev C,
+                                                       unsigned long long *__restrict__ rec, unsigned int *__restrict__ missed)
+{
+    const unsigned long long *dict = reinterpret_cast<const unsigned long long *>(C.dict);
+    for (int i = threadIdx.x; i < C.doff[nd]; i += kBlock) dict_lds[i] = dict[i];
+    __syncthreads();
+    constexpr int PER = 64 / W;
+    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < ld; r += (int64_t)gridDim.x * kBlock) {
+        unsigned long long w[2] = {0ull, 0ull};
+        for (int d = 0; d < nd; ++d) {
+            const unsigned long long v = (unsigned long long)__double_as_longlong(val[(int64_t)d * ld + r]);
+            int lo = C.doff[d], hi = C.doff[d + 1] - 1;        // the value is in the dictionary: lo ends on it
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (dict_lds[mid] < v) lo = mid + 1;
+                else hi = mid;
+            }
+            if (dict_lds[lo] != v) atomicAdd(missed, 1u);       // (cannot happen; the host refuses the image if it does)
+            const unsigned long long code = (unsigned long long)(lo - C.doff[d]);
+            w[d / PER] |= code << ((d % PER) * W);
+        }
+        rec[r * (REC / 8)] = w[0];
+        if (REC == 16) rec[r * 2 + 1] = w[1];
+    }
+}
+
+int build_dia_code(kfsp_ctx *ctx)
+{
+    ctx->dia_coded = false;
+    ctx->dia_code_w = ctx->dia_code_rec = 0;
+    ctx->dia_code_us = 0;
+    for (int d = 0; d <= kMaxDiag; ++d) ctx->dia_doff[d] = 0;
+    for (int d = 0; d < kMaxDiag; ++d) ctx->dia_distinct[d] = 0;
+    if (!ctx->use_dia || ctx->use_box || ctx->nd < 1 || ctx->dia_ld < 128 || ctx->opt_dia_code == 0) return 0;
+    // the coded kernel exists for the unmasked single-rank product only
+    if (ctx->use_comm || ctx->dia_masked) return 0;
+    // auto: only where the product is bound by the bytes of the value streams - a generator that cannot stay in the
+    // 256 MiB Infinity Cache between two products (the rule of use_nt).  Below that the product gains nothing and the
+    // build is never repaid (DESIGN.md 4.1e has the measurements).
+    const double plain = (double)ctx->nd * (double)ctx->dia_ld * 8.0;
+    if (ctx->opt_dia_code < 0 && plain <= 192.0 * 1024 * 1024) return 0;
+    // ... and only the 8-byte record (up to 8 one-byte or 4 two-byte codes per row), the form that was measured at
+    // scale; generators with more diagonals are coded on request (dia_code = 1)
+    if (ctx->opt_dia_code < 0 && ctx->nd > 8) return 0;
+    hipStream_t st = ctx->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int nd = ctx->nd;
+    const int64_t ld = ctx->dia_ld;
+    HIP_TRY_B(ctx->d_dhash.reserve((size_t)2 * kMaxDiag * kDictSlots, false));
+    HIP_TRY_B(ctx->d_scan.reserve(sizeof(ScanOut), false));
+    static_assert(sizeof(DictCount) + sizeof(unsigned int) <= sizeof(ScanOut), "the counters live in the scan scratch");
+    DictCount *dcnt = reinterpret_cast<DictCount *>(ctx->d_scan.p);
+    unsigned int *missed = reinterpret_cast<unsigned int *>(dcnt + 1);
+    HIP_TRY_B(hipMemsetAsync(dcnt, 0, sizeof(DictCount) + sizeof(unsigned int), st));
+    HIP_TRY_B(hipMemsetAsync(ctx->d_dhash.p, 0xFF, (size_t)nd * kDictSlots * sizeof(unsigned long long), st));
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ld + kBlock - 1) / kBlock, 1024));
+    hipLaunchKernelGGL(k_dia_dict_scan, dim3(grid), dim3(kBlock), 0, st, ld, nd, ctx->d_dia.p, ctx->d_dhash.p, dcnt);
+    DictCount h;
+    HIP_TRY_B(hipMemcpyAsync(&h, dcnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY_B(hipStreamSynchronize(st));
+    bool over = h.stop != 0;
+    for (int d = 0; d < nd; ++d) {
+        ctx->dia_distinct[d] = h.n[d];
+        over = over || h.n[d] > (unsigned int)kDictCap;
+    }
+    int rec = 0;
+    int w = over ? 0 : dia_code_rule(nd, ctx->dia_distinct, kDiaCodeLds, &rec);
+    if (ctx->opt_dia_code < 0 && rec != 8) w = 0;
+    if (w) {
+        DiaCodeDev C;
+        C.doff[0] = 0;
+        for (int d = 0; d < kMaxDiag; ++d) C.doff[d + 1] = C.doff[d] + (d < nd ? (int32_t)ctx->dia_distinct[d] : 0);
+        HIP_TRY_B(ctx->d_ddict.reserve((size_t)kDictCap, false));
+        HIP_TRY_B(ctx->d_dcode.reserve((size_t)ld * (size_t)(rec / 8), false));
+        C.dict = ctx->d_ddict.p;
+        C.rec = ctx->d_dcode.p;
+        C.w = w;
+        C.rec_bytes = rec;
+        hipLaunchKernelGGL(k_dia_dict_sort, dim3(nd), dim3(kBlock), 0, st, ctx->d_dhash.p, ctx->d_dhash.p + (size_t)kMaxDiag * kDictSlots, C,
+                           reinterpret_cast<unsigned long long *>(ctx->d_ddict.p));
+        const size_t lds = (size_t)C.doff[nd] * sizeof(double);
+        const dim3 g(grid), b(kBlock);
+        if (w == 8 && rec == 8) hipLaunchKernelGGL((k_dia_encode<8, 8>), g, b, lds, st, ld, nd, ctx->d_dia.p, C, ctx->d_dcode.p, missed);
+        else if (w == 8) hipLaunchKernelGGL((k_dia_encode<8, 16>), g, b, lds, st, ld, nd, ctx->d_dia.p, C, ctx->d_dcode.p, missed);
+        else if (rec == 8) hipLaunchKernelGGL((k_dia_encode<16, 8>), g, b, lds, st, ld, nd, ctx->d_dia.p, C, ctx->d_dcode.p, missed);
+        else hipLaunchKernelGGL((k_dia_encode<16, 16>), g, b, lds, st, ld, nd, ctx->d_dia.p, C, ctx->d_dcode.p, missed);
+        unsigned int hm = 0;
+        HIP_TRY_B(hipMemcpyAsync(&hm, missed, sizeof(hm), hipMemcpyDeviceToHost, st));
+        HIP_TRY_B(hipStreamSynchronize(st));
+        if (hm != 0) {
+            ctx->err = "coded banded image: a stored value is missing from its dictionary";
+            return -1;
+        }
+        for (int d = 0; d <= kMaxDiag; ++d) ctx->dia_doff[d] = C.doff[d];
+        ctx->dia_code_w = w;
+        ctx->dia_code_rec = rec;
+        ctx->dia_coded = true;
+    }
+    ctx->dia_code_us = (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 

@@ -200,6 +200,15 @@ struct kfsp_ctx {
     int64_t coded_slots = 0;         // entries (incl. padding) of those chunks
     int64_t coded_tab_bytes = 0;     // bytes of their offset tables, in 64-byte lines
     int64_t sell_reach = -1;         // max |col - row| over the local SELL rows (-1: unknown)
+    // dictionary-coded values of the banded image (kernel format 9; kfsp_internal.h DiaCodeDev, kfsp_build.hip build_dia_code).
+    // Valid for the image in d_dia only: every path that writes d_dia ends in build_dia_code, which drops or rebuilds it.
+    DevBuf<unsigned long long> d_dcode, d_dhash;   // the records; the build's tables
+    DevBuf<double> d_ddict;
+    bool dia_coded = false;
+    int dia_code_w = 0, dia_code_rec = 0;          // bits per code, bytes per record
+    int32_t dia_doff[kMaxDiag + 1] = {0};
+    int64_t dia_distinct[kMaxDiag] = {0};          // distinct values per diagonal as far as they were counted
+    int64_t dia_code_us = 0;                       // what the last build_dia_code took
     // which 128-row groups of which diagonals hold entries at all (used when enough are empty)
     DevBuf<uint32_t> d_gmask;
     DevBuf<double> d_zero;   // 128 zeros, the stand-in for an empty segment
@@ -361,6 +370,7 @@ struct kfsp_ctx {
     int64_t coords_n = 0;                  // states whose coordinates sit in d_coords (kfsp_set_state_coords), 0: none
     int32_t coords_ld = 0, coords_ns = 0;
     int64_t opt_sell_code = -1;            // dictionary-coded SELL columns: -1 auto (under the internal state order), 0 never, 1 always try
+    int64_t opt_dia_code = -1;             // dictionary-coded banded values: -1 auto (generators beyond the Infinity Cache), 0 never, 1 always try
     int64_t opt_box_store = 0;            // 1: kfsp_set_matrix_box writes the generator out as stored diagonals on the device (banded form)
     int64_t opt_state_order = 1;          // 1: use kfsp_set_state_coords for large, long-lived generators (0: never)
     int64_t opt_ssa_general = 0;          // 1: the SSA walk always runs its general kernel (A/B of the register-resident one)
@@ -427,6 +437,8 @@ int state_order_from_resident(kfsp_ctx *ctx, int32_t n, int32_t ns, int32_t ld, 
 bool state_order_after_drop(kfsp_ctx *ctx, int32_t n_old, int32_t n_new, const uint8_t *keep, const int32_t *scan, int *rc);
 int compact_resident_ell(kfsp_ctx *ctx, int64_t n, int bw, int ld, const uint8_t *keep, int64_t n_keep, bool with_coords, int lds);
 int build_dia_mask(kfsp_ctx *ctx);
+// after a banded generator was stored and its masks decided: build the dictionary-coded image of its values, or drop a stale one
+int build_dia_code(kfsp_ctx *ctx);
 // after a SELL image was stored (d_off, d_col, d_val): try the dictionary-coded column form
 int build_sell_code(kfsp_ctx *ctx);
 // kfsp_set_matrix_box with option box_store: the box generator written out as stored diagonals (d_dia, d_diag)

@@ -81,6 +81,46 @@ struct DiaDev {
     const double *zero;
 };
 
+// Banded form with dictionary-coded values (kernel format 9).  An off-diagonal of a chemical-master-equation generator
+// holds one reaction's propensity a_k(x - nu_k), a function of the one or two species the reaction depends on: a stored
+// diagonal of millions of entries carries a few hundred distinct doubles.  Per diagonal the distinct 64-bit patterns
+// (compared as integers: +0.0 and -0.0 are two entries; the padding zeros are entries too) form a dictionary, sorted
+// as unsigned integers; a row stores one code per diagonal instead of one double.  The nd codes of a row are one
+// RECORD of 8 or 16 bytes (code d in bits [W d, W d + W) of the record, little endian), records in row order, so
+// that the two rows a lane owns are adjacent and one 16-byte load (two for 16-byte records) fetches all their
+// codes.  The kernel keeps every dictionary in LDS and computes with dict[d][code]: the very doubles of the plain
+// streams, the same multiply-adds in the same order, bit-identical products.  DIAG stays an 8-byte stream (it has
+// about as many distinct values as rows).  One code width per matrix, chosen by dia_code_rule; a matrix that does not
+// fit keeps the plain kernel.  The plain streams stay resident (block products, masked / halo / partitioned forms,
+// kfsp_get_matrix read them): the coded image costs 8 or 16 B per row on top.
+constexpr int kDiaCodeLds = 40 * 1024;        // LDS bytes all dictionaries together may take: 4 workgroups per CU stay resident
+struct DiaCodeDev {
+    const unsigned long long *rec;   // [ld] records of rec_bytes each
+    const double *dict;              // the dictionaries back to back: diagonal d at doff[d] .. doff[d + 1]
+    int32_t doff[kMaxDiag + 1];
+    int32_t w, rec_bytes;            // bits per code (8 / 16), bytes per record (8 / 16)
+};
+// Code width for a matrix whose diagonal d has distinct[d] distinct values, 0: no coded image.  8 bits when every
+// diagonal has <= 256 values; 16 bits when every diagonal has <= 65 536 and all dictionaries together fit lds_bytes
+// (16 dictionaries of 256 doubles are 32 KB: the 8-bit form always fits kDiaCodeLds); a row's codes must fit a
+// 16-byte record (8-bit codes: always; 16-bit codes: up to 8 diagonals).
+inline int dia_code_rule(int nd, const int64_t *distinct, int64_t lds_bytes, int *rec_bytes)
+{
+    if (nd < 1 || nd > kMaxDiag) return 0;
+    int64_t total = 0, most = 0;
+    for (int d = 0; d < nd; ++d) {
+        if (distinct[d] < 1) return 0;
+        total += distinct[d];
+        most = distinct[d] > most ? distinct[d] : most;
+    }
+    if (most > 65536 || total * 8 > lds_bytes) return 0;
+    const int w = most <= 256 ? 8 : 16;
+    const int bytes = nd * w / 8;
+    if (bytes > 16) return 0;
+    if (rec_bytes) *rec_bytes = bytes <= 8 ? 8 : 16;
+    return w;
+}
+
 // Matrix-free generator of a lexicographic box [0,d_1) x ... x [0,d_ns) (species 1 fastest): no
 // stored entries at all.  Propensities are products of one-species factors,
 //   a_k(x) = prod_i T_{k,i}[x_{s(k,i)}]   (mass action, Hill functions of one species, ...),
@@ -135,6 +175,7 @@ struct Pending {
 struct SpmvArgs {
     SellDev A;
     DiaDev D;             // used instead of A by the banded kernels
+    DiaCodeDev C;         // format 9: the coded values of D's diagonals
     BoxDev B;             // matrix-free box generator (format 3): the descriptor, by value (uniform kernel argument)
     const double *box_tab;   // ... and its factor tables (device memory, staged to LDS by the kernel)
     const BoxFast *box_fast; // format 4: the single-factor form of the same box (device memory)
@@ -229,7 +270,8 @@ int launch_arnoldi_small(const SmallArnoldiArgs &a, bool dia, int64_t lds_limit,
 
 // kernel launchers (kfsp_kernels.hip)
 // fmt: 0 SELL-64, 1 banded, 2 banded with group masks, 3 matrix-free box (lds_bytes = size of the factor tables),
-// 4 matrix-free box, single-factor fast path, 5 SELL-64 with dictionary-coded columns
+// 4 matrix-free box, single-factor fast path, 5 SELL-64 with dictionary-coded columns, 9 banded with dictionary-coded
+// values (a.C; the dictionaries' LDS is sized by the launcher)
 void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nontemporal, int fmt, hipStream_t s, size_t lds_bytes = 0);
 // format 6: the single-factor matrix-free product with the near part of x staged in LDS (reach rows on either side of a
 // workgroup's 512; lds_bytes = table image + two windows)

@@ -261,8 +261,55 @@ __device__ __forceinline__ xpair_t ld_xpair(const double *__restrict__ xg, int64
     return *reinterpret_cast<const xpair_u *>(xg + p);
 }
 
-template <bool NT, bool MASKED>
-__device__ __forceinline__ d2 rows_dia(const DiaDev &D, const double *__restrict__ xg, int64_t row0,
+extern __shared__ double box_lds[];   // dynamic LDS: the factor tables of the matrix-free kernels, the dictionaries of the coded banded one
+
+// Banded form with dictionary-coded values (format 9, DiaCodeDev in kfsp_internal.h).  The records of the lane's two rows are
+// adjacent: ONE 16-byte load (REC = 8) or two (REC = 16) bring every code of both rows, whatever the number of diagonals.
+// W: bits per code; a record word holds 64 / W codes, diagonal d in word d / (64 / W).
+typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+template <int REC>
+struct DiaCodes {
+    unsigned long long a[REC / 8], b[REC / 8];          // record words of row 2 l and of row 2 l + 1
+};
+template <bool NT, int REC>
+__device__ __forceinline__ DiaCodes<REC> ld_codes(const DiaCodeDev &C, int64_t r)
+{
+    DiaCodes<REC> k;
+    const ull2 *p = reinterpret_cast<const ull2 *>(C.rec + r * (REC / 8));
+    if (REC == 8) {
+        const ull2 t = NT ? __builtin_nontemporal_load(p) : *p;
+        k.a[0] = t.x;
+        k.b[0] = t.y;
+    } else {
+        const ull2 t = NT ? __builtin_nontemporal_load(p) : *p;
+        const ull2 u = NT ? __builtin_nontemporal_load(p + 1) : p[1];
+        k.a[0] = t.x;
+        k.a[REC / 8 - 1] = t.y;
+        k.b[0] = u.x;
+        k.b[REC / 8 - 1] = u.y;
+    }
+    return k;
+}
+// the stored values of diagonal d in the lane's two rows: dict[d][code], from LDS
+template <int W, int REC>
+__device__ __forceinline__ d2 coded_vals(const DiaCodeDev &C, const DiaCodes<REC> &k, int d)
+{
+    constexpr int PER = 64 / W;
+    const bool hi = REC == 16 && d >= PER;               // (uniform: d is the loop counter)
+    const unsigned long long wa = hi ? k.a[REC / 8 - 1] : k.a[0], wb = hi ? k.b[REC / 8 - 1] : k.b[0];
+    const int sh = (d & (PER - 1)) * W;
+    const unsigned ca = (unsigned)(wa >> sh) & ((1u << W) - 1u), cb = (unsigned)(wb >> sh) & ((1u << W) - 1u);
+    const double *t = box_lds + C.doff[d];
+    d2 v;
+    v.x = t[ca];
+    v.y = t[cb];
+    return v;
+}
+
+// W > 0: the values come from the dictionaries (coded_vals) instead of from the 16-byte value streams; everything else - the
+// x pairs, the clamp, the order of the multiply-adds - is the same code, so the sums are the same bits.
+template <bool NT, bool MASKED, int W = 0, int REC = 8>
+__device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, const double *__restrict__ xg, int64_t row0,
                                        int64_t c, int lane, unsigned m)
 {
     const int64_t r = (c << 7) + 2 * lane;
@@ -270,6 +317,8 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const double *__restrict
     const int64_t last = D.n - 1;
     const double *vp = D.val + r;
     const double *zp = D.zero + 2 * lane;
+    DiaCodes<REC> codes;
+    if (W) codes = ld_codes<NT, REC>(C, r);
     // m: which diagonals have entries in this group (same for the whole wavefront; the
     // caller fetched it one trip ahead, so no load sits in front of the address arithmetic)
     const d2 dg = ld_stream2<NT>(D.diag + r);
@@ -281,8 +330,8 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const double *__restrict
     for (; d + 2 <= D.nd; d += 2) {
         const bool on0 = !MASKED || ((m >> d) & 1u), on1 = !MASKED || ((m >> (d + 1)) & 1u);
         // an empty segment costs no HBM traffic: zeros from a cached line, x from the row itself
-        const d2 v0 = ld_stream2<NT>(on0 ? vp + (int64_t)(d + 0) * D.ld : zp);
-        const d2 v1 = ld_stream2<NT>(on1 ? vp + (int64_t)(d + 1) * D.ld : zp);
+        const d2 v0 = W ? coded_vals<(W ? W : 8), REC>(C, codes, d + 0) : ld_stream2<NT>(on0 ? vp + (int64_t)(d + 0) * D.ld : zp);
+        const d2 v1 = W ? coded_vals<(W ? W : 8), REC>(C, codes, d + 1) : ld_stream2<NT>(on1 ? vp + (int64_t)(d + 1) * D.ld : zp);
         const xpair_t x0 = ld_xpair(xg, g + (on0 ? D.delta[d + 0] : 0), last);
         const xpair_t x1 = ld_xpair(xg, g + (on1 ? D.delta[d + 1] : 0), last);
         sum.x += v0.x * x0.x;
@@ -292,7 +341,7 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const double *__restrict
     }
     for (; d < D.nd; ++d) {
         const bool on0 = !MASKED || ((m >> d) & 1u);
-        const d2 v0 = ld_stream2<NT>(on0 ? vp + (int64_t)d * D.ld : zp);
+        const d2 v0 = W ? coded_vals<(W ? W : 8), REC>(C, codes, d) : ld_stream2<NT>(on0 ? vp + (int64_t)d * D.ld : zp);
         const xpair_t x0 = ld_xpair(xg, g + (on0 ? D.delta[d] : 0), last);
         sum.x += v0.x * x0.x;
         sum.y += v0.y * x0.y;
@@ -471,7 +520,6 @@ __device__ __forceinline__ void box_load(const BoxFast *__restrict__ F, BoxRegs<
     R.bias8 = __builtin_amdgcn_readfirstlane(F->bias8);
 }
 
-extern __shared__ double box_lds[];   // matrix-free kernels: the image of the factor tables (dynamic LDS)
 // byte pointers that keep their address space through integer arithmetic (LDS reads, scalar-base global loads)
 typedef const __attribute__((address_space(3))) char *lds_bytes_t;
 typedef const __attribute__((address_space(1))) char *global_bytes_t;
@@ -598,12 +646,15 @@ __device__ __forceinline__ d2 rows_box1(const BoxRegs<NS, PER> &R, const double 
 }
 
 // FMT: 0 SELL-64, 1 banded, 2 banded with group masks, 3 matrix-free box (descriptor interpreted at run time),
-// 4 matrix-free box, single-factor fast path with NS species and NE entry slots per species
+// 4 matrix-free box, single-factor fast path with NS species and NE entry slots per species, 5 SELL-64 with coded columns,
+// 9 banded with dictionary-coded values (NS = bits per code, NE = bytes per row record)
 template <int MODE, bool NT, int FMT, int NS = 0, int NE = 0>
 __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
 {
     constexpr bool DIA = FMT != 0 && FMT != 5;
     constexpr bool BOX = FMT == 3 || FMT == 4;
+    constexpr bool CODED = FMT == 9;
+    constexpr int CW = CODED ? NS : 0, CREC = CODED && NE == 16 ? 16 : 8;
     __shared__ double red[12];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -617,6 +668,12 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
         __syncthreads();
         tab = box_lds;
         if (FMT == 4) box_load(a.box_fast, boxr);
+    }
+    if (CODED) {
+        // the dictionaries of all diagonals, back to back (<= kDiaCodeLds bytes: 4 workgroups per CU)
+        const int nent = a.C.doff[a.D.nd];
+        for (int i = threadIdx.x; i < nent; i += kBlock) box_lds[i] = a.C.dict[i];
+        __syncthreads();
     }
 
     // SELL: one 64-row chunk per wavefront trip; DIA: one 128-row group
@@ -639,7 +696,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
     if (c < cend) {
         if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
         else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-        else if (DIA) sum = rows_dia<NT, FMT == 2>(a.D, a.xg, a.row0, ct, lane, gm);
+        else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC>(a.D, a.C, a.xg, a.row0, ct, lane, gm);
         else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
     }
@@ -700,7 +757,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
         if (c < cend) {
             if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
             else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-            else if (DIA) sum = rows_dia<NT, FMT == 2>(a.D, a.xg, a.row0, ct, lane, gm);
+            else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC>(a.D, a.C, a.xg, a.row0, ct, lane, gm);
             else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
         }
@@ -972,9 +1029,36 @@ static void launch_box_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStre
     else hipLaunchKernelGGL((k_spmv<3, false, FMT, NS, NE>), g, b, lds, st, a);
 }
 
+template <bool NT, int W, int REC>
+static void launch_coded_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, size_t lds)
+{
+    if (mode == 0) hipLaunchKernelGGL((k_spmv<0, NT, 9, W, REC>), g, b, lds, st, a);
+    else if (mode == 1) hipLaunchKernelGGL((k_spmv<1, NT, 9, W, REC>), g, b, lds, st, a);
+    else if (mode == 2) hipLaunchKernelGGL((k_spmv<2, NT, 9, W, REC>), g, b, lds, st, a);
+    else hipLaunchKernelGGL((k_spmv<3, NT, 9, W, REC>), g, b, lds, st, a);
+}
+
+template <bool NT>
+static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st)
+{
+    const size_t lds = (size_t)a.C.doff[a.D.nd] * sizeof(double);
+    if (a.C.w == 8) {
+        if (a.C.rec_bytes == 8) launch_coded_mode<NT, 8, 8>(mode, g, b, a, st, lds);
+        else launch_coded_mode<NT, 8, 16>(mode, g, b, a, st, lds);
+    } else {
+        if (a.C.rec_bytes == 8) launch_coded_mode<NT, 16, 8>(mode, g, b, a, st, lds);
+        else launch_coded_mode<NT, 16, 16>(mode, g, b, a, st, lds);
+    }
+}
+
 void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nt, int fmt, hipStream_t st, size_t lds_bytes)
 {
     dim3 g(grid), b(kBlock);
+    if (fmt == 9) {
+        if (nt) launch_coded<true>(mode, g, b, a, st);
+        else launch_coded<false>(mode, g, b, a, st);
+        return;
+    }
     if (fmt == 3) {
         launch_box_mode<3, 0, 0>(mode, g, b, a, st, lds_bytes);
         return;

@@ -63,6 +63,9 @@ def load_library():
         "kfsp_num_states": [vp, C.POINTER(i64)],
         "kfsp_layout_info": [vp, vp],
         "kfsp_build_info": [vp, vp],
+        "kfsp_dia_code_info": [vp, vp],
+        "kfsp_dia_code_dict": [vp, C.c_int32, i64, vp, C.POINTER(i64)],
+        "kfsp_dia_code_rule": [C.c_int32, vp, i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
         "kfsp_set_trip_order": [vp, i64, vp],
         "kfsp_onestep": [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(i32), vp, vp],
         "kfsp_onestep_columns": [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(i32), vp, vp, vp, i32, vp],
@@ -519,6 +522,23 @@ class KfspContext:
         self._chk(self._lib.kfsp_layout_info(self._h, _p(v)), "kfsp_layout_info")
         keys = ("format", "exchange", "halo_rows", "sell_reach", "coded_chunks", "chunks", "code_words", "state_order")
         return dict(zip(keys, (int(x) for x in v)))
+
+    def dia_code_info(self):
+        """the dictionary-coded image of a banded generator's values (kfsp_dia_code_info)"""
+        v = np.zeros(24, dtype=np.int64)
+        self._chk(self._lib.kfsp_dia_code_info(self._h, _p(v)), "kfsp_dia_code_info")
+        keys = ("width", "record_bytes", "coded_bytes", "dict_bytes", "diagonals", "build_us", "active")
+        out = dict(zip(keys, (int(x) for x in v[:7])))
+        out["distinct"] = [int(x) for x in v[8:8 + out["diagonals"]]]
+        return out
+
+    def dia_code_dict(self, d):
+        """dictionary of diagonal d of the coded image, ascending as unsigned 64-bit patterns"""
+        n = C.c_int64(0)
+        self._chk(self._lib.kfsp_dia_code_dict(self._h, int(d), 0, None, C.byref(n)), "kfsp_dia_code_dict")
+        out = np.empty(n.value, dtype=np.float64)
+        self._chk(self._lib.kfsp_dia_code_dict(self._h, int(d), n.value, _p(out), C.byref(n)), "kfsp_dia_code_dict")
+        return out
 
     def build_info(self):
         """how the rebuilds of a resident FSP went (kfsp_build_info)"""
