@@ -460,7 +460,15 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
 /* exp(tA) W for k start vectors on ONE pass over the generator per product: transition probabilities from several
  * observed states, several initial distributions of one model.  The generator must be a stored one (SELL-64, coded
  * SELL, banded, masked banded): a matrix-free box (kernel formats 3, 4, 6, 7, 8; option box_store = 1 stores it) and a
- * context with a communicator or a group head return -12.  A block lives beside w (w is never touched) until the
+ * context with a communicator or a group head return -12.
+ * Option "block_box" = 1 (default 0) lets the block calls take a MATRIX-FREE box as well: the row of a single-factor box
+ * (the form kernel format 4 multiplies with) is rebuilt once and applied to all columns, so a product moves the block
+ * alone, and column j of kfsp_spmm is bit-identical to kfsp_spmv of column j on the same context (formats 4 and 7).
+ * The option is read by every block call, before or after kfsp_set_matrix_box.  Still -12 with it: a box without the
+ * single-factor form (a propensity of several factors, a step of more than 2, more than 4 propensities on a species),
+ * option box_generic = 1, a block so wide that an entry reaches more than 2^32 bytes (8 kp bytes per row of reach),
+ * communicator and group contexts.  The options box_lds / box_pencil choose among single-vector kernels only.
+ * A block lives beside w (w is never touched) until the
  * generator changes: the next kfsp_set_matrix_* / kfsp_update_matrix_ell / kfsp_drop_compact / kfsp_expand_resident
  * discards it, and kfsp_get_block then fails.  On the device a block holds kp = k rounded up to 2, 4, 8 or 16 doubles
  * per row (zero padding columns); the basis of kfsp_expv_block takes (m + 2) kp rows-long columns. */
@@ -615,7 +623,8 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * "m_max" (largest Krylov dimension the basis is allocated for, default and maximum 100 = M_MAX of
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
- * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "box_pencil" (-1, default: a matrix-free box whose slowest species is
+ * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
+ * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other
  * coordinates is worked out once per pencil; kernel format 7, products bit-identical to format 4; 0: never; 1: also on small boxes; 2: pencils in SLABS, format 8 - a workgroup's

@@ -18,9 +18,14 @@
 // Dot products and norms are block partials in a fixed layout, summed in a fixed order by one small finishing
 // launch: two runs give the same bits.  A column whose H(j+1,j) <= break_tol stops there (its coefficients become 0,
 // its H is exact); a column with beta = 0 is skipped from the start and stays exactly 0.
+//
+// Matrix-free boxes (option block_box, k_spmm_box below; DESIGN.md 12, "Matrix-free boxes"): the row of a single-factor box is rebuilt
+// once - coordinates, {sum, valid} look-ups, one LDS read per entry - and applied to all kp columns, in the operation
+// order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_kernels.hip).
 #pragma clang fp contract(off)
 
 #include "kfsp_block.h"
+#include "kfsp_box_dev.h"
 #include "kfsp_ctx.h"
 
 #include <algorithm>
@@ -184,6 +189,9 @@ struct SpmmArgs {
     int64_t trips;
     const int32_t *trip_order;
     int64_t rows_red;        // rows that enter the reductions
+    const double *box_tab;   // matrix-free box: the table image (staged to LDS), its length in doubles and the
+    int box_ntab;            // single-factor descriptor behind it
+    const BoxFast *box_fast;
 };
 
 // per-column sums of the block: v[c] summed over the wavefront, then the four wavefronts in a fixed order
@@ -249,6 +257,124 @@ __global__ __launch_bounds__(kBlock) void k_spmm(SpmmArgs a)
     if (DOTS) {
         block_sum_cols<KP>(da, red, a.part + (size_t)blockIdx.x * K);
         block_sum_cols<KP>(db, red, a.part + ((size_t)kMaxGrid + blockIdx.x) * K);
+    }
+}
+
+// Row r0 + lane of a single-factor matrix-free box (BoxFast) applied to the kp columns of X.  Per column the operations of
+// rows_box1 (kfsp_kernels.hip) as its ISA has them: the accumulator starts at +0.0, ONE v_fma_f64 per entry slot in
+// species-then-slot order (the first one against the literal 0, so a leading 0.0 * x of either sign leaves +0.0), then
+// fma(-dsum, x_row, acc) with dsum the species' shares added in species order.  An invalid slot reads the 0.0 at the head
+// of the LDS image and the row's OWN row of X (the single-vector kernel may read a neighbour's element there: any finite
+// number, times 0.0, added to an accumulator that is not -0.0).  X is addressed as wave base (scalar) + 32-bit lane
+// offset: box_block_reach_ok checks that the largest reach fits for this kp.
+template <int KP, int NS, int PER>
+__device__ __forceinline__ void row_box_blk(const BoxRegs<NS, PER> &R, const double *__restrict__ X, int64_t r0, int lane,
+                                            double (&s)[KP])
+{
+    const uint64_t xb = reinterpret_cast<uint64_t>(X + r0 * KP) - (uint64_t)(uint32_t)R.bias8 * (uint64_t)KP;
+    const global_bytes_t xw = (global_bytes_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)xb) |
+                                               (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(xb >> 32)) << 32);
+    const unsigned voff = (unsigned)(8 * KP * lane) + (unsigned)R.bias8 * (unsigned)KP;
+    auto ld = [&](unsigned at, double (&x)[KP]) {
+#pragma unroll
+        for (int q = 0; q < KP / 2; ++q) {
+            const box_pair_t t = *(const __attribute__((address_space(1), aligned(16))) box_pair_t *)(xw + at + 16 * q);
+            x[2 * q] = t.x;
+            x[2 * q + 1] = t.y;
+        }
+    };
+    // coordinates of the row: successive division by the box dimensions (exact: r < 2^31, one correction step)
+    int co[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t q = (uint32_t)(r0 + lane);
+#pragma unroll
+    for (int S = 0; S + 1 < NS; ++S) {
+        const int d = R.dims[S];
+        uint32_t t = (uint32_t)((double)q * R.inv_dim[S]);
+        int r = (int)(q - t * (uint32_t)d);
+        const int lo = r < 0, hi = r >= d;
+        t = t - lo + hi;
+        r = r + (lo ? d : 0) - (hi ? d : 0);
+        co[S] = r;
+        q = t;
+    }
+    co[NS - 1] = (int)q;
+    double dsum;
+    unsigned valid;
+    box_df<NS, PER>(R, co[0], co[1], co[2], co[3], co[4], co[5], dsum, valid);
+    double xd[KP], x[KP];
+    ld(voff, xd);
+#pragma unroll
+    for (int c = 0; c < KP; ++c) s[c] = 0.0;
+    const unsigned lds0 = (unsigned)(size_t)(lds_bytes_t)box_lds;                  // LDS address of the image = of its 0.0
+#pragma unroll
+    for (int S = 0; S < NS; ++S) {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int m = __builtin_amdgcn_sbfe(valid, S * PER + j, 1);            // -1: the source state lies inside the box
+            const unsigned at = lds0 + (unsigned)(8 * co[S] + R.koff8[S][j]);      // a_k(x - nu_k) ...
+            const double a = *(const __attribute__((address_space(3))) double *)(size_t)((m & at) | (~m & lds0));   // ... or 0
+            const unsigned vsrc = voff + (unsigned)R.delta8[S][j] * (unsigned)KP;
+            ld(m ? vsrc : voff, x);
+            fma_row<KP>(a, x, s);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KP; ++c) s[c] = __builtin_fma(-dsum, xd[c], s[c]);
+}
+
+// The block product of a matrix-free box: trips, trip order and partial layout of k_spmm's banded form.  Every workgroup
+// stages the table image into dynamic LDS first (as k_spmv<.., 4> does) and reads the descriptor into scalar registers
+// once per wavefront.  Rows in [n, rows_act) are written as zeros.  The reductions reuse the image's LDS once all
+// wavefronts are done with it (the image may fill the 64 KB a workgroup gets).
+template <int KP, int NS, int PER, bool DOTS>
+__global__ __launch_bounds__(kBlock) void k_spmm_box(SpmmArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int i = threadIdx.x; i < a.box_ntab; i += kBlock) box_lds[i] = a.box_tab[i];
+    __syncthreads();
+    BoxRegs<NS, PER> R;
+    box_load(a.box_fast, R);
+    const int xcd = blockIdx.x & 7;
+    const int slot = blockIdx.x >> 3;
+    const int bx = gridDim.x >> 3;
+    const int64_t cpx = (a.trips + 7) >> 3;
+    const int64_t cbeg = (int64_t)xcd * cpx;
+    const int64_t cend = (cbeg + cpx < a.trips) ? cbeg + cpx : a.trips;
+    const int64_t cstep = (int64_t)bx * 4;
+    double da[KP], db[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) da[c] = db[c] = 0.0;
+    for (int64_t t = cbeg + (int64_t)slot * 4 + wave; t < cend; t += cstep) {
+        const int64_t ct = a.trip_order ? (int64_t)__builtin_amdgcn_readfirstlane(a.trip_order[t]) : t;
+        for (int h = 0; h < 2; ++h) {
+            const int64_t r0 = (ct << 7) + h * 64;
+            const int64_t r = r0 + lane;
+            double s[KP];
+            if (r < a.D.n) {
+                row_box_blk<KP, NS, PER>(R, a.X, r0, lane, s);
+            } else {
+#pragma unroll
+                for (int c = 0; c < KP; ++c) s[c] = 0.0;
+            }
+            st_row<KP>(a.Y, r, s);
+            if (DOTS && r < a.rows_red) {
+                double u[KP];
+                if (a.ua) {
+                    ld_row<KP>(a.ua, r, u);
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) da[c] = __builtin_fma(u[c], s[c], da[c]);
+                }
+                ld_row<KP>(a.ub, r, u);
+#pragma unroll
+                for (int c = 0; c < KP; ++c) db[c] = __builtin_fma(u[c], s[c], db[c]);
+            }
+        }
+    }
+    if (DOTS) {
+        __syncthreads();
+        block_sum_cols<KP>(da, box_lds, a.part + (size_t)blockIdx.x * K);
+        block_sum_cols<KP>(db, box_lds, a.part + ((size_t)kMaxGrid + blockIdx.x) * K);
     }
 }
 
@@ -474,6 +600,9 @@ struct PhaseTimer {
     ~PhaseTimer() { c->t_ms[phase] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+const char *const kBoxReachMsg = "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
+                                 "at this block width (fewer columns, or option box_store = 1)";
+
 int kp_of(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)); }
 
 int spmm_fmt(const kfsp_ctx *c) { return c->use_dia ? (c->dia_masked ? 2 : 1) : (c->sell_coded ? 5 : 0); }
@@ -517,6 +646,61 @@ void launch_spmm_kp(int fmt, bool dots, int g, const SpmmArgs &a, hipStream_t st
 #undef KFSP_SPMM
 }
 
+typedef void (*SpmmBoxFn)(SpmmArgs);
+
+template <int KP, bool DOTS>
+SpmmBoxFn spmm_box_fn_kp(int inst)
+{
+    // inst = species of the instantiation * 16 + slots per species (BoxDev::pad, kfsp_set_matrix_box)
+    switch (inst) {
+    case 2 * 16 + 2: return k_spmm_box<KP, 2, 2, DOTS>;
+    case 3 * 16 + 2: return k_spmm_box<KP, 3, 2, DOTS>;
+    case 6 * 16 + 2: return k_spmm_box<KP, 6, 2, DOTS>;
+    default: return k_spmm_box<KP, 6, 4, DOTS>;
+    }
+}
+
+SpmmBoxFn spmm_box_fn(int kp, int inst, bool dots)
+{
+    switch (kp) {
+    case 2: return dots ? spmm_box_fn_kp<2, true>(inst) : spmm_box_fn_kp<2, false>(inst);
+    case 4: return dots ? spmm_box_fn_kp<4, true>(inst) : spmm_box_fn_kp<4, false>(inst);
+    case 8: return dots ? spmm_box_fn_kp<8, true>(inst) : spmm_box_fn_kp<8, false>(inst);
+    default: return dots ? spmm_box_fn_kp<16, true>(inst) : spmm_box_fn_kp<16, false>(inst);
+    }
+}
+
+// In the block layout a reach of delta rows is 8 kp delta bytes, and k_spmm_box addresses X as scalar base + unsigned
+// 32-bit lane offset: the backward plus the forward reach plus one 128-row group must stay below 2^32 bytes.
+bool box_block_reach_ok(const kfsp_ctx *c, int kp)
+{
+    const int64_t back = std::max<int64_t>(0, -(int64_t)c->delta[0]), fwd = std::max<int64_t>(0, (int64_t)c->delta[c->nd - 1]);
+    return (back + fwd + 128) * 8 * (int64_t)kp < (1LL << 32);
+}
+
+// The matrix-free block product.  Every workgroup copies the table image first, so no more workgroups are launched
+// than are resident at once (the rule of the single-vector product, run_product): the runtime says how many fit.
+int spmm_box(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
+{
+    const SpmmBoxFn fn = spmm_box_fn(kp, ctx->box.pad, dots);
+    const size_t lds = std::max<size_t>(ctx->box_lds_bytes, (size_t)4 * kp * sizeof(double));
+    int &occ = ctx->blk_box_occ[kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3))][dots ? 1 : 0];
+    if (occ == 0) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kBlock, lds) != hipSuccess) nb = 1;
+        occ = std::max(nb, 1);
+    }
+    int64_t g = round_up((a.trips + 3) / 4, 8);
+    g = std::min<int64_t>(g, ctx->opt_grid > 0 ? std::min<int64_t>(round_up(ctx->opt_grid, 8), kMaxGrid)
+                                               : std::min<int64_t>(1024, (int64_t)256 * occ));
+    g = std::max<int64_t>(g, 8);
+    a.box_tab = ctx->d_box.p;
+    a.box_ntab = ctx->box.ntab;
+    a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
+    hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kBlock), lds, ctx->stream, a);
+    return (int)g;
+}
+
 // Y = A X (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
 int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
 {
@@ -540,6 +724,10 @@ int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, co
     a.trips = spmm_trips(ctx);
     a.trip_order = ctx->trip_order_n == a.trips ? ctx->d_trip_order.p : nullptr;
     a.rows_red = ctx->nchunks * kChunk;
+    a.box_tab = nullptr;
+    a.box_ntab = 0;
+    a.box_fast = nullptr;
+    if (ctx->use_box) return spmm_box(ctx, kp, dots, a);
     const int g = spmm_grid(ctx);
     const int fmt = spmm_fmt(ctx);
     switch (kp) {
@@ -626,6 +814,7 @@ void block_release(kfsp_ctx *ctx)
     ctx->d_bscal.release();
     ctx->d_bpart.release();
     ctx->blk_k = ctx->blk_kp = ctx->bv_kp = 0;
+    std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
 }
 
 int block_supported(kfsp_ctx *ctx)
@@ -633,7 +822,16 @@ int block_supported(kfsp_ctx *ctx)
     if (ctx->group || ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm)
         return fail(ctx, -12, "several vectors at once: not with a row partition (communicator or group context)");
     if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
-    if (ctx->use_box) return fail(ctx, -12, "several vectors at once: not for a matrix-free generator (option box_store = 1 stores it)");
+    if (ctx->use_box) {
+        if (!ctx->opt_block_box)
+            return fail(ctx, -12, "several vectors at once: not for a matrix-free generator (option box_store = 1 stores it, "
+                                  "option block_box = 1 takes it matrix-free)");
+        if (ctx->opt_box_generic)
+            return fail(ctx, -12, "several vectors at once: not for the interpreted matrix-free product (option box_generic = 1)");
+        if (!ctx->box_fast)
+            return fail(ctx, -12, "several vectors at once: this matrix-free box has no single-factor form (option box_store = 1 stores it)");
+        return 0;
+    }
     if (!ctx->use_dia && !ctx->have_sell) return fail(ctx, -12, "several vectors at once: no stored generator");
     return 0;
 }
@@ -730,6 +928,7 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
         if (!W) return fail(ctx, -5, "null W");
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
+        if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         ctx->blk_k = 0;
         if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
             ctx->d_blk.release();
@@ -771,6 +970,7 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         if (!Y) return fail(ctx, -5, "null Y");
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
+        if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         if (int rc = ensure_basis(ctx, kp, 2)) return rc;
         double *x = bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
         if (int rc = upload_block(ctx, k, kp, ld, X, x)) return rc;

@@ -672,7 +672,8 @@ class KfspContext:
 
     # -- several vectors at once
     def set_block(self, W):
-        """k start vectors as the columns of W (shape n x k, 1 <= k <= 16), caller's state order."""
+        """k start vectors as the columns of W (shape n x k, 1 <= k <= 16), caller's state order.
+        Stored generators; a matrix-free box (set_matrix_box(..., store=False)) only after set_option("block_box", 1)."""
         Wf, k = _block_columns(W, self.n)
         self._chk(self._lib.kfsp_set_block(self._h, k, self.n, self.n, _p(Wf)), "kfsp_set_block")
         self.block_k = k
@@ -686,7 +687,8 @@ class KfspContext:
         return W
 
     def spmm(self, X):
-        """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j])."""
+        """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j]) - also on a
+        matrix-free box under set_option("block_box", 1)."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
         self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm")
@@ -709,4 +711,5 @@ class KfspContext:
         return ms.value
 
     def set_option(self, name, value):
+        """kfsp_set_option (include/kfsp.h lists the names), e.g. "block_box" = 1: the block calls take a matrix-free box."""
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
