@@ -493,6 +493,30 @@ typedef struct {
 int kfsp_expv_block(kfsp_ctx *ctx, double t, double tol, int32_t m, double *wsum, kfsp_block_stats *stats);
 /* reps block products Y = A X on the resident block, bracketed by HIP events (like kfsp_spmv_bench) */
 int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total);
+/* The three device phases of one step of kfsp_expv_block, as kfsp_begin_step / kfsp_arnoldi / kfsp_combine are those of
+ * the single-vector step.  All arrays are host memory with 16 entries per row, one per block column (entries >= k
+ * belong to the padding columns).  Common returns: -1 null context or no block resident, -12 as kfsp_set_block, -2 m
+ * (mx) out of range: m < 1, m > 100, m beyond option m_max, m beyond the m of the last kfsp_block_begin; -3 no
+ * kfsp_block_begin since kfsp_set_block (arnoldi, combine) or null beta (begin); -4 / -5 a null array.
+ * kfsp_block_begin: u_1 = W, beta[c] = ||W_c||_2; lays the basis out for dimension m.
+ * kfsp_block_arnoldi: IOP(2) Arnoldi of dimension m for every column plus the AVNORM product.
+ *   hb[(j * 3 + t) * 16 + c], j = 1..m, t = 0, 1, 2: H(j-1,j), H(j,j), H(j+1,j) of column c (102 * 3 * 16 doubles);
+ *   nrm[j * 16 + c] = ||u_j||, j = 1..m+1 (103 * 16 doubles); brk[c] = 0, or j when H(j+1,j) <= break_tol ended column
+ *   c after its column j (its later entries are 0), or -1 for a column with beta = 0; avnorm[c] = ||A v_{m+1}||.
+ * kfsp_block_combine: W_c = max(sum_{i < mx} coef[i * 16 + c] u_{i+1,c}, 0) and wsum[c] = ||W_c||_1; mx <= m + 2.
+ * Option "block_small" = 1 (default 0): where kfsp_arnoldi would take its one-launch pass - at most 4096 rows, a banded
+ * or plain (not coded) SELL image, no box, communicator or group, options small_kernel and fused_ortho on - each of the
+ * three is ONE launch of one 1024-lane workgroup per block column, and H, the norms and AVNORM of a column are the
+ * bits kfsp_begin_step + kfsp_arnoldi(m, 1, 2, break_tol) give for that column alone (whenever the two agree on beta:
+ * the sums of squares are taken in different orders).  "small_lds" chooses between SELL from LDS and from global
+ * memory as it does there.  Anywhere else the option changes nothing.  Read by every block call. */
+int kfsp_block_begin(kfsp_ctx *ctx, int32_t m, double *beta /* [16] */);
+int kfsp_block_arnoldi(kfsp_ctx *ctx, int32_t m, double break_tol, double *hb, double *nrm, int32_t *brk, double *avnorm);
+int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *wsum /* [16] */);
+/* kfsp_block_info: how the last block calls ran: v[0] = 1 when the last kfsp_block_arnoldi (or pass of kfsp_expv_block) was one launch,
+ * v[1] its kernel variant (0 SELL from global memory, 1 banded, 2 SELL from LDS), v[2], v[3], v[4] = kernel launches
+ * enqueued by the last begin, arnoldi, combine, v[5] = dynamic LDS bytes of the pass kernel, v[6..7] = 0 */
+int kfsp_block_info(kfsp_ctx *ctx, int64_t v[8]);
 
 /* ---- lock-step diagnostics ---------------------------------------------- */
 /* The accept/reject decisions of DGEXPV_FSP hinge on quantities that amplify
@@ -624,7 +648,8 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
- * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "box_pencil" (-1, default: a matrix-free box whose slowest species is
+ * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
+ * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other
  * coordinates is worked out once per pencil; kernel format 7, products bit-identical to format 4; 0: never; 1: also on small boxes; 2: pencils in SLABS, format 8 - a workgroup's

@@ -22,6 +22,11 @@
 // Matrix-free boxes (option block_box, k_spmm_box below; DESIGN.md 12, "Matrix-free boxes"): the row of a single-factor box is rebuilt
 // once - coordinates, {sum, valid} look-ups, one LDS read per entry - and applied to all kp columns, in the operation
 // order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_kernels.hip).
+//
+// Small generators (option block_small; DESIGN.md 12, "Small generators"): where the single-vector path takes its
+// one-launch pass (<= kSmallRows rows, a banded or plain SELL image, no partition), a block step is three launches of
+// one 1024-lane workgroup per block column: k_bbegin_small, k_barnoldi_small (kfsp_kernels.hip: the pass of
+// k_arnoldi_small, compiled from the same lines) and k_bcombine_small.
 #pragma clang fp contract(off)
 
 #include "kfsp_block.h"
@@ -49,7 +54,9 @@ constexpr int kBRK = kGG + K;                   // [K]: 0 running, j broke down 
 constexpr int kAVN = kBRK + K;                  // [K]
 constexpr int kWS = kAVN + K;                   // [K]
 constexpr int kCMB = kWS + K;                   // [kMMax + 3][K]: combine coefficients
-constexpr int kScal = kCMB + (kMMax + 3) * K;
+constexpr int kSQ1 = kCMB + (kMMax + 3) * K;    // [K]: ||u_1||^2 (what k_barnoldi_small starts from)
+constexpr int kScal = kSQ1 + K;
+constexpr int kSmallBlock = 1024;               // lanes of a small-path workgroup
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef int i2 __attribute__((ext_vector_type(2)));
@@ -530,6 +537,7 @@ __global__ __launch_bounds__(kBlock) void k_bfinal(int stage, int j, int kp, int
         nrm[K + c] = n1;
         brk = n1 > 0.0 ? 0.0 : -1.0;
         gg = 0.0;
+        sc[kSQ1 + c] = s0;
         break;
     }
     case kFinDots: {
@@ -571,6 +579,59 @@ __global__ __launch_bounds__(kBlock) void k_bfinal(int stage, int j, int kp, int
         sc[kWS + c] = s0;
         break;
     }
+}
+
+// ---- the small path: one workgroup of 1024 lanes per block column, rows below nact only
+// the sum of v over the workgroup, wavefronts in a fixed order
+__device__ __forceinline__ double small_sum(double v, double *red)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kSmallBlock / 64; ++w) s += red[w];
+    return s;
+}
+
+// u_1 = W, beta = ||W_c|| and the start of the column's bookkeeping (k_bcopy_nrm + k_bfinal(kFinBegin))
+__global__ __launch_bounds__(kSmallBlock) void k_bbegin_small(int nact, int kp, const double *__restrict__ w, double *__restrict__ u,
+                                                              double *__restrict__ sc)
+{
+    __shared__ double red[kSmallBlock / 64];
+    const int c = blockIdx.x;
+    double a = 0.0;
+    for (int r = threadIdx.x; r < nact; r += kSmallBlock) {
+        const double v = w[r * kp + c];
+        u[r * kp + c] = v;
+        a = __builtin_fma(v, v, a);
+    }
+    const double s0 = small_sum(a, red);
+    if (threadIdx.x != 0) return;
+    const double n1 = sqrt(s0);
+    sc[kNRM + K + c] = n1;
+    sc[kBRK + c] = n1 > 0.0 ? 0.0 : -1.0;
+    sc[kGG + c] = 0.0;
+    sc[kSQ1 + c] = s0;
+}
+
+// W_c = max(sum_i coef_i u_{i+1,c}, 0) and its sum: per element the operations of k_bcombine in its order
+__global__ __launch_bounds__(kSmallBlock) void k_bcombine_small(int nact, int kp, const double *__restrict__ U, int64_t ldc, int mx,
+                                                                const double *__restrict__ coef, double *__restrict__ w,
+                                                                double *__restrict__ sc)
+{
+    __shared__ double red[kSmallBlock / 64];
+    const int c = blockIdx.x;
+    double a = 0.0;
+    for (int r = threadIdx.x; r < nact; r += kSmallBlock) {
+        double s = 0.0;
+        for (int j = 0; j < mx; ++j) s = __builtin_fma(coef[j * K + c], U[(size_t)j * ldc + r * kp + c], s);
+        s = s > 0.0 ? s : 0.0;
+        w[r * kp + c] = s;
+        a += s;
+    }
+    const double s0 = small_sum(a, red);
+    if (threadIdx.x == 0) sc[kWS + c] = s0;
 }
 
 // ---- host side
@@ -622,6 +683,14 @@ int spmm_grid(const kfsp_ctx *c)
     int64_t g = round_up((t + 3) / 4, 8);
     g = std::min<int64_t>(g, c->opt_grid > 0 ? std::min<int64_t>(round_up(c->opt_grid, 8), kMaxGrid) : 1024);
     return (int)std::max<int64_t>(g, 8);
+}
+
+// The small path is taken where kfsp_arnoldi (qiop = 2) takes k_arnoldi_small on this context (kfsp_api.cpp), short of
+// coded SELL columns: those stay on the multi-launch path.
+bool small_path(const kfsp_ctx *c)
+{
+    return c->opt_block_small != 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->use_box &&
+           c->nchunks * kChunk <= kSmallRows && (c->use_dia || (c->have_sell && !c->sell_coded)) && c->slots < (1LL << 31);
 }
 
 int flat_grid(const kfsp_ctx *c, int kp)
@@ -701,10 +770,9 @@ int spmm_box(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
     return (int)g;
 }
 
-// Y = A X (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
-int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
+// the generator's images as the kernels take them
+void matrix_args(const kfsp_ctx *ctx, SpmmArgs &a)
 {
-    SpmmArgs a;
     a.A = SellDev{ctx->nloc, ctx->nchunks, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, ctx->d_diag.p,
                   ctx->d_dtab.p, ctx->d_dtlen.p, ctx->d_code.p, ctx->d_codeoff.p};
     a.D.nd = ctx->nd;
@@ -716,6 +784,13 @@ int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, co
     a.D.n = ctx->n;
     a.D.gmask = ctx->dia_masked ? ctx->d_gmask.p : nullptr;
     a.D.zero = ctx->d_zero.p;
+}
+
+// Y = A X (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
+int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
+{
+    SpmmArgs a;
+    matrix_args(ctx, a);
     a.X = X;
     a.Y = Y;
     a.ua = ua;
@@ -813,7 +888,8 @@ void block_release(kfsp_ctx *ctx)
     ctx->d_bstage.release();
     ctx->d_bscal.release();
     ctx->d_bpart.release();
-    ctx->blk_k = ctx->blk_kp = ctx->bv_kp = 0;
+    ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->blk_begin_m = 0;
+    std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
     std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
 }
 
@@ -851,11 +927,19 @@ int block_begin(kfsp_ctx *ctx, int m, double *beta)
     HIP_TRY(hipSetDevice(ctx->device));
     const int kp = ctx->blk_kp;
     if (int rc = ensure_basis(ctx, kp, m + 2)) return rc;
-    const int g = flat_grid(ctx, kp);
-    hipLaunchKernelGGL(k_bcopy_nrm, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2,
-                       reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)),
-                       ctx->d_bpart.p);
-    finalize(ctx, kFinBegin, 1, kp, g);
+    ctx->blk_begin_m = m;
+    if (small_path(ctx)) {
+        hipLaunchKernelGGL(k_bbegin_small, dim3(kp), dim3(kSmallBlock), 0, ctx->stream, (int)(ctx->nchunks * kChunk), kp,
+                           bcol(ctx->d_blk.p, ctx, kp, 0), bcol(ctx->d_bv.p, ctx, kp, 0), ctx->d_bscal.p);
+        ctx->blk_info[2] = 1;
+    } else {
+        const int g = flat_grid(ctx, kp);
+        hipLaunchKernelGGL(k_bcopy_nrm, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2,
+                           reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)),
+                           ctx->d_bpart.p);
+        finalize(ctx, kFinBegin, 1, kp, g);
+        ctx->blk_info[2] = 2;
+    }
     HIP_TRY(hipMemcpyAsync(beta, ctx->d_bscal.p + kNRM + K, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -872,7 +956,35 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     const int64_t np = red_pairs(ctx, kp);
     double *V = ctx->d_bv.p;
     auto u = [&](int j) { return bcol(V, ctx, kp, j - 1); };   // u_j, 1-based
-    for (int j = 1; j <= m; ++j) {
+    const bool small = small_path(ctx);
+    ctx->blk_info[0] = small ? 1 : 0;
+    ctx->blk_info[1] = ctx->blk_info[5] = 0;
+    ctx->blk_info[3] = small ? 1 : 4 * m + 3;
+    if (small) {
+        SmallArnoldiArgs sa;
+        SpmmArgs tmp;
+        matrix_args(ctx, tmp);
+        sa.A = tmp.A;
+        sa.D = tmp.D;
+        sa.V = nullptr;
+        sa.ldv = (int64_t)col_len(ctx, kp);
+        sa.nact = ctx->nchunks * kChunk;
+        sa.m = m;
+        sa.jold = 1;
+        sa.sq = sa.gfin = sa.Hd = nullptr;
+        sa.break_tol = break_tol;
+        sa.brk_flag = nullptr;
+        sa.slots = ctx->use_dia ? 0 : ctx->slots;
+        double *sc = ctx->d_bscal.p;
+        const SmallBlockArgs sb{u(1), kp, ctx->blk_k, K, sc + kHB, sc + kNRM, sc + kBRK, sc + kAVN, sc + kSQ1};
+        int fmt = 0;
+        size_t lds = 0;
+        if (const int e = launch_barnoldi_small(sa, sb, kp, ctx->use_dia, ctx->opt_small_lds ? ctx->lds_per_block : 0, st, &fmt, &lds))
+            return hip_fail(ctx, (hipError_t)e, "hipFuncSetAttribute(k_barnoldi_small)");
+        ctx->blk_info[1] = fmt;
+        ctx->blk_info[5] = (int64_t)lds;
+    }
+    for (int j = 1; j <= m && !small; ++j) {
         const int g = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true);
         finalize(ctx, kFinDots, j, kp, g);
         hipLaunchKernelGGL(k_bortho, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
@@ -880,10 +992,12 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
                            ctx->d_bscal.p + kCO, ctx->d_bpart.p);
         finalize(ctx, kFinNorm, j, kp, gv, break_tol);
     }
-    // the extra product for AVNORM (:261-263) into the scratch column
-    spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false);
-    hipLaunchKernelGGL(k_bnorm, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p);
-    finalize(ctx, kFinAvn, m + 1, kp, gv);
+    if (!small) {
+        // the extra product for AVNORM (:261-263) into the scratch column
+        spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false);
+        hipLaunchKernelGGL(k_bnorm, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p);
+        finalize(ctx, kFinAvn, m + 1, kp, gv);
+    }
     std::vector<double> h((size_t)kScal);
     HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_bscal.p, (size_t)kCMB * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -901,11 +1015,19 @@ int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
     const int kp = ctx->blk_kp;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(ctx->d_bscal.p + kCMB, coef, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
-    const int g = flat_grid(ctx, kp);
-    hipLaunchKernelGGL(k_bcombine, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
-                       (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
-                       ctx->d_bpart.p);
-    finalize(ctx, kFinWsum, 0, kp, g);
+    if (small_path(ctx)) {
+        hipLaunchKernelGGL(k_bcombine_small, dim3(kp), dim3(kSmallBlock), 0, st, (int)(ctx->nchunks * kChunk), kp,
+                           bcol(ctx->d_bv.p, ctx, kp, 0), (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB,
+                           bcol(ctx->d_blk.p, ctx, kp, 0), ctx->d_bscal.p);
+        ctx->blk_info[4] = 1;
+    } else {
+        const int g = flat_grid(ctx, kp);
+        hipLaunchKernelGGL(k_bcombine, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
+                           (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
+                           ctx->d_bpart.p);
+        finalize(ctx, kFinWsum, 0, kp, g);
+        ctx->blk_info[4] = 2;
+    }
     HIP_TRY(hipMemcpyAsync(wsum, ctx->d_bscal.p + kWS, K * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -929,7 +1051,7 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
         if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
-        ctx->blk_k = 0;
+        ctx->blk_k = ctx->blk_begin_m = 0;
         if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
             ctx->d_blk.release();
             HIP_TRY(ctx->d_blk.reserve(col_len(ctx, kp), false));
@@ -979,6 +1101,61 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return 0;
     });
+}
+
+// what the three pass calls share: a context that takes blocks and holds one
+static int block_call_ok(kfsp_ctx *ctx)
+{
+    if (int rc = block_supported(ctx)) return rc;
+    if (ctx->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
+    return 0;
+}
+
+int kfsp_block_begin(kfsp_ctx *ctx, int32_t m, double *beta)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_call_ok(ctx)) return rc;
+        if (m < 1 || m > kMMax) return fail(ctx, -2, "bad m (need 1 <= m <= 100)");
+        if (m > block_mmax(ctx)) return fail(ctx, -2, "m exceeds option m_max");
+        if (!beta) return fail(ctx, -3, "null beta");
+        return block_begin(ctx, m, beta);
+    });
+}
+
+int kfsp_block_arnoldi(kfsp_ctx *ctx, int32_t m, double break_tol, double *hb, double *nrm, int32_t *brk, double *avnorm)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_call_ok(ctx)) return rc;
+        if (m < 1 || m > kMMax) return fail(ctx, -2, "bad m (need 1 <= m <= 100)");
+        if (m > block_mmax(ctx)) return fail(ctx, -2, "m exceeds option m_max");
+        if (ctx->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
+        if (m > ctx->blk_begin_m) return fail(ctx, -2, "m exceeds the m of kfsp_block_begin (the basis is laid out for that one)");
+        if (!hb || !nrm || !brk || !avnorm) return fail(ctx, -4, "null output");
+        return block_arnoldi(ctx, m, break_tol, hb, nrm, brk, avnorm);
+    });
+}
+
+int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *wsum)
+{
+    if (!ctx) return -1;
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_call_ok(ctx)) return rc;
+        if (ctx->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
+        if (mx < 1 || mx > ctx->blk_begin_m + 2) return fail(ctx, -2, "bad mx (need 1 <= mx <= m + 2 of kfsp_block_begin)");
+        if (!coef) return fail(ctx, -4, "null coef");
+        if (!wsum) return fail(ctx, -5, "null wsum");
+        return block_combine(ctx, mx, coef, wsum);
+    });
+}
+
+int kfsp_block_info(kfsp_ctx *ctx, int64_t *v)
+{
+    if (!ctx) return -1;
+    if (!v) return fail(ctx, -2, "null v");
+    for (int i = 0; i < 8; ++i) v[i] = ctx->blk_info[i];
+    return 0;
 }
 
 int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)

@@ -268,6 +268,24 @@ struct SmallArnoldiArgs {
 // lds_limit: bytes of LDS one workgroup may use; returns a hipError_t
 int launch_arnoldi_small(const SmallArnoldiArgs &a, bool dia, int64_t lds_limit, hipStream_t s);
 
+// The same pass for the k independent columns of a block (kfsp_block.hip, option block_small): one workgroup per block
+// column in ONE launch.  Row r of basis column j of block column c lies at V[j * a.ldv + r * es + c]; the scalars go to
+// the per-column arrays of the block path, entry c of rows of sk doubles.
+struct SmallBlockArgs {
+    double *V;            // row 0 of u_1 (a.V is not used)
+    int64_t es;           // doubles between the rows of a column (kp)
+    int k;                // columns that carry a start vector (workgroups c >= k only clear their columns)
+    int sk;               // doubles between the rows of the scalar arrays
+    double *hb, *nrm;     // [(j * 3 + t) * sk], [j * sk]
+    double *brk;          // in: 0 run, != 0 skip; out: j when H(j+1,j) <= break_tol
+    double *avn;
+    const double *sq1;    // ||u_1||^2 per column
+};
+// kp workgroups; fmt and lds receive the kernel variant (0 SELL from global memory, 1 banded, 2 SELL from LDS) and its
+// dynamic LDS bytes; returns a hipError_t
+int launch_barnoldi_small(const SmallArnoldiArgs &a, const SmallBlockArgs &b, int kp, bool dia, int64_t lds_limit, hipStream_t s,
+                          int *fmt, size_t *lds);
+
 // kernel launchers (kfsp_kernels.hip)
 // fmt: 0 SELL-64, 1 banded, 2 banded with group masks, 3 matrix-free box (lds_bytes = size of the factor tables),
 // 4 matrix-free box, single-factor fast path, 5 SELL-64 with dictionary-coded columns, 9 banded with dictionary-coded

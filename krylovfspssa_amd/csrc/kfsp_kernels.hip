@@ -15,6 +15,7 @@
 //   k_ortho2        both DDOT/DAXPY pairs of an IOP(2) column + DNRM2 in one pass
 //   k_combine       DGEMV :444 + clamp :447-449 + DASUM :450
 //   k_copy_nrm2     DCOPY :176 / v1 = w/beta :223-226 + DNRM2 :177,:540
+#include <type_traits>
 #include "kfsp_internal.h"
 #include "kfsp_box_dev.h"
 
@@ -1832,10 +1833,82 @@ __device__ __forceinline__ double small_product_row(const SmallArnoldiArgs &a, c
     return row_sell_pre(a.A, xs, r, off, w, dg);
 }
 
-template <int FMT>
-__global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs a)
+// Where the scalars of a pass go.  The single-vector pass writes the H image, the squared norms and the breakdown flag
+// of the multi-launch path (kfsp_arnoldi copies them out).
+struct SmallSinkSingle {
+    double *sq, *gfin, *Hd;
+    int *brk_flag;
+    int jold, m;
+    // what is known about column jold: ||u_jold||^2, u_jold . u_{jold-1}, 1/||u_{jold-1}|| (carried in a register)
+    __device__ __forceinline__ void start(double &S, double &g, double &s1) const
+    {
+        S = sq[jold];
+        g = gfin[jold];
+        s1 = jold >= 2 ? 1.0 / sqrt(sq[jold - 1]) : 0.0;
+    }
+    // column j is about to be multiplied: S = ||u_j||^2
+    __device__ __forceinline__ void column(int j, double S, double nrm) const
+    {
+        sq[j] = S;
+        if (j > jold) Hd[(size_t)(j - 2) * kMH + (j - 1)] = nrm;           // H(j,j-1)
+    }
+    __device__ __forceinline__ void h1(int j, double h, double g) const
+    {
+        Hd[(size_t)(j - 1) * kMH + (j - 2)] = h;                           // H(j-1,j)
+        gfin[j] = g;
+    }
+    __device__ __forceinline__ void h2(int j, double h) const { Hd[(size_t)(j - 1) * kMH + (j - 1)] = h; }   // H(j,j)
+    // the column behind the loop (jl = m + 1 when the loop ran)
+    __device__ __forceinline__ void last(int jl, bool looped, double S, double nrm, double g) const
+    {
+        sq[jl] = S;
+        if (looped) {
+            Hd[(size_t)(m - 1) * kMH + m] = nrm;                           // H(m+1,m)
+            gfin[m + 1] = g;
+        }
+    }
+    __device__ __forceinline__ void broke(int) const { *brk_flag = 1; }
+    __device__ __forceinline__ void avnorm(double av) const
+    {
+        Hd[(size_t)kMH * kMH] = av;
+        Hd[(size_t)kMH * kMH + 1] = sqrt(av);
+    }
+};
+
+// The block pass (kfsp_block.hip) keeps per column what block_arnoldi copies out of d_bscal: entry c of rows of sk.
+struct SmallSinkBlock {
+    double *hb, *nrm, *brk, *avn;      // already offset by the column
+    int sk;
+    double S1;                         // ||u_1||^2
+    __device__ __forceinline__ void start(double &S, double &g, double &s1) const
+    {
+        S = S1;
+        g = s1 = 0.0;
+    }
+    __device__ __forceinline__ void column(int j, double, double n) const
+    {
+        nrm[(size_t)j * sk] = n;
+        if (j > 1) hb[(size_t)((j - 1) * 3 + 2) * sk] = n;                 // H(j,j-1)
+    }
+    __device__ __forceinline__ void h1(int j, double h, double) const { hb[(size_t)(j * 3) * sk] = h; }
+    __device__ __forceinline__ void h2(int j, double h) const { hb[(size_t)(j * 3 + 1) * sk] = h; }
+    __device__ __forceinline__ void last(int jl, bool, double S, double n, double) const { column(jl, S, n); }
+    __device__ __forceinline__ void broke(int j) const { *brk = (double)j; }
+    __device__ __forceinline__ void avnorm(double av) const { *avn = sqrt(av); }
+};
+
+// The pass itself, shared by the single-vector kernel (one workgroup, STRIDED = false: rows are contiguous) and the
+// block kernel (one workgroup per block column, rows es doubles apart): the same source lines under the same
+// contraction setting, so a column's H, norms and AVNORM are the same bits on both.  V is column 0 of the basis (u_1).
+// Returns 0, or j when H(j+1,j) <= break_tol ended the pass (uniform over the workgroup).
+template <int FMT, bool STRIDED, class SINK>
+__device__ __forceinline__ int small_pass(const SmallArnoldiArgs &a, double *V, int64_t es_in, const SINK &sink)
 {
     constexpr bool DIA = FMT == 1;
+    // element of row r in a basis column; a block column has at most kSmallRows rows of at most 16 doubles: 32 bits do,
+    // and so do the chunk offsets of its generator (launch_barnoldi_small's caller checks the slots)
+    auto at = [&](int64_t r) -> int64_t { return STRIDED ? (int64_t)((int)r * (int)es_in) : r; };
+    typedef typename std::conditional<STRIDED, int, int64_t>::type chunk_off_t;
     // dynamic LDS: the source column u_j [nact doubles]; FMT 2 also the generator's slots
     // [slots doubles | slots 16-bit columns]
     extern __shared__ double dyn_lds[];
@@ -1851,11 +1924,9 @@ __global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs 
             cs[i] = (unsigned short)a.A.col[i];
         }
     }
-    double *Hd = a.Hd;
-    double S = a.sq[a.jold];          // squared norm of the column about to be multiplied
-    double g = a.gfin[a.jold];        // u_jold . u_{jold-1}
-    double s1 = a.jold >= 2 ? 1.0 / sqrt(a.sq[a.jold - 1]) : 0.0;   // 1/||u_{j-1}||, carried in a register
-    int64_t offs[kSmallTrips];
+    double S, g, s1;
+    sink.start(S, g, s1);
+    chunk_off_t offs[kSmallTrips];
     int wid[kSmallTrips];
     double dg[kSmallTrips];                            // DIAG of this lane's rows: the same in every column
 #pragma unroll
@@ -1865,35 +1936,36 @@ __global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs 
         wid[t] = 0;
         dg[t] = 0.0;
         if (!DIA && r < a.nact) {
-            offs[t] = a.A.off[r >> 6];
+            offs[t] = (chunk_off_t)a.A.off[r >> 6];
             wid[t] = (int)((a.A.off[(r >> 6) + 1] - offs[t]) >> 6);
             dg[t] = a.A.diag[r];
         }
+        if (STRIDED) {                   // a wavefront's lanes share the chunk: scalar registers, the 128 vector ones are short
+            offs[t] = (chunk_off_t)__builtin_amdgcn_readfirstlane((int)offs[t]);
+            wid[t] = __builtin_amdgcn_readfirstlane(wid[t]);
+        }
     }
     {
-        const double *src = a.V + (size_t)(a.jold - 1) * a.ldv;
-        for (int64_t r = tid; r < a.nact; r += kSmallBlock) xs[r] = src[r];
+        const double *src = V + (size_t)(a.jold - 1) * a.ldv;
+        for (int64_t r = tid; r < a.nact; r += kSmallBlock) xs[r] = src[at(r)];
     }
     __syncthreads();
-    bool broke = false;
+    int broke = 0;
     // u_{j-1} on this lane's rows: read once for the first column, then carried over (it is
     // the source column of the previous iteration)
     double v1[kSmallTrips];
 #pragma unroll
     for (int t = 0; t < kSmallTrips; ++t) {
         const int64_t r = small_row<DIA>(t);
-        v1[t] = (a.jold >= 2 && r < a.nact) ? a.V[(size_t)(a.jold - 2) * a.ldv + r] : 0.0;
+        v1[t] = (a.jold >= 2 && r < a.nact) ? V[(size_t)(a.jold - 2) * a.ldv + at(r)] : 0.0;
     }
     for (int j = a.jold; j <= a.m; ++j) {
         const bool u1 = j >= 2;
-        double *dst = a.V + (size_t)j * a.ldv;
+        double *dst = V + (size_t)j * a.ldv;
         const double nrm = sqrt(S);
-        if (tid == 0) {
-            a.sq[j] = S;
-            if (j > a.jold) Hd[(size_t)(j - 2) * kMH + (j - 1)] = nrm;     // H(j,j-1)
-        }
+        if (tid == 0) sink.column(j, S, nrm);
         if (j > a.jold && !(nrm > a.break_tol)) {      // happy breakdown :249 (S is the same in every lane)
-            broke = true;
+            broke = j - 1;
             break;
         }
         const double s2 = 1.0 / nrm;
@@ -1916,14 +1988,11 @@ __global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs 
             const double h1 = pa * s1;
             c1 = h1 * s1;
             h2 = (pb - c1 * g) * s2;
-            if (tid == 0) {
-                Hd[(size_t)(j - 1) * kMH + (j - 2)] = h1;                  // H(j-1,j)
-                a.gfin[j] = g;
-            }
+            if (tid == 0) sink.h1(j, h1, g);
         } else {
             h2 = pb * s2;
         }
-        if (tid == 0) Hd[(size_t)(j - 1) * kMH + (j - 1)] = h2;            // H(j,j)
+        if (tid == 0) sink.h2(j, h2);
         const double c2 = h2 * s2;
         double asq = 0.0, ag = 0.0;
 #pragma unroll
@@ -1933,7 +2002,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs 
                 const double v2 = xs[r];
                 const double w = y[t] - c1 * v1[t] - c2 * v2;
                 v1[t] = v2;              // next column's u_{j-1}
-                dst[r] = w;
+                dst[at(r)] = w;
                 xs[r] = w;               // own rows only; nobody gathers before the barrier below
                 asq += w * w;
                 ag += w * v2;
@@ -1946,24 +2015,18 @@ __global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs 
         s1 = s2;
     }
     if (broke) {
-        if (tid == 0) *a.brk_flag = 1;
-        return;
+        if (tid == 0) sink.broke(broke);
+        return broke;
     }
     // the extra product for AVNORM (:261-263); from column jold when the loop did not run
     const bool looped = a.jold <= a.m;
     const int jl = looped ? a.m + 1 : a.jold;
-    double *dst = a.V + (size_t)jl * a.ldv;
+    double *dst = V + (size_t)jl * a.ldv;
     const double nrm = sqrt(S);
-    if (tid == 0) {
-        a.sq[jl] = S;
-        if (looped) {
-            Hd[(size_t)(a.m - 1) * kMH + a.m] = nrm;                       // H(m+1,m)
-            a.gfin[a.m + 1] = g;
-        }
-    }
+    if (tid == 0) sink.last(jl, looped, S, nrm, g);
     if (looped && !(nrm > a.break_tol)) {
-        if (tid == 0) *a.brk_flag = 1;
-        return;
+        if (tid == 0) sink.broke(a.m);
+        return a.m;
     }
     const double s2 = 1.0 / nrm;
     double av = 0.0, dummy = 0.0;
@@ -1972,14 +2035,42 @@ __global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs 
         const int64_t r = small_row<DIA>(t);
         if (r < a.nact) {
             const double yv = s2 * small_product_row<FMT>(a, xs, vs, cs, r, offs[t], wid[t], dg[t]);
-            dst[r] = yv;
+            dst[at(r)] = yv;
             av += yv * yv;
         }
     }
     small_reduce2(av, dummy, red + rb);
-    if (tid == 0) {
-        Hd[(size_t)kMH * kMH] = av;
-        Hd[(size_t)kMH * kMH + 1] = sqrt(av);
+    if (tid == 0) sink.avnorm(av);
+    return 0;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(kSmallBlock) void k_arnoldi_small(SmallArnoldiArgs a)
+{
+    const SmallSinkSingle sink{a.sq, a.gfin, a.Hd, a.brk_flag, a.jold, a.m};
+    small_pass<FMT, false>(a, a.V, 1, sink);
+}
+
+// The block pass: workgroup c runs the whole pass of block column c (row r of column j at V[j ldv + r es + c]).  Its
+// scalars are cleared first (a column that stops early leaves zeros behind it, as the multi-launch path does), and so
+// are the basis columns the pass does not reach: u_2 .. u_{m+2} of a skipped (beta = 0) or padding column, the columns
+// behind a breakdown.  Only rows below nact are touched.
+template <int FMT>
+__global__ __launch_bounds__(kSmallBlock) void k_barnoldi_small(SmallArnoldiArgs a, SmallBlockArgs b)
+{
+    const int c = blockIdx.x, tid = threadIdx.x;
+    double *V = b.V + c;
+    const SmallSinkBlock sink{b.hb + c, b.nrm + c, b.brk + c, b.avn + c, b.sk, b.sq1[c]};
+    const bool skip = c >= b.k || b.brk[c] != 0.0;
+    for (int i = 3 + tid; i < (a.m + 2) * 3; i += kSmallBlock) sink.hb[(size_t)i * b.sk] = 0.0;
+    for (int i = 2 + tid; i <= a.m + 2; i += kSmallBlock) sink.nrm[(size_t)i * b.sk] = 0.0;
+    if (tid == 0) *sink.avn = 0.0;
+    __syncthreads();
+    const int jb = skip ? 0 : small_pass<FMT, true>(a, V, b.es, sink);
+    if (!skip && jb == 0) return;
+    for (int j = jb + 2; j <= a.m + 2; ++j) {
+        double *col = V + (size_t)(j - 1) * a.ldv;
+        for (int64_t r = tid; r < a.nact; r += kSmallBlock) col[r * b.es] = 0.0;
     }
 }
 
@@ -2004,6 +2095,26 @@ int launch_arnoldi_small(const SmallArnoldiArgs &a, bool dia, int64_t lds_limit,
     if (dia) hipLaunchKernelGGL((k_arnoldi_small<1>), dim3(1), dim3(kSmallBlock), small_lds_bytes(a.nact, 0, false), st, a);
     else if (lmat) hipLaunchKernelGGL((k_arnoldi_small<2>), dim3(1), dim3(kSmallBlock), want, st, a);
     else hipLaunchKernelGGL((k_arnoldi_small<0>), dim3(1), dim3(kSmallBlock), small_lds_bytes(a.nact, 0, false), st, a);
+    return 0;
+}
+
+int launch_barnoldi_small(const SmallArnoldiArgs &a, const SmallBlockArgs &b, int kp, bool dia, int64_t lds_limit, hipStream_t st,
+                          int *fmt, size_t *lds)
+{
+    static bool raised = false;
+    const size_t want = small_lds_bytes(a.nact, a.slots, true);
+    const bool lmat = !dia && a.slots > 0 && (int64_t)want + 512 <= lds_limit;
+    if (lmat && !raised) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_barnoldi_small<2>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit - 512);
+        if (e != hipSuccess) return (int)e;
+        raised = true;
+    }
+    *fmt = dia ? 1 : (lmat ? 2 : 0);
+    *lds = lmat ? want : small_lds_bytes(a.nact, 0, false);
+    if (dia) hipLaunchKernelGGL((k_barnoldi_small<1>), dim3(kp), dim3(kSmallBlock), *lds, st, a, b);
+    else if (lmat) hipLaunchKernelGGL((k_barnoldi_small<2>), dim3(kp), dim3(kSmallBlock), *lds, st, a, b);
+    else hipLaunchKernelGGL((k_barnoldi_small<0>), dim3(kp), dim3(kSmallBlock), *lds, st, a, b);
     return 0;
 }
 

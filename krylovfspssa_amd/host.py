@@ -104,6 +104,10 @@ def load_library():
         "kfsp_spmm": [vp, i32, i64, vp, vp],
         "kfsp_expv_block": [vp, dbl, dbl, i32, vp, vp],
         "kfsp_spmm_bench": [vp, C.c_int, C.POINTER(C.c_float)],
+        "kfsp_block_begin": [vp, i32, vp],
+        "kfsp_block_arnoldi": [vp, i32, dbl, vp, vp, vp, vp],
+        "kfsp_block_combine": [vp, i32, vp, vp],
+        "kfsp_block_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -144,6 +148,7 @@ class BlockStats(C.Structure):
 
 
 BLOCK_K_MAX = 16
+BLOCK_M_MAX = 100          # kMMax: the arrays of kfsp_block_arnoldi are laid out for it whatever m is
 
 
 def _block_columns(W, n):
@@ -703,6 +708,51 @@ class KfspContext:
         st = BlockStats()
         self._chk(self._lib.kfsp_expv_block(self._h, float(t), float(tol), int(m), _p(ws), C.byref(st)), "kfsp_expv_block")
         return ws[:k].copy(), st
+
+    def _block_k(self):
+        k = getattr(self, "block_k", 0)
+        if not 1 <= k <= BLOCK_K_MAX:
+            raise KfspError("no block was set on this context")
+        return k
+
+    def block_begin(self, m):
+        """u_1 = W for the resident block -> beta[k] (kfsp_block_begin); the basis is laid out for dimension m."""
+        k = self._block_k()
+        beta = np.zeros(BLOCK_K_MAX, dtype=np.float64)
+        self._chk(self._lib.kfsp_block_begin(self._h, int(m), _p(beta)), "kfsp_block_begin")
+        return beta[:k].copy()
+
+    def block_arnoldi(self, m, break_tol=1e-7):
+        """IOP(2) Arnoldi of dimension m for every column -> (hb, nrm, brk, avnorm): hb[j, t, c] = H(j-1,j), H(j,j),
+        H(j+1,j) (t = 0, 1, 2) of column c for j = 1..m (row 0 is unused), nrm[j, c] = ||u_j|| for j = 1..m+1, brk[c]
+        = 0, the column a breakdown ended c after, or -1 (beta = 0), avnorm[c]."""
+        k = self._block_k()
+        hb = np.zeros(((BLOCK_M_MAX + 2), 3, BLOCK_K_MAX), dtype=np.float64)
+        nrm = np.zeros((BLOCK_M_MAX + 3, BLOCK_K_MAX), dtype=np.float64)
+        brk = np.zeros(BLOCK_K_MAX, dtype=np.int32)
+        avn = np.zeros(BLOCK_K_MAX, dtype=np.float64)
+        self._chk(self._lib.kfsp_block_arnoldi(self._h, int(m), float(break_tol), _p(hb), _p(nrm), _p(brk), _p(avn)),
+                  "kfsp_block_arnoldi")
+        return hb[:m + 1, :, :k].copy(), nrm[:m + 2, :k].copy(), brk[:k].copy(), avn[:k].copy()
+
+    def block_combine(self, mx, coef):
+        """W_c = max(sum_{i < mx} coef[i, c] u_{i+1,c}, 0) for the resident block -> wsum[k]"""
+        k = self._block_k()
+        coef = np.asarray(coef, dtype=np.float64)
+        if coef.ndim != 2 or coef.shape[0] < mx or coef.shape[1] != k:
+            raise ValueError(f"coef must have shape (>= {mx}, {k}), got {coef.shape}")
+        cf = np.zeros((int(mx), BLOCK_K_MAX), dtype=np.float64)
+        cf[:, :k] = coef[:mx]
+        ws = np.zeros(BLOCK_K_MAX, dtype=np.float64)
+        self._chk(self._lib.kfsp_block_combine(self._h, int(mx), _p(cf), _p(ws)), "kfsp_block_combine")
+        return ws[:k].copy()
+
+    def block_info(self):
+        """how the last block calls ran (kfsp_block_info)"""
+        v = np.zeros(8, dtype=np.int64)
+        self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info")
+        return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes"),
+                        (int(x) for x in v[:6])))
 
     def spmm_bench(self, reps):
         """ms for reps block products on the resident block"""
