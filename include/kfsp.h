@@ -471,7 +471,25 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
  * A block lives beside w (w is never touched) until the
  * generator changes: the next kfsp_set_matrix_* / kfsp_update_matrix_ell / kfsp_drop_compact / kfsp_expand_resident
  * discards it, and kfsp_get_block then fails.  On the device a block holds kp = k rounded up to 2, 4, 8 or 16 doubles
- * per row (zero padding columns); the basis of kfsp_expv_block takes (m + 2) kp rows-long columns. */
+ * per row (zero padding columns); the basis of kfsp_expv_block takes (m + 2) kp rows-long columns.
+ * BACKWARD SOLVES.  Option "adjoint" = 1 (default 0; read by kfsp_spmm, kfsp_block_begin / _arnoldi / _combine,
+ * kfsp_expv_block and kfsp_spmm_bench at every call, so it may change between two calls on one context) makes the
+ * product of all of them Y = A^T X.  A is the FSP-truncated generator exactly as the forward product applies it: DIAG
+ * is still the sum of ALL propensities of a state, including those of reactions that leave the FSP.  So for a column f
+ * (a function of the state: a count, a product of counts, the indicator of a set) u = exp(t A^T) f is
+ *   u(x) = E[ f(X_t) ; X has not left the FSP up to t | X_0 = x ]    for every state x at once
+ * (the backward Kolmogorov equation on the truncated generator), and 1 - exp(t A^T) 1 is the probability of having left
+ * the FSP by t per start state.  Everything behind the product - the k independent IOP(2) bases, the step control, the
+ * Pade - is the forward path's.  Per column the order of operations of a row is fixed (s = -(DIAG x) first, then one
+ * fused multiply-add per entry: banded diagonals ascending, reference slots ascending, box slots species by species),
+ * so column j of A^T X does not depend on k or on the slot it sits in.  With "adjoint" = 1 the calls also return -12
+ * for a SELL context whose reference arrays ADJ / OFFDIAG / DIAG are not resident (kfsp_set_matrix_csr uploads: the
+ * transposed SELL product reads those arrays; kfsp_set_matrix_ell keeps them, option box_store = 1 stores a box as
+ * diagonals), and option "block_small" is not taken (the multi-launch path runs).  Partitions, mixed forward and backward
+ * columns in one block and the Fortran binding are not provided.
+ * Option "block_clamp" = 0 (default 1, independent of "adjoint"): kfsp_block_combine and the steps of kfsp_expv_block do
+ * not clamp at 0 - W_c = sum_i coef_i u_i from the same chain of fused multiply-adds - and wsum[c] = sum_i |W_ic|: an
+ * observable may be signed, and the backward solution of a signed f is no probability vector. */
 /* k start vectors (1 <= k <= 16), W column-major host memory W[j*ldw + i], i in the caller's order (the internal state
  * order is applied as in kfsp_set_vector); n = the number of states of the generator */
 int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W);
@@ -515,7 +533,8 @@ int kfsp_block_arnoldi(kfsp_ctx *ctx, int32_t m, double break_tol, double *hb, d
 int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *wsum /* [16] */);
 /* kfsp_block_info: how the last block calls ran: v[0] = 1 when the last kfsp_block_arnoldi (or pass of kfsp_expv_block) was one launch,
  * v[1] its kernel variant (0 SELL from global memory, 1 banded, 2 SELL from LDS), v[2], v[3], v[4] = kernel launches
- * enqueued by the last begin, arnoldi, combine, v[5] = dynamic LDS bytes of the pass kernel, v[6..7] = 0 */
+ * enqueued by the last begin, arnoldi, combine, v[5] = dynamic LDS bytes of the pass kernel, v[6] = 1 when the last
+ * kfsp_block_arnoldi, kfsp_spmm or kfsp_spmm_bench multiplied with A^T (option "adjoint"), v[7] = 0 */
 int kfsp_block_info(kfsp_ctx *ctx, int64_t v[8]);
 
 /* ---- lock-step diagnostics ---------------------------------------------- */
@@ -648,7 +667,7 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
- * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
+ * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
  * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other

@@ -2633,6 +2633,8 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "box_tile") ctx->opt_box_tile = value;
     else if (k == "block_box") ctx->opt_block_box = value;
     else if (k == "block_small") ctx->opt_block_small = value;
+    else if (k == "adjoint") ctx->opt_adjoint = value != 0;
+    else if (k == "block_clamp") ctx->opt_block_clamp = value != 0;
     else if (k == "box_pencil") ctx->opt_box_pencil = value;
     else if (k == "box_slab_waves") ctx->opt_box_slab_waves = value;
     else if (k == "sell_code") ctx->opt_sell_code = value;

@@ -29,7 +29,7 @@
 // k_arnoldi_small, compiled from the same lines) and k_bcombine_small.
 #pragma clang fp contract(off)
 
-#include "kfsp_block.h"
+#include "kfsp_block_dev.h"
 #include "kfsp_box_dev.h"
 #include "kfsp_ctx.h"
 
@@ -57,45 +57,6 @@ constexpr int kCMB = kWS + K;                   // [kMMax + 3][K]: combine coeff
 constexpr int kSQ1 = kCMB + (kMMax + 3) * K;    // [K]: ||u_1||^2 (what k_barnoldi_small starts from)
 constexpr int kScal = kSQ1 + K;
 constexpr int kSmallBlock = 1024;               // lanes of a small-path workgroup
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef int i2 __attribute__((ext_vector_type(2)));
-
-template <int KP>
-__device__ __forceinline__ void ld_row(const double *__restrict__ X, int64_t row, double (&x)[KP])
-{
-    const d2 *p = reinterpret_cast<const d2 *>(X + row * KP);
-#pragma unroll
-    for (int q = 0; q < KP / 2; ++q) {
-        const d2 t = p[q];
-        x[2 * q] = t.x;
-        x[2 * q + 1] = t.y;
-    }
-}
-
-template <int KP>
-__device__ __forceinline__ void st_row(double *__restrict__ Y, int64_t row, const double (&s)[KP])
-{
-    d2 *p = reinterpret_cast<d2 *>(Y + row * KP);
-#pragma unroll
-    for (int q = 0; q < KP / 2; ++q) p[q] = d2{s[2 * q], s[2 * q + 1]};
-}
-
-// s = -(diag x): the single-vector kernels' v_mul_f64 of DIAG and x with the sign folded in
-template <int KP>
-__device__ __forceinline__ void diag_row(double dg, const double (&x)[KP], double (&s)[KP])
-{
-#pragma unroll
-    for (int c = 0; c < KP; ++c) s[c] = -(dg * x[c]);
-}
-
-// s += v x as ONE rounding per column (the single-vector kernels' v_fmac_f64)
-template <int KP>
-__device__ __forceinline__ void fma_row(double v, const double (&x)[KP], double (&s)[KP])
-{
-#pragma unroll
-    for (int c = 0; c < KP; ++c) s[c] = __builtin_fma(v, x[c], s[c]);
-}
 
 // SELL-64 row (plain or dictionary-coded columns), the slot order and addresses of row_sell / row_sell_coded
 template <int KP, bool CODED>
@@ -184,40 +145,6 @@ __device__ __forceinline__ void row_dia_blk(const DiaDev &D, const double *__res
         ld_row<KP>(X, xr(ge + (on0 ? D.delta[d] : 0)), x0);
         fma_row<KP>(v0, x0, s);
     }
-}
-
-struct SpmmArgs {
-    SellDev A;
-    DiaDev D;
-    const double *X;
-    double *Y;
-    const double *ua, *ub;   // DOTS: partials of ua . Y (ua may be null) and ub . Y per column
-    double *part;            // [2][kMaxGrid][K]
-    int64_t trips;
-    const int32_t *trip_order;
-    int64_t rows_red;        // rows that enter the reductions
-    const double *box_tab;   // matrix-free box: the table image (staged to LDS), its length in doubles and the
-    int box_ntab;            // single-factor descriptor behind it
-    const BoxFast *box_fast;
-};
-
-// per-column sums of the block: v[c] summed over the wavefront, then the four wavefronts in a fixed order
-template <int KP>
-__device__ __forceinline__ void block_sum_cols(double (&v)[KP], double *red, double *out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < KP; ++c)
-        for (int o = 32; o >= 1; o >>= 1) v[c] += __shfl_xor(v[c], o);
-    if (lane == 0)
-#pragma unroll
-        for (int c = 0; c < KP; ++c) red[wave * KP + c] = v[c];
-    __syncthreads();
-    if (threadIdx.x < KP) {
-        const int c = threadIdx.x;
-        out[c] = (red[c] + red[KP + c]) + (red[2 * KP + c] + red[3 * KP + c]);
-    }
-    __syncthreads();
 }
 
 // FMT: 0 SELL-64, 5 SELL-64 with coded columns, 1 banded, 2 banded with group masks.  XCD-aware trip mapping and
@@ -467,9 +394,11 @@ __global__ __launch_bounds__(kBlock) void k_bnorm(int64_t npairs, int half, cons
     flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
 }
 
-// W = max(sum_i coef_i u_i, 0) (DGEMV :444, clamp :447-449), partial: sum W (DASUM :450)
+// W = max(sum_i coef_i u_i, 0) (DGEMV :444, clamp :447-449), partial: sum W (DASUM :450).  clamp = 0 (option block_clamp,
+// signed observables of a backward solve): W = sum_i coef_i u_i as it comes out of the same fma chain, partial: sum |W|
 __global__ __launch_bounds__(kBlock) void k_bcombine(int64_t npairs, int half, const double *__restrict__ U, int64_t ldc, int mx,
-                                                     const double *__restrict__ coef, d2 *__restrict__ w, double *__restrict__ part)
+                                                     const double *__restrict__ coef, d2 *__restrict__ w, double *__restrict__ part,
+                                                     int clamp)
 {
     __shared__ double red[8 * K];
     const int q = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) % half);
@@ -481,11 +410,13 @@ __global__ __launch_bounds__(kBlock) void k_bcombine(int64_t npairs, int half, c
             s.x = __builtin_fma(coef[j * K + 2 * q], u.x, s.x);
             s.y = __builtin_fma(coef[j * K + 2 * q + 1], u.y, s.y);
         }
-        s.x = s.x > 0.0 ? s.x : 0.0;
-        s.y = s.y > 0.0 ? s.y : 0.0;
+        if (clamp) {
+            s.x = s.x > 0.0 ? s.x : 0.0;
+            s.y = s.y > 0.0 ? s.y : 0.0;
+        }
         w[i] = s;
-        a0 += s.x;
-        a1 += s.y;
+        a0 += clamp ? s.x : __builtin_fabs(s.x);
+        a1 += clamp ? s.y : __builtin_fabs(s.y);
     }
     flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
 }
@@ -615,10 +546,10 @@ __global__ __launch_bounds__(kSmallBlock) void k_bbegin_small(int nact, int kp, 
     sc[kSQ1 + c] = s0;
 }
 
-// W_c = max(sum_i coef_i u_{i+1,c}, 0) and its sum: per element the operations of k_bcombine in its order
+// W_c = max(sum_i coef_i u_{i+1,c}, 0) and its sum: per element the operations of k_bcombine in its order, clamp included
 __global__ __launch_bounds__(kSmallBlock) void k_bcombine_small(int nact, int kp, const double *__restrict__ U, int64_t ldc, int mx,
                                                                 const double *__restrict__ coef, double *__restrict__ w,
-                                                                double *__restrict__ sc)
+                                                                double *__restrict__ sc, int clamp)
 {
     __shared__ double red[kSmallBlock / 64];
     const int c = blockIdx.x;
@@ -626,9 +557,9 @@ __global__ __launch_bounds__(kSmallBlock) void k_bcombine_small(int nact, int kp
     for (int r = threadIdx.x; r < nact; r += kSmallBlock) {
         double s = 0.0;
         for (int j = 0; j < mx; ++j) s = __builtin_fma(coef[j * K + c], U[(size_t)j * ldc + r * kp + c], s);
-        s = s > 0.0 ? s : 0.0;
+        if (clamp) s = s > 0.0 ? s : 0.0;
         w[r * kp + c] = s;
-        a += s;
+        a += clamp ? s : __builtin_fabs(s);
     }
     const double s0 = small_sum(a, red);
     if (threadIdx.x == 0) sc[kWS + c] = s0;
@@ -661,6 +592,8 @@ struct PhaseTimer {
     ~PhaseTimer() { c->t_ms[phase] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+const char *const kAdjFormMsg = "several vectors at once, option adjoint: the generator is resident in no form the transposed product reads";
+
 const char *const kBoxReachMsg = "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
                                  "at this block width (fewer columns, or option box_store = 1)";
 
@@ -686,10 +619,11 @@ int spmm_grid(const kfsp_ctx *c)
 }
 
 // The small path is taken where kfsp_arnoldi (qiop = 2) takes k_arnoldi_small on this context (kfsp_api.cpp), short of
-// coded SELL columns: those stay on the multi-launch path.
+// coded SELL columns: those stay on the multi-launch path.  So does every backward pass (option adjoint): k_barnoldi_small
+// has the forward product compiled in.
 bool small_path(const kfsp_ctx *c)
 {
-    return c->opt_block_small != 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->use_box &&
+    return c->opt_block_small != 0 && c->opt_adjoint == 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->use_box &&
            c->nchunks * kChunk <= kSmallRows && (c->use_dia || (c->have_sell && !c->sell_coded)) && c->slots < (1LL << 31);
 }
 
@@ -786,7 +720,50 @@ void matrix_args(const kfsp_ctx *ctx, SpmmArgs &a)
     a.D.zero = ctx->d_zero.p;
 }
 
-// Y = A X (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
+// The reference arrays in the order the device keeps its vectors: the relabelled copies under the internal state order.
+bool ell_adj_args(const kfsp_ctx *ctx, EllAdjDev &e)
+{
+    const DevBuf<int32_t> &adj = ctx->perm_on ? ctx->d_ell_adj2 : ctx->d_ell_adj;
+    const DevBuf<double> &off = ctx->perm_on ? ctx->d_ell_off2 : ctx->d_ell_off;
+    const DevBuf<double> &diag = ctx->perm_on ? ctx->d_ell_diag2 : ctx->d_ell_diag;
+    if (!adj.p || !off.p || !diag.p || !ell_adj_resident(ctx->n, ctx->ell_cols, ctx->ell_ld, ctx->ell_bw, adj.cap, off.cap, diag.cap))
+        return false;
+    e = EllAdjDev{adj.p, off.p, diag.p, ctx->n, ctx->ell_ld, ctx->ell_bw};
+    return true;
+}
+
+// Y = A^T X (option adjoint, kfsp_block_adj.hip): the grid rules of the forward product of the same form.  -1: the
+// generator is in no form the transposed product reads (block_supported refuses those first).
+int spmm_adjoint(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
+{
+    if (ctx->use_box) {
+        BoxAdjDev b;
+        if (!box_adj_build(ctx->box, b)) return -1;
+        const size_t lds = std::max<size_t>(ctx->box_lds_bytes, (size_t)4 * kp * sizeof(double));
+        int &occ = ctx->blk_box_t_occ[kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3))][dots ? 1 : 0];
+        if (occ == 0) occ = spmm_box_t_resident(kp, ctx->box.pad, dots, lds);
+        int64_t g = round_up((a.trips + 3) / 4, 8);
+        g = std::min<int64_t>(g, ctx->opt_grid > 0 ? std::min<int64_t>(round_up(ctx->opt_grid, 8), kMaxGrid)
+                                                   : std::min<int64_t>(1024, (int64_t)256 * occ));
+        g = std::max<int64_t>(g, 8);
+        a.box_tab = ctx->d_box.p;
+        a.box_ntab = ctx->box.ntab;
+        a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
+        launch_spmm_box_t(kp, ctx->box.pad, dots, (int)g, lds, a, b, ctx->stream);
+        return (int)g;
+    }
+    const int g = spmm_grid(ctx);
+    if (ctx->use_dia) {
+        launch_spmm_t(kp, dots, g, a, ctx->stream);
+        return g;
+    }
+    EllAdjDev e;
+    if (!ell_adj_args(ctx, e)) return -1;
+    launch_spmm_ell_t(kp, dots, g, a, e, ctx->stream);
+    return g;
+}
+
+// Y = A X, or A^T X under option adjoint (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
 int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
 {
     SpmmArgs a;
@@ -802,6 +779,7 @@ int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, co
     a.box_tab = nullptr;
     a.box_ntab = 0;
     a.box_fast = nullptr;
+    if (ctx->opt_adjoint) return spmm_adjoint(ctx, kp, dots, a);
     if (ctx->use_box) return spmm_box(ctx, kp, dots, a);
     const int g = spmm_grid(ctx);
     const int fmt = spmm_fmt(ctx);
@@ -891,6 +869,7 @@ void block_release(kfsp_ctx *ctx)
     ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->blk_begin_m = 0;
     std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
     std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
+    std::memset(ctx->blk_box_t_occ, 0, sizeof(ctx->blk_box_t_occ));
 }
 
 int block_supported(kfsp_ctx *ctx)
@@ -909,6 +888,11 @@ int block_supported(kfsp_ctx *ctx)
         return 0;
     }
     if (!ctx->use_dia && !ctx->have_sell) return fail(ctx, -12, "several vectors at once: no stored generator");
+    EllAdjDev e;
+    if (ctx->opt_adjoint && !ctx->use_dia && !ell_adj_args(ctx, e))
+        return fail(ctx, -12, "several vectors at once, option adjoint: the transposed product of a SELL generator reads the reference "
+                              "arrays ADJ / OFFDIAG / DIAG, and none are resident for this one (kfsp_set_matrix_ell uploads them; "
+                              "option box_store = 1 stores a box as diagonals)");
     return 0;
 }
 
@@ -959,6 +943,7 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     const bool small = small_path(ctx);
     ctx->blk_info[0] = small ? 1 : 0;
     ctx->blk_info[1] = ctx->blk_info[5] = 0;
+    ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
     ctx->blk_info[3] = small ? 1 : 4 * m + 3;
     if (small) {
         SmallArnoldiArgs sa;
@@ -986,6 +971,7 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     }
     for (int j = 1; j <= m && !small; ++j) {
         const int g = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true);
+        if (g < 0) return fail(ctx, -12, kAdjFormMsg);
         finalize(ctx, kFinDots, j, kp, g);
         hipLaunchKernelGGL(k_bortho, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
                            reinterpret_cast<const d2 *>(j >= 2 ? u(j - 1) : nullptr), reinterpret_cast<const d2 *>(u(j)),
@@ -994,7 +980,7 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     }
     if (!small) {
         // the extra product for AVNORM (:261-263) into the scratch column
-        spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false);
+        if (spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false) < 0) return fail(ctx, -12, kAdjFormMsg);
         hipLaunchKernelGGL(k_bnorm, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p);
         finalize(ctx, kFinAvn, m + 1, kp, gv);
     }
@@ -1018,13 +1004,13 @@ int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
     if (small_path(ctx)) {
         hipLaunchKernelGGL(k_bcombine_small, dim3(kp), dim3(kSmallBlock), 0, st, (int)(ctx->nchunks * kChunk), kp,
                            bcol(ctx->d_bv.p, ctx, kp, 0), (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB,
-                           bcol(ctx->d_blk.p, ctx, kp, 0), ctx->d_bscal.p);
+                           bcol(ctx->d_blk.p, ctx, kp, 0), ctx->d_bscal.p, ctx->opt_block_clamp ? 1 : 0);
         ctx->blk_info[4] = 1;
     } else {
         const int g = flat_grid(ctx, kp);
         hipLaunchKernelGGL(k_bcombine, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
                            (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
-                           ctx->d_bpart.p);
+                           ctx->d_bpart.p, ctx->opt_block_clamp ? 1 : 0);
         finalize(ctx, kFinWsum, 0, kp, g);
         ctx->blk_info[4] = 2;
     }
@@ -1096,7 +1082,8 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         if (int rc = ensure_basis(ctx, kp, 2)) return rc;
         double *x = bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
         if (int rc = upload_block(ctx, k, kp, ld, X, x)) return rc;
-        spmm(ctx, kp, x, y, nullptr, nullptr, false);
+        if (spmm(ctx, kp, x, y, nullptr, nullptr, false) < 0) return fail(ctx, -12, kAdjFormMsg);
+        ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
         if (int rc = download_block(ctx, k, kp, y, ld, Y)) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return 0;
@@ -1172,7 +1159,9 @@ int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)
         const double *x = bcol(ctx->d_blk.p, ctx, kp, 0);
         double *y = bcol(ctx->d_bv.p, ctx, kp, 0);
         HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-        for (int r = 0; r < reps; ++r) spmm(ctx, kp, x, y, nullptr, nullptr, false);
+        ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
+        for (int r = 0; r < reps; ++r)
+            if (spmm(ctx, kp, x, y, nullptr, nullptr, false) < 0) return fail(ctx, -12, kAdjFormMsg);
         HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
         HIP_TRY(hipEventSynchronize(ctx->ev1));
         HIP_TRY(hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));

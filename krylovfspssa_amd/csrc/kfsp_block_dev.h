@@ -1,0 +1,171 @@
+// Private: what the two translation units of the block product share - kfsp_block.hip (Y = A X and everything behind
+// the product) and kfsp_block_adj.hip (Y = A^T X, option adjoint).  The row helpers, SpmmArgs and block_sum_cols are the
+// ones kfsp_block.hip always had; the descriptors at the end belong to the transposed product.
+#pragma once
+
+#include "kfsp_block.h"
+#include "kfsp_internal.h"
+
+namespace kfsp {
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef int i2 __attribute__((ext_vector_type(2)));
+
+#if defined(__HIPCC__)
+template <int KP>
+__device__ __forceinline__ void ld_row(const double *__restrict__ X, int64_t row, double (&x)[KP])
+{
+    const d2 *p = reinterpret_cast<const d2 *>(X + row * KP);
+#pragma unroll
+    for (int q = 0; q < KP / 2; ++q) {
+        const d2 t = p[q];
+        x[2 * q] = t.x;
+        x[2 * q + 1] = t.y;
+    }
+}
+
+template <int KP>
+__device__ __forceinline__ void st_row(double *__restrict__ Y, int64_t row, const double (&s)[KP])
+{
+    d2 *p = reinterpret_cast<d2 *>(Y + row * KP);
+#pragma unroll
+    for (int q = 0; q < KP / 2; ++q) p[q] = d2{s[2 * q], s[2 * q + 1]};
+}
+
+// s = -(diag x): the single-vector kernels' v_mul_f64 of DIAG and x with the sign folded in
+template <int KP>
+__device__ __forceinline__ void diag_row(double dg, const double (&x)[KP], double (&s)[KP])
+{
+#pragma unroll
+    for (int c = 0; c < KP; ++c) s[c] = -(dg * x[c]);
+}
+
+// s += v x as ONE rounding per column (the single-vector kernels' v_fmac_f64)
+template <int KP>
+__device__ __forceinline__ void fma_row(double v, const double (&x)[KP], double (&s)[KP])
+{
+#pragma unroll
+    for (int c = 0; c < KP; ++c) s[c] = __builtin_fma(v, x[c], s[c]);
+}
+#endif
+
+struct SpmmArgs {
+    SellDev A;
+    DiaDev D;
+    const double *X;
+    double *Y;
+    const double *ua, *ub;   // DOTS: partials of ua . Y (ua may be null) and ub . Y per column
+    double *part;            // [2][kMaxGrid][kBlockMaxK]
+    int64_t trips;
+    const int32_t *trip_order;
+    int64_t rows_red;        // rows that enter the reductions
+    const double *box_tab;   // matrix-free box: the table image (staged to LDS), its length in doubles and the
+    int box_ntab;            // single-factor descriptor behind it
+    const BoxFast *box_fast;
+};
+
+#if defined(__HIPCC__)
+// per-column sums of the block: v[c] summed over the wavefront, then the four wavefronts in a fixed order
+template <int KP>
+__device__ __forceinline__ void block_sum_cols(double (&v)[KP], double *red, double *out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < KP; ++c)
+        for (int o = 32; o >= 1; o >>= 1) v[c] += __shfl_xor(v[c], o);
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < KP; ++c) red[wave * KP + c] = v[c];
+    __syncthreads();
+    if (threadIdx.x < KP) {
+        const int c = threadIdx.x;
+        out[c] = (red[c] + red[KP + c]) + (red[2 * KP + c] + red[3 * KP + c]);
+    }
+    __syncthreads();
+}
+#endif
+
+// ---- the transposed product (kfsp_block_adj.hip)
+
+// The reference arrays ADJ / OFFDIAG / DIAG as they stay on the device (kfsp_build.hip), in the order the device keeps
+// its vectors: column c holds the reactions that LEAVE state c - the gather row c of A^T.
+struct EllAdjDev {
+    const int32_t *adj;      // [n][ld], 1-based target of slot k of state c at adj[c * ld + k]; outside [1, n]: no target
+    const double *off;       // [n][ld] the propensities
+    const double *diag;      // [n]
+    int64_t n;
+    int32_t ld, bw;
+};
+
+// Row of A^T of a single-factor box, beside BoxFast (whose image and layout stay as they are): for slot (s, j) of the
+// forward form - the j-th reaction, by ascending source offset, whose propensity depends on species s - the offset of the
+// propensity at the row's OWN coordinate, the X offset of the TARGET state x + nu and which coordinate tests the target
+// has to pass.  Uniform kernel argument.
+struct BoxAdjDev {
+    int32_t aoff8[kBoxFastS][kBoxFastPer];    // byte offset in the LDS image of the slot's factor table (+ 8 x_s: a_k(x))
+    int32_t tdelta8[kBoxFastS][kBoxFastPer];  // 8 * (x index of the target state relative to the row)
+    uint32_t need[kBoxFastS][kBoxFastPer];    // bits the row's test word must have: bit 5 s + nu_s + 2 for every species the
+                                              // reaction moves; kBoxAdjNever for an unused slot
+    int32_t bias8;                            // bytes the wave's x base lies below its first row (>= the largest backward reach)
+};
+constexpr uint32_t kBoxAdjNever = 1u << 31;   // a bit no test word has
+
+// Fills the descriptor from the box as kfsp_set_matrix_box stored it (reactions by ascending source offset; inst = species
+// of the instantiation * 16 + slots per species, BoxDev::pad).  False: the box is not a single-factor one of that shape.
+static inline bool box_adj_build(const BoxDev &B, BoxAdjDev &out)
+{
+    const int ns_inst = B.pad / 16, per = B.pad % 16;
+    if (ns_inst < 1 || ns_inst > kBoxFastS || per < 1 || per > kBoxFastPer || B.ns < 1 || B.ns > ns_inst || B.nr < 1 ||
+        B.nr > kBoxMaxR)
+        return false;
+    for (int s = 0; s < kBoxFastS; ++s)
+        for (int j = 0; j < kBoxFastPer; ++j) {
+            out.aoff8[s][j] = 0;
+            out.tdelta8[s][j] = 0;
+            out.need[s][j] = kBoxAdjNever;
+        }
+    int fill[kBoxFastS] = {0};
+    int64_t fwd = 0;
+    for (int p = 0; p < B.nr; ++p) {
+        if (B.ndep[p] != 1) return false;
+        const int s = B.dep_s[p][0];
+        if (s < 0 || s >= B.ns) return false;
+        const int j = fill[s]++;
+        if (j >= per) return false;
+        uint32_t need = 0;
+        if (B.nmov[p] < 0 || B.nmov[p] > kBoxMaxDep) return false;
+        for (int i = 0; i < B.nmov[p]; ++i) {
+            const int ms = B.mov_s[p][i], nu = B.mov_nu[p][i];
+            if (ms < 0 || ms >= B.ns || nu < -2 || nu > 2) return false;
+            need |= 1u << (5 * ms + nu + 2);
+        }
+        out.aoff8[s][j] = 8 * B.dep_off[p][0];
+        out.tdelta8[s][j] = -8 * B.delta[p];
+        out.need[s][j] = need;
+        fwd = B.delta[p] > fwd ? (int64_t)B.delta[p] : fwd;
+    }
+    out.bias8 = (int32_t)(8 * fwd);
+    return true;
+}
+
+// The transposed SELL product reads the reference arrays: they must be the current generator's (n columns resident,
+// a leading dimension that holds the bw slots) and the buffers as long as that says.
+static inline bool ell_adj_resident(int64_t n, int64_t ell_cols, int32_t ell_ld, int32_t ell_bw, size_t cap_adj, size_t cap_off,
+                             size_t cap_diag)
+{
+    if (n < 1 || ell_cols != n || ell_bw < 1 || ell_ld < ell_bw) return false;
+    const size_t nent = (size_t)n * (size_t)ell_ld;
+    return cap_adj >= nent && cap_off >= nent && cap_diag >= (size_t)n;
+}
+
+// launches (kfsp_block_adj.hip); the grid is the caller's.  Hidden: the shared object exports nothing new.
+#define KFSP_LOCAL __attribute__((visibility("hidden")))
+KFSP_LOCAL void launch_spmm_t(int kp, bool dots, int grid, const SpmmArgs &a, hipStream_t st);
+KFSP_LOCAL void launch_spmm_ell_t(int kp, bool dots, int grid, const SpmmArgs &a, const EllAdjDev &e, hipStream_t st);
+// workgroups of k_spmm_box_t resident per CU with `lds` bytes of dynamic LDS (>= 1)
+KFSP_LOCAL int spmm_box_t_resident(int kp, int inst, bool dots, size_t lds);
+KFSP_LOCAL void launch_spmm_box_t(int kp, int inst, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxAdjDev &b,
+                                  hipStream_t st);
+#undef KFSP_LOCAL
+
+}  // namespace kfsp

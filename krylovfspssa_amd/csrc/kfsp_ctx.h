@@ -327,6 +327,7 @@ struct kfsp_ctx {
     int blk_begin_m = 0;         // Krylov dimension the last block_begin laid the basis out for (0: none since kfsp_set_block)
     int64_t blk_info[8] = {};    // kfsp_block_info: how the last block_begin / block_arnoldi / block_combine ran
     int blk_box_occ[4][2] = {};  // workgroups of k_spmm_box resident per CU, by [log2 kp - 1][dots] (0: not asked yet)
+    int blk_box_t_occ[4][2] = {};   // the same for k_spmm_box_t (kfsp_block_adj.hip)
 
     // scalars
     DevBuf<double> d_part;   // kNumPartial * kMaxGrid
@@ -377,6 +378,8 @@ struct kfsp_ctx {
     int64_t opt_box_store = 0;            // 1: kfsp_set_matrix_box writes the generator out as stored diagonals on the device (banded form)
     int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12)
     int64_t opt_block_small = 0;          // 1: the block path takes its one-launch kernels where the single-vector path takes k_arnoldi_small
+    int64_t opt_adjoint = 0;              // 1: the block calls multiply with A^T (kfsp_block_adj.hip): backward solves exp(tA^T) F
+    int64_t opt_block_clamp = 1;          // 0: the block combine does not clamp at 0 and wsum is the l1 norm (signed observables)
     int64_t opt_state_order = 1;          // 1: use kfsp_set_state_coords for large, long-lived generators (0: never)
     int64_t opt_ssa_general = 0;          // 1: the SSA walk always runs its general kernel (A/B of the register-resident one)
     int64_t opt_keep_coords = 0;          // 1: coordinates handed over stay resident even when no order is derived from them

@@ -691,22 +691,44 @@ class KfspContext:
         self._chk(self._lib.kfsp_get_block(self._h, k, self.n, self.n, _p(W)), "kfsp_get_block")
         return W
 
-    def spmm(self, X):
+    def _with_block_options(self, call, adjoint, clamp):
+        """call() with option "adjoint" = 1 / "block_clamp" = 0 where asked for; afterwards each option that was changed
+        is back at what set_option last set (else the library's default).  A forward, clamped call touches no option."""
+        seen = getattr(self, "_options", {})
+        todo = []
+        if adjoint:
+            todo.append(("adjoint", 1, seen.get("adjoint", 0)))
+        if not clamp:
+            todo.append(("block_clamp", 0, seen.get("block_clamp", 1)))
+        for name, v, _ in todo:
+            self.set_option(name, v)
+        try:
+            return call()
+        finally:
+            for name, _, old in todo:
+                self.set_option(name, old)
+
+    def spmm(self, X, adjoint=False):
         """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j]) - also on a
-        matrix-free box under set_option("block_box", 1)."""
+        matrix-free box under set_option("block_box", 1).  adjoint=True: A^T X (option "adjoint" round the call)."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
-        self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm")
+        self._with_block_options(lambda: self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm"),
+                                 adjoint, True)
         return Y
 
-    def expv_block(self, t, tol, m=30):
-        """W <- exp(t A) W for the resident block -> (wsum[k], BlockStats)."""
+    def expv_block(self, t, tol, m=30, adjoint=False, clamp=True):
+        """W <- exp(t A) W for the resident block -> (wsum[k], BlockStats).  adjoint=True: the backward solve
+        W <- exp(t A^T) W, E[f(X_t); still inside the FSP | X_0 = x] for every state x and observable column f;
+        clamp=False: columns are not clamped at 0 after a step (signed observables) and wsum is their l1 norm.  Both are
+        the options "adjoint" / "block_clamp", set round the call and put back to forward / clamped."""
         k = getattr(self, "block_k", 0)
         if not 1 <= k <= BLOCK_K_MAX:
             raise KfspError("no block was set on this context")
         ws = np.zeros(BLOCK_K_MAX, dtype=np.float64)
         st = BlockStats()
-        self._chk(self._lib.kfsp_expv_block(self._h, float(t), float(tol), int(m), _p(ws), C.byref(st)), "kfsp_expv_block")
+        self._with_block_options(lambda: self._chk(self._lib.kfsp_expv_block(self._h, float(t), float(tol), int(m), _p(ws),
+                                                                             C.byref(st)), "kfsp_expv_block"), adjoint, clamp)
         return ws[:k].copy(), st
 
     def _block_k(self):
@@ -751,8 +773,8 @@ class KfspContext:
         """how the last block calls ran (kfsp_block_info)"""
         v = np.zeros(8, dtype=np.int64)
         self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info")
-        return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes"),
-                        (int(x) for x in v[:6])))
+        return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes", "adjoint"),
+                        (int(x) for x in v[:7])))
 
     def spmm_bench(self, reps):
         """ms for reps block products on the resident block"""
@@ -763,3 +785,6 @@ class KfspContext:
     def set_option(self, name, value):
         """kfsp_set_option (include/kfsp.h lists the names), e.g. "block_box" = 1: the block calls take a matrix-free box."""
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
+        if not hasattr(self, "_options"):
+            self._options = {}
+        self._options[name] = int(value)
