@@ -1,7 +1,8 @@
 // Host side of libkfsp_hip: the C ABI of include/kfsp.h, the device context
-// (basis, vectors, generator, scalar staging), the ELL -> SELL transpose, the
-// RCCL row-partition plumbing and the host Pade exponential.
-#include "kfsp_ctx.h"
+// (basis, vectors, generator, scalar staging), the ELL -> SELL transpose and the
+// Arnoldi / combine passes.  The collectives and the halo exchange live in
+// kfsp_comm.cpp, the host Pade exponential in kfsp_padm.cpp.
+#include "kfsp_host.h"
 
 #include <algorithm>
 #include <chrono>
@@ -18,92 +19,12 @@ namespace {
 
 constexpr int kAbiVersion = 2;   // 2: kfsp_dgexpv_replay, KFSP_EV_READY
 
-}  // namespace
-
-namespace {
-
-struct PhaseTimer {
-    kfsp_ctx *c;
-    int phase;
-    std::chrono::steady_clock::time_point t0;
-    PhaseTimer(kfsp_ctx *c_, int p) : c(c_), phase(p), t0(std::chrono::steady_clock::now()) {}
-    ~PhaseTimer() { c->t_ms[phase] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-int fail(kfsp_ctx *c, int code, const char *what)
-{
-    if (c) c->err = what;
-    return code;
-}
-
-// C++ exceptions (host allocations) end at the C boundary as status codes
-template <class F>
-int no_throw(kfsp_ctx *c, F &&body)
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return fail(c, 4001, "out of host memory");
-    } catch (const std::exception &e) {
-        if (c) c->err = std::string("exception: ") + e.what();
-        return 4000;
-    } catch (...) {
-        return fail(c, 4000, "unknown exception");
-    }
-}
-
-int hip_fail(kfsp_ctx *c, hipError_t e, const char *where)
-{
-    if (c) c->err = std::string(where) + ": " + hipGetErrorString(e);
-    return 1000 + (int)e;
-}
-
-int nccl_fail(kfsp_ctx *c, ncclResult_t r, const char *where)
-{
-    if (c) c->err = std::string(where) + ": " + ncclGetErrorString(r);
-    return 2000 + (int)r;
-}
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return hip_fail(ctx, e_, #expr); \
-    } while (0)
-
-#define NCCL_TRY(expr)                                           \
-    do {                                                         \
-        ncclResult_t r_ = (expr);                                \
-        if (r_ != ncclSuccess) return nccl_fail(ctx, r_, #expr); \
-    } while (0)
-
-int spmv_grid(const kfsp_ctx *c)
-{
-    // a wavefront trip covers 64 rows (SELL) or 128 rows (banded, two rows per lane)
-    const int64_t trips = c->use_dia ? (c->nchunks + 1) / 2 : c->nchunks;
-    int64_t g = round_up((trips + 3) / 4, 8);
-    // 1024 workgroups (4 per CU, 16 waves per CU) already saturate HBM with the
-    // 5-9 independent loads a lane keeps in flight, and halve the partial sums
-    // every consumer has to re-add (measured: profiles/r01_sweep.log)
-    const int64_t cap = c->opt_grid > 0 ? round_up(c->opt_grid, 8) : 1024;
-    g = std::min<int64_t>(g, std::min<int64_t>(cap, kMaxGrid));
-    return (int)std::max<int64_t>(g, 8);
-}
-
 // Rows the streaming kernels touch: the SELL-padded local block.  Every pass
 // rewrites exactly these rows of every column it uses, so stale data beyond
 // them (left by a larger, earlier FSP) is never read.
 int64_t act_pairs(const kfsp_ctx *c) { return c->nchunks * (kChunk / 2); }
 
-// Streaming kernels: every consumer re-sums the producer's partials, so the
-// grid is kept at <= 1024 workgroups (4 per CU) with >= 4 pairs per lane; the
-// loops are unrolled so that this still keeps > 16 MB of loads in flight.
-int vec_grid(const kfsp_ctx *c)
-{
-    int64_t g = (act_pairs(c) + 4 * kBlock - 1) / (4 * kBlock);
-    const int64_t cap = c->opt_vgrid > 0 ? c->opt_vgrid : 1024;
-    g = std::min<int64_t>(g, std::min<int64_t>(cap, kMaxGrid));
-    return (int)std::max<int64_t>(g, 1);
-}
+int vec_grid(const kfsp_ctx *c) { return kfsp::vec_grid(act_pairs(c), c->opt_vgrid); }
 
 // the product reads the dictionary-coded image of the banded values (kernel format 9): unmasked, single rank, stored
 bool dia_code_on(const kfsp_ctx *c) { return c->use_dia && !c->use_box && c->dia_coded && !c->dia_masked && !c->use_comm; }
@@ -125,25 +46,10 @@ double *next_partial(kfsp_ctx *c)
     return p;
 }
 
-SellDev sell_of(const kfsp_ctx *c)
-{
-    return SellDev{c->nloc, c->nchunks, c->d_off.p, c->d_col.p, c->d_val.p, c->d_diag.p,
-                   c->d_dtab.p, c->d_dtlen.p, c->d_code.p, c->d_codeoff.p};
-}
-
 // generator part of the product kernel's arguments
 void set_matrix_args(const kfsp_ctx *c, SpmvArgs &a)
 {
-    a.A = sell_of(c);
-    a.D.nd = c->nd;
-    for (int d = 0; d < kMaxDiag; ++d) a.D.delta[d] = c->delta[d];
-    a.D.val = c->d_dia.p;
-    a.D.ld = c->dia_ld;
-    a.D.diag = c->d_diag.p;
-    a.D.nchunks = c->nchunks;
-    a.D.n = c->n;
-    a.D.gmask = c->dia_masked ? c->d_gmask.p : nullptr;
-    a.D.zero = c->d_zero.p;
+    generator_args(c, a.A, a.D);
     a.C.rec = c->d_dcode.p;
     a.C.dict = c->d_ddict.p;
     for (int d = 0; d <= kMaxDiag; ++d) a.C.doff[d] = c->dia_doff[d];
@@ -157,107 +63,6 @@ void set_matrix_args(const kfsp_ctx *c, SpmvArgs &a)
     a.partial2 = nullptr;
     a.trip_order = nullptr;
 }
-
-// ---- the two collectives of the data path, over RCCL or the loop-back transport ----
-constexpr int kLoopVals = 16;                              // values one all-reduce may carry (the 16 FIND_DROPTOL sums)
-constexpr int kLoopScratch = 64 * kLoopVals + kLoopVals;   // doubles: up to 64 ranks x 16 scalars (+ result)
-
-// buf[0..count) <- sum (or max) over ranks, in place, on stream st
-int comm_allreduce(kfsp_ctx *ctx, double *buf, int count, bool take_max, hipStream_t st)
-{
-    if (!ctx->loop) {
-        std::lock_guard<std::mutex> lk(ctx->comm_mu);
-        if (ctx->comm_aborted) return fail(ctx, 2999, "the communicator was aborted");
-        NCCL_TRY(ncclAllReduce(buf, buf, (size_t)count, ncclDouble, take_max ? ncclMax : ncclSum, ctx->comm, st));
-        return 0;
-    }
-    kfsp::LoopGroup *g = ctx->loop;
-    if (count > kLoopVals || g->n > 64) return fail(ctx, -1, "loop-back all-reduce: too many values");
-    HIP_TRY(hipStreamSynchronize(st));                  // this rank's contribution is in memory
-    g->slot[(size_t)ctx->rank] = buf;
-    if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");
-    double *h = ctx->h_loop;
-    for (int p = 0; p < g->n; ++p)
-        HIP_TRY(hipMemcpyAsync(h + kLoopVals * p, g->slot[(size_t)p], (size_t)count * sizeof(double), hipMemcpyDefault, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");   // everyone has read
-    double *r = h + kLoopVals * g->n;
-    for (int i = 0; i < count; ++i) {
-        double a = h[i];
-        for (int p = 1; p < g->n; ++p) a = take_max ? std::max(a, h[kLoopVals * p + i]) : a + h[kLoopVals * p + i];   // rank order: same bits on every rank
-        r[i] = a;
-    }
-    HIP_TRY(hipMemcpyAsync(buf, r, (size_t)count * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-// recv[p*count .. (p+1)*count) <- send of rank p, on stream st
-int comm_allgather(kfsp_ctx *ctx, const double *send, double *recv, size_t count, hipStream_t st)
-{
-    if (!ctx->loop) {
-        std::lock_guard<std::mutex> lk(ctx->comm_mu);
-        if (ctx->comm_aborted) return fail(ctx, 2999, "the communicator was aborted");
-        NCCL_TRY(ncclAllGather(send, recv, count, ncclDouble, ctx->comm, st));
-        return 0;
-    }
-    kfsp::LoopGroup *g = ctx->loop;
-    HIP_TRY(hipStreamSynchronize(st));
-    g->slot[(size_t)ctx->rank] = send;
-    if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");
-    for (int p = 0; p < g->n; ++p)
-        HIP_TRY(hipMemcpyAsync(recv + (size_t)p * count, g->slot[(size_t)p], count * sizeof(double), hipMemcpyDefault, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");   // nobody reuses its send buffer before all have copied
-    return 0;
-}
-
-// the same for raw bytes (flags)
-int comm_allgather_bytes(kfsp_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st)
-{
-    if (!ctx->loop) {
-        std::lock_guard<std::mutex> lk(ctx->comm_mu);
-        if (ctx->comm_aborted) return fail(ctx, 2999, "the communicator was aborted");
-        NCCL_TRY(ncclAllGather(send, recv, bytes, ncclUint8, ctx->comm, st));
-        return 0;
-    }
-    kfsp::LoopGroup *g = ctx->loop;
-    HIP_TRY(hipStreamSynchronize(st));
-    g->slot[(size_t)ctx->rank] = send;
-    if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");
-    for (int p = 0; p < g->n; ++p)
-        HIP_TRY(hipMemcpyAsync(static_cast<char *>(recv) + (size_t)p * bytes, g->slot[(size_t)p], bytes, hipMemcpyDefault, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");
-    return 0;
-}
-
-}  // namespace
-
-namespace kfsp {
-// the collectives for the translation units of the expansion step (the walk's records of a partitioned expansion)
-int comm_gather_doubles(kfsp_ctx *ctx, const double *send, double *recv, size_t count, hipStream_t st) { return comm_allgather(ctx, send, recv, count, st); }
-int comm_gather_bytes(kfsp_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st) { return comm_allgather_bytes(ctx, send, recv, bytes, st); }
-
-// Called from ANOTHER thread than the one that drives ctx (the watchdog of a group context, kfsp_group.cpp) when a peer
-// failed or a deadline expired: the rank may sit in hipStreamSynchronize behind a collective its peers never entered.
-// ncclCommAbort makes the collective's kernel give up; the loop-back transport releases its barriers.  The rank's
-// pending call then returns an error, later collectives return 2999.  comm_mu keeps the abort from running while
-// the driving thread is in the middle of enqueuing on the same communicator.
-void comm_abort(kfsp_ctx *ctx)
-{
-    if (ctx->loop) {
-        ctx->loop->abort();
-        return;
-    }
-    std::lock_guard<std::mutex> lk(ctx->comm_mu);
-    if (ctx->comm && !ctx->comm_aborted) (void)ncclCommAbort(ctx->comm);
-    ctx->comm = nullptr;
-    ctx->comm_aborted = true;
-}
-}  // namespace kfsp
-
-namespace {
 
 // Make block partials a scalar every rank agrees on.
 int publish(kfsp_ctx *ctx, Pending local, Pending *out)
@@ -274,16 +79,6 @@ int publish(kfsp_ctx *ctx, Pending local, Pending *out)
     return 0;
 }
 
-int gather_source(kfsp_ctx *ctx, const double *src_local, const double **xg);
-int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st);
-
-int trips_grid(int64_t trips, int64_t cap)
-{
-    int64_t g = round_up((trips + 3) / 4, 8);
-    g = std::min<int64_t>(g, cap);
-    return (int)std::max<int64_t>(g, 8);
-}
-
 // One generator product y = (s) A x from the local source column `src` (or from
 // a full global vector when src_is_global).  `a` carries everything except the
 // source pointer, the trip range and the partial buffers.  With a banded
@@ -298,14 +93,14 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     ++ctx->prod_count;
     const bool dia = ctx->use_dia && !force_sell;
     const bool nt = use_nt(ctx);
-    const int64_t trips = dia ? (ctx->nchunks + 1) / 2 : ctx->nchunks;
-    int64_t cap = ctx->opt_grid > 0 ? round_up(ctx->opt_grid, 8) : 1024;
-    if (ctx->use_box && dia && ctx->opt_grid <= 0) {
+    const int64_t trips = product_trips(ctx->nchunks, dia);
+    int64_t dflt_cap = 1024;   // the grid without option grid_blocks (product_grid)
+    if (ctx->use_box && dia) {
         // every workgroup of a matrix-free product copies the table image into its LDS first: no more
         // workgroups than are resident at once (160 KB of LDS per CU), or the later ones pay that copy
         // again for fewer rows each (toggle 1000 x 1000, 64 KB image: 8.3 us with 512, 12.1 us with 1024)
         const int64_t per_cu = std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)(ctx->box_lds_bytes + 512));
-        cap = std::min<int64_t>(cap, 256 * per_cu);
+        dflt_cap = std::min<int64_t>(dflt_cap, 256 * per_cu);
     }
     double *P1 = mode != 0 ? next_partial(ctx) : nullptr;
     double *P2 = mode == 3 ? next_partial(ctx) : nullptr;
@@ -340,7 +135,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         a.trip_split = INT64_MAX;
         a.trip_jump = 0;
         a.trip_order = (ctx->trip_order_n == trips && !force_sell) ? ctx->d_trip_order.p : nullptr;
-        const int g = trips_grid(trips, cap);
+        const int g = product_grid(trips, ctx->opt_grid, dflt_cap);
         if (fmt == 4 && ctx->box_slab && ctx->opt_box_pencil == 2 && !ctx->use_comm && ctx->opt_box_lds == 0) {
             // format 8: one workgroup per 128 rows x W lines of the second-slowest species, walking the planes in step
             const int64_t total = ctx->slab_lo_trips * ctx->slab_groups;
@@ -359,7 +154,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
             // format 7: one wavefront per pencil of 128 rows x all planes of the slowest species
             // (3 workgroups per CU: measured best on the 22^6 box and its slab - 768: 798 / 77.7 us, 512: 866 / 84, 1024: 936 / 86,
             // 2048: 816 / 81; anything that is not a multiple of 256 leaves some CUs with one more - profiles/r04_pencil_grid_sweep.txt)
-            const int gp = trips_grid(ctx->pencil_trips, ctx->opt_grid > 0 ? cap : 768);
+            const int gp = product_grid(ctx->pencil_trips, ctx->opt_grid, 768);
             launch_spmv_pencil(mode, gp, a, st, ctx->box_lds_bytes, ctx->pencil_plane_rows, ctx->pencil_planes, ctx->pencil_trips,
                                ctx->pencil_order_n == ctx->pencil_trips ? ctx->d_pencil_order.p : nullptr, ctx->pencil_simple);
             if (p1) *p1 = Pending{P1, gp};
@@ -384,9 +179,8 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     HIP_TRY(hipEventRecord(ctx->ev_halo, ctx->comm_stream));
     a.xg = src - ctx->row0;
     int used = 0;
-    auto launch_range = [&](int64_t b, int64_t e, int64_t split, int64_t jump, int64_t gcap) {
+    auto launch_range = [&](int64_t b, int64_t e, int64_t split, int64_t jump, int g) {
         if (e <= b) return;
-        const int g = trips_grid(e - b, gcap);
         a.partial = P1 ? P1 + used : nullptr;
         a.partial2 = P2 ? P2 + used : nullptr;
         a.trip_begin = b;
@@ -396,11 +190,12 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         launch_spmv(mode, g, a, nt, fmt, st, ctx->box_lds_bytes);
         used += g;
     };
-    launch_range(lo, hi, INT64_MAX, 0, std::min<int64_t>(cap, kMaxGrid - 512));   // interior: no halo row is read
+    // interior: no halo row is read (the boundary launch keeps 512 of the slot's kMaxGrid partials)
+    launch_range(lo, hi, INT64_MAX, 0, std::min(product_grid(hi - lo, ctx->opt_grid, dflt_cap), kMaxGrid - 512));
     HIP_TRY(hipStreamWaitEvent(st, ctx->ev_halo, 0));
     // one launch for both boundary ranges: linear trips [0, lo) are themselves,
     // [lo, lo + trips - hi) stand for [hi, trips)
-    launch_range(0, lo + (trips - hi), lo, hi - lo, 512);
+    launch_range(0, lo + (trips - hi), lo, hi - lo, product_grid(lo + (trips - hi), 0, 512));
     if (p1) *p1 = Pending{P1, used};
     if (p2) *p2 = Pending{P2, used};
     return 0;
@@ -422,120 +217,6 @@ int publish_n(kfsp_ctx *ctx, const Pending *local, int k, Pending *out)
     return 0;
 }
 
-int resize(kfsp_ctx *ctx, int64_t n);
-
-// Banded generator: only the `halo` boundary rows of the two neighbours are ever
-// read.  Every rank contributes [its first halo rows | its last halo rows]; one
-// all-gather of these strips, then the two strips this rank needs are dropped
-// into the margins of the source column itself.  All on stream st.
-int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st)
-{
-    const int64_t H = ctx->halo, L = ctx->L;
-    double *col = const_cast<double *>(src_local);
-    if (ctx->opt_halo_p2p != 0) {
-        // Neighbours only, and straight between the columns: a rank's first H rows go into the margin
-        // behind the previous rank's block, its last H rows into the margin in front of the next rank's.
-        // No staging copies, no strips of ranks that are not neighbours (an all-gather moves
-        // nranks * 2H doubles to every rank for the 2H it needs).
-        const bool up = ctx->rank > 0, down = ctx->rank + 1 < ctx->nranks;
-        if (!ctx->loop) {
-            std::lock_guard<std::mutex> lk(ctx->comm_mu);
-            if (ctx->comm_aborted) return fail(ctx, 2999, "the communicator was aborted");
-            NCCL_TRY(ncclGroupStart());
-            if (up) {
-                NCCL_TRY(ncclSend(src_local, (size_t)H, ncclDouble, ctx->rank - 1, ctx->comm, st));
-                NCCL_TRY(ncclRecv(col - H, (size_t)H, ncclDouble, ctx->rank - 1, ctx->comm, st));
-            }
-            if (down) {
-                NCCL_TRY(ncclSend(src_local + (L - H), (size_t)H, ncclDouble, ctx->rank + 1, ctx->comm, st));
-                NCCL_TRY(ncclRecv(col + L, (size_t)H, ncclDouble, ctx->rank + 1, ctx->comm, st));
-            }
-            NCCL_TRY(ncclGroupEnd());
-            return 0;
-        }
-        kfsp::LoopGroup *g = ctx->loop;
-        HIP_TRY(hipStreamSynchronize(st));
-        g->slot[(size_t)ctx->rank] = src_local;
-        if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");
-        if (up)      // the previous rank's LAST rows sit just below row 0
-            HIP_TRY(hipMemcpyAsync(col - H, static_cast<const double *>(g->slot[(size_t)ctx->rank - 1]) + (L - H),
-                                   (size_t)H * sizeof(double), hipMemcpyDefault, st));
-        if (down)    // the next rank's FIRST rows follow row L-1
-            HIP_TRY(hipMemcpyAsync(col + L, static_cast<const double *>(g->slot[(size_t)ctx->rank + 1]),
-                                   (size_t)H * sizeof(double), hipMemcpyDefault, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!g->barrier()) return fail(ctx, 2999, "loop-back barrier timed out");   // nobody moves on before all have copied
-        return 0;
-    }
-    double *send = ctx->d_strip.p, *recv = ctx->d_strip.p + 2 * H;
-    HIP_TRY(hipMemcpyAsync(send, src_local, (size_t)H * sizeof(double), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(send + H, src_local + (L - H), (size_t)H * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (int rc = comm_allgather(ctx, send, recv, (size_t)(2 * H), st)) return rc;
-    if (ctx->rank > 0)                 // the previous rank's LAST rows sit just below row 0
-        HIP_TRY(hipMemcpyAsync(col - H, recv + (size_t)(ctx->rank - 1) * 2 * H + H, (size_t)H * sizeof(double),
-                               hipMemcpyDeviceToDevice, st));
-    if (ctx->rank + 1 < ctx->nranks)   // the next rank's FIRST rows follow row L-1
-        HIP_TRY(hipMemcpyAsync(col + L, recv + (size_t)(ctx->rank + 1) * 2 * H, (size_t)H * sizeof(double),
-                               hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-// The source column must be visible in full on every rank before a product.
-int gather_source(kfsp_ctx *ctx, const double *src_local, const double **xg)
-{
-    if (!ctx->use_comm) {
-        *xg = src_local - ctx->row0;       // row0 == 0 here
-        return 0;
-    }
-    if (ctx->use_halo) {
-        if (int rc = exchange_strips(ctx, src_local, ctx->stream)) return rc;
-        *xg = src_local - ctx->row0;       // global index g lives at src_local[g - row0]
-        return 0;
-    }
-    if (int rc = comm_allgather(ctx, src_local, ctx->d_xg.p, (size_t)ctx->L, ctx->stream)) return rc;
-    *xg = ctx->d_xg.p;
-    return 0;
-}
-
-// After a generator was set: agree across ranks on the exchange mode.  Halo
-// exchange needs every rank to hold a banded block whose reach max|delta| does
-// not exceed one block length (only the two neighbours are involved then).
-int setup_exchange(kfsp_ctx *ctx)
-{
-    ctx->use_halo = false;
-    ctx->halo = 0;
-    if (!ctx->use_comm) return 0;
-    int64_t reach = 0;
-    for (int d = 0; d < ctx->nd; ++d) reach = std::max<int64_t>(reach, std::llabs((long long)ctx->delta[d]));
-    // a SELL generator with a bounded reach max |col - row| (known from its build; small under the internal
-    // lexicographic state order) reads only boundary rows of its neighbours too
-    const bool sell_ok = !ctx->use_dia && ctx->have_sell && ctx->sell_reach >= 0 && ctx->opt_halo_sell != 0;
-    if (sell_ok) reach = ctx->sell_reach;
-    // ranks without rows take part with neutral values
-    const bool ok_local = ctx->opt_halo != 0 && (ctx->nloc == 0 || ctx->use_dia || sell_ok);
-    double h[2] = {ok_local ? 0.0 : 1.0, (double)reach};          // max over ranks of (not ok, reach)
-    double *st = ctx->d_stage.p;
-    HIP_TRY(hipMemcpyAsync(st, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = comm_allreduce(ctx, st, 2, true, ctx->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const int64_t H = round_up(std::max<int64_t>((int64_t)h[1], 1), 8);
-    if (h[0] != 0.0 || H > ctx->L) return 0;                      // someone is not banded, or reach > one block
-    ctx->halo = H;
-    if (H + 2 * kChunk > ctx->margin) {
-        // re-lay the basis with room for the strips (its contents are rebuilt by
-        // the next begin_step anyway)
-        // + 128: the banded kernel works on 128-row groups, whose padded rows read up
-        // to one group beyond the block end
-        ctx->margin = round_up(H + H / 4 + 2 * kChunk, 64);
-        ctx->relayout = true;
-        if (int rc = resize(ctx, ctx->n)) return rc;
-    }
-    HIP_TRY(ctx->d_strip.reserve((size_t)(2 * H) * (size_t)(ctx->nranks + 1), true));
-    ctx->use_halo = true;
-    return 0;
-}
-
 // (Re)size everything that depends on the number of states.
 // M_MAX + 2 basis columns and one scratch column (option m_max caps it: at 10^8 states 105 columns are 90 GB)
 // num_cols: the columns d_V HAS (option m_max only takes effect when the next generator re-lays the basis, so every
@@ -547,7 +228,10 @@ inline int64_t mmax_now(const kfsp_ctx *c) { return c->v_mmax ? std::min(c->v_mm
 // column j (0-based) of the basis: `margin` halo rows sit on either side of it
 inline double *vcol(const kfsp_ctx *c, int j) { return c->d_V.p + (size_t)j * (size_t)c->ldv + (size_t)c->margin; }
 
-int resize(kfsp_ctx *ctx, int64_t n)
+}  // namespace
+
+// (kfsp_comm.cpp re-lays the basis through it when the halo margins grow)
+int kfsp::resize(kfsp_ctx *ctx, int64_t n)
 {
     ctx->n = n;
     ctx->trip_order_n = 0;             // a trip order belongs to one generator
@@ -582,6 +266,8 @@ int resize(kfsp_ctx *ctx, int64_t n)
     if (xg > ctx->d_xg.cap) HIP_TRY(ctx->d_xg.reserve(xg + xg / 2, true));
     return 0;
 }
+
+namespace {
 
 // Upload gather rows given as per-row counts + a fill callback.
 struct HostSell {
@@ -820,9 +506,6 @@ int init_context(kfsp_ctx *ctx)
     return 0;
 }
 
-}  // namespace
-
-namespace {
 // The order in which a product over a lexicographic box takes its 128-row trips when the box is too large for the caches
 // (option "box_tile": -1 auto, 0 never, 1 always): rows are cut below the slowest stride that is still at most 16 K rows
 // (cut), r = hi * S_cut + lo; blocks of B = 1024 rows of lo; per block ALL lines hi back to back.  A row's +-S neighbours
@@ -954,101 +637,6 @@ int kfsp_destroy(kfsp_ctx *ctx)
 }
 
 const char *kfsp_last_error(const kfsp_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
-
-int kfsp_comm_unique_id(void *id_bytes)
-{
-    if (!id_bytes) return -1;
-    static_assert(sizeof(ncclUniqueId) == KFSP_UNIQUE_ID_BYTES, "ncclUniqueId size");
-    ncclUniqueId id;
-    ncclResult_t r = ncclGetUniqueId(&id);
-    if (r != ncclSuccess) return 2000 + (int)r;
-    std::memcpy(id_bytes, &id, sizeof(id));
-    return 0;
-}
-
-int kfsp_comm_init(kfsp_ctx *ctx, int nranks, int rank, const void *id_bytes)
-{
-    if (!ctx) return -1;
-    if (nranks < 1) return fail(ctx, -2, "nranks < 1");
-    if (rank < 0 || rank >= nranks) return fail(ctx, -3, "rank out of range");
-    if (nranks > 1 && !id_bytes) return fail(ctx, -4, "null unique id");
-    if (ctx->group) return fail(ctx, -9, "a group context makes its own communicator");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->comm) {
-        // (abort, not destroy: the usual reason to come here twice is a communicator that returned an
-        // error on some rank, and destroying one of those can wait for ever)
-        (void)ncclCommAbort(ctx->comm);
-        ctx->comm = nullptr;
-    }
-    ctx->loop = nullptr;
-    ctx->comm_aborted = false;
-    ctx->nranks = nranks;
-    ctx->rank = rank;
-    // a unique id with nranks == 1 still creates a (one-rank) communicator, so the
-    // collective code path can be exercised on a single GPU
-    ctx->use_comm = false;
-    if (id_bytes) {
-        ncclUniqueId id;
-        std::memcpy(&id, id_bytes, sizeof(id));
-        NCCL_TRY(ncclCommInitRank(&ctx->comm, nranks, id, rank));
-        ctx->use_comm = true;
-        if (!ctx->comm_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_src, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_halo, hipEventDisableTiming));
-        }
-    }
-    ctx->relayout = true;   // new margins / block length: re-lay the basis on the next matrix
-    ctx->use_halo = false;
-    return 0;
-}
-
-int kfsp_loopback_create(int nranks, void **group)
-{
-    if (nranks < 1 || nranks > 64) return -1;
-    if (!group) return -2;
-    kfsp::LoopGroup *g = new (std::nothrow) kfsp::LoopGroup;
-    if (!g) return 4001;
-    g->n = nranks;
-    g->slot.assign((size_t)nranks, nullptr);
-    *group = g;
-    return 0;
-}
-
-int kfsp_loopback_destroy(void *group)
-{
-    delete static_cast<kfsp::LoopGroup *>(group);
-    return 0;
-}
-
-int kfsp_comm_init_loopback(kfsp_ctx *ctx, void *group, int rank)
-{
-    if (!ctx) return -1;
-    if (!group) return fail(ctx, -2, "null group");
-    kfsp::LoopGroup *g = static_cast<kfsp::LoopGroup *>(group);
-    if (rank < 0 || rank >= g->n) return fail(ctx, -3, "rank out of range");
-    if (ctx->group) return fail(ctx, -9, "a group context makes its own communicator");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->comm) {
-        (void)ncclCommAbort(ctx->comm);   // as kfsp_comm_init: destroying a failed communicator can wait for ever
-        ctx->comm = nullptr;
-    }
-    ctx->loop = g;
-    ctx->comm_aborted = false;
-    ctx->nranks = g->n;
-    ctx->rank = rank;
-    ctx->use_comm = true;
-    if (!ctx->h_loop)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_loop), (size_t)(kLoopScratch + 8) * sizeof(double), hipHostMallocDefault));
-    if (!ctx->comm_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_src, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_halo, hipEventDisableTiming));
-    }
-    ctx->relayout = true;   // new margins / block length: re-lay the basis on the next matrix
-    ctx->use_halo = false;
-    return 0;
-}
 
 int kfsp_partition(int64_t n, int nranks, int rank, int64_t *row0, int64_t *nrows, int64_t *block_len)
 {
@@ -1772,10 +1360,7 @@ int kfsp_arnoldi(kfsp_ctx *ctx, int m, int jold, int qiop, double break_tol, dou
                        (ctx->use_dia || ctx->have_sell) && !ctx->use_box;
     if (small) {
         SmallArnoldiArgs sa;
-        SpmvArgs tmp;
-        set_matrix_args(ctx, tmp);
-        sa.A = tmp.A;
-        sa.D = tmp.D;
+        generator_args(ctx, sa.A, sa.D);
         sa.V = V;
         sa.ldv = ldv;
         sa.nact = ctx->nchunks * kChunk;

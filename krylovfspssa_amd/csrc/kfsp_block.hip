@@ -31,7 +31,7 @@
 
 #include "kfsp_block_dev.h"
 #include "kfsp_box_dev.h"
-#include "kfsp_ctx.h"
+#include "kfsp_host.h"
 
 #include <algorithm>
 #include <chrono>
@@ -566,32 +566,6 @@ __global__ __launch_bounds__(kSmallBlock) void k_bcombine_small(int nact, int kp
 }
 
 // ---- host side
-int fail(kfsp_ctx *c, int code, const char *what)
-{
-    c->err = what;
-    return code;
-}
-
-int hip_fail(kfsp_ctx *c, hipError_t e, const char *where)
-{
-    c->err = std::string(where) + ": " + hipGetErrorString(e);
-    return 1000 + (int)e;
-}
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return hip_fail(ctx, e_, #expr); \
-    } while (0)
-
-struct PhaseTimer {
-    kfsp_ctx *c;
-    int phase;
-    std::chrono::steady_clock::time_point t0;
-    PhaseTimer(kfsp_ctx *c_, int p) : c(c_), phase(p), t0(std::chrono::steady_clock::now()) {}
-    ~PhaseTimer() { c->t_ms[phase] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
 const char *const kAdjFormMsg = "several vectors at once, option adjoint: the generator is resident in no form the transposed product reads";
 
 const char *const kBoxReachMsg = "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
@@ -600,7 +574,7 @@ const char *const kBoxReachMsg = "several vectors at once: the entries of this m
 int kp_of(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)); }
 
 int spmm_fmt(const kfsp_ctx *c) { return c->use_dia ? (c->dia_masked ? 2 : 1) : (c->sell_coded ? 5 : 0); }
-int64_t spmm_trips(const kfsp_ctx *c) { return c->use_dia ? (c->nchunks + 1) / 2 : c->nchunks; }
+int64_t spmm_trips(const kfsp_ctx *c) { return product_trips(c->nchunks, c->use_dia); }
 // rows a product writes, and rows of a block column (margins included)
 int64_t rows_act(const kfsp_ctx *c) { return spmm_trips(c) * (c->use_dia ? 128 : 64); }
 int64_t col_rows(const kfsp_ctx *c) { return rows_act(c) + 2 * kMargin; }
@@ -610,13 +584,7 @@ double *bcol(double *base, const kfsp_ctx *c, int kp, int j) { return base + (si
 // 16-byte pairs the streaming kernels cover: the rows of the SELL-padded block, like act_pairs
 int64_t red_pairs(const kfsp_ctx *c, int kp) { return c->nchunks * kChunk * (int64_t)kp / 2; }
 
-int spmm_grid(const kfsp_ctx *c)
-{
-    const int64_t t = spmm_trips(c);
-    int64_t g = round_up((t + 3) / 4, 8);
-    g = std::min<int64_t>(g, c->opt_grid > 0 ? std::min<int64_t>(round_up(c->opt_grid, 8), kMaxGrid) : 1024);
-    return (int)std::max<int64_t>(g, 8);
-}
+int spmm_grid(const kfsp_ctx *c) { return product_grid(spmm_trips(c), c->opt_grid, 1024); }
 
 // The small path is taken where kfsp_arnoldi (qiop = 2) takes k_arnoldi_small on this context (kfsp_api.cpp), short of
 // coded SELL columns: those stay on the multi-launch path.  So does every backward pass (option adjoint): k_barnoldi_small
@@ -627,12 +595,8 @@ bool small_path(const kfsp_ctx *c)
            c->nchunks * kChunk <= kSmallRows && (c->use_dia || (c->have_sell && !c->sell_coded)) && c->slots < (1LL << 31);
 }
 
-int flat_grid(const kfsp_ctx *c, int kp)
-{
-    int64_t g = (red_pairs(c, kp) + 4 * kBlock - 1) / (4 * kBlock);
-    g = std::min<int64_t>(g, c->opt_vgrid > 0 ? std::min<int64_t>(c->opt_vgrid, kMaxGrid) : 1024);
-    return (int)std::max<int64_t>(g, 1);
-}
+// grid of the streaming kernels over a block column
+int flat_grid(const kfsp_ctx *c, int kp) { return vec_grid(red_pairs(c, kp), c->opt_vgrid); }
 
 template <int KP>
 void launch_spmm_kp(int fmt, bool dots, int g, const SpmmArgs &a, hipStream_t st)
@@ -681,43 +645,32 @@ bool box_block_reach_ok(const kfsp_ctx *c, int kp)
     return (back + fwd + 128) * 8 * (int64_t)kp < (1LL << 32);
 }
 
-// The matrix-free block product.  Every workgroup copies the table image first, so no more workgroups are launched
-// than are resident at once (the rule of the single-vector product, run_product): the runtime says how many fit.
-int spmm_box(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
+// Launch geometry of the matrix-free block product, forward and transposed: the dynamic LDS (*lds), the table pointers
+// of `a`, and the grid (returned).  Every workgroup copies the table image first, so no more workgroups are launched than
+// are resident at once (the rule of the single-vector product, run_product): the runtime says how many fit - resident(lds),
+// asked once per width and variant and kept in `cache` (blk_box_occ or blk_box_t_occ).
+template <class Resident>
+int box_block_geometry(const kfsp_ctx *ctx, int kp, bool dots, int (&cache)[4][2], Resident resident, SpmmArgs &a, size_t *lds)
 {
-    const SpmmBoxFn fn = spmm_box_fn(kp, ctx->box.pad, dots);
-    const size_t lds = std::max<size_t>(ctx->box_lds_bytes, (size_t)4 * kp * sizeof(double));
-    int &occ = ctx->blk_box_occ[kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3))][dots ? 1 : 0];
-    if (occ == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kBlock, lds) != hipSuccess) nb = 1;
-        occ = std::max(nb, 1);
-    }
-    int64_t g = round_up((a.trips + 3) / 4, 8);
-    g = std::min<int64_t>(g, ctx->opt_grid > 0 ? std::min<int64_t>(round_up(ctx->opt_grid, 8), kMaxGrid)
-                                               : std::min<int64_t>(1024, (int64_t)256 * occ));
-    g = std::max<int64_t>(g, 8);
+    *lds = std::max<size_t>(ctx->box_lds_bytes, (size_t)4 * kp * sizeof(double));
+    int &occ = cache[kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3))][dots ? 1 : 0];
+    if (occ == 0) occ = std::max(resident(*lds), 1);
     a.box_tab = ctx->d_box.p;
     a.box_ntab = ctx->box.ntab;
     a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
-    hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kBlock), lds, ctx->stream, a);
-    return (int)g;
+    return product_grid(a.trips, ctx->opt_grid, std::min<int64_t>(1024, (int64_t)256 * occ));
 }
 
-// the generator's images as the kernels take them
-void matrix_args(const kfsp_ctx *ctx, SpmmArgs &a)
+int spmm_box(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
 {
-    a.A = SellDev{ctx->nloc, ctx->nchunks, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, ctx->d_diag.p,
-                  ctx->d_dtab.p, ctx->d_dtlen.p, ctx->d_code.p, ctx->d_codeoff.p};
-    a.D.nd = ctx->nd;
-    for (int d = 0; d < kMaxDiag; ++d) a.D.delta[d] = ctx->delta[d];
-    a.D.val = ctx->d_dia.p;
-    a.D.ld = ctx->dia_ld;
-    a.D.diag = ctx->d_diag.p;
-    a.D.nchunks = ctx->nchunks;
-    a.D.n = ctx->n;
-    a.D.gmask = ctx->dia_masked ? ctx->d_gmask.p : nullptr;
-    a.D.zero = ctx->d_zero.p;
+    const SpmmBoxFn fn = spmm_box_fn(kp, ctx->box.pad, dots);
+    size_t lds = 0;
+    const int g = box_block_geometry(ctx, kp, dots, ctx->blk_box_occ, [&](size_t bytes) {
+        int nb = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kBlock, bytes) == hipSuccess ? nb : 1;
+    }, a, &lds);
+    hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kBlock), lds, ctx->stream, a);
+    return g;
 }
 
 // The reference arrays in the order the device keeps its vectors: the relabelled copies under the internal state order.
@@ -739,18 +692,11 @@ int spmm_adjoint(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
     if (ctx->use_box) {
         BoxAdjDev b;
         if (!box_adj_build(ctx->box, b)) return -1;
-        const size_t lds = std::max<size_t>(ctx->box_lds_bytes, (size_t)4 * kp * sizeof(double));
-        int &occ = ctx->blk_box_t_occ[kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3))][dots ? 1 : 0];
-        if (occ == 0) occ = spmm_box_t_resident(kp, ctx->box.pad, dots, lds);
-        int64_t g = round_up((a.trips + 3) / 4, 8);
-        g = std::min<int64_t>(g, ctx->opt_grid > 0 ? std::min<int64_t>(round_up(ctx->opt_grid, 8), kMaxGrid)
-                                                   : std::min<int64_t>(1024, (int64_t)256 * occ));
-        g = std::max<int64_t>(g, 8);
-        a.box_tab = ctx->d_box.p;
-        a.box_ntab = ctx->box.ntab;
-        a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
-        launch_spmm_box_t(kp, ctx->box.pad, dots, (int)g, lds, a, b, ctx->stream);
-        return (int)g;
+        size_t lds = 0;
+        const int g = box_block_geometry(ctx, kp, dots, ctx->blk_box_t_occ,
+                                         [&](size_t bytes) { return spmm_box_t_resident(kp, ctx->box.pad, dots, bytes); }, a, &lds);
+        launch_spmm_box_t(kp, ctx->box.pad, dots, g, lds, a, b, ctx->stream);
+        return g;
     }
     const int g = spmm_grid(ctx);
     if (ctx->use_dia) {
@@ -767,7 +713,7 @@ int spmm_adjoint(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
 int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
 {
     SpmmArgs a;
-    matrix_args(ctx, a);
+    generator_args(ctx, a.A, a.D);
     a.X = X;
     a.Y = Y;
     a.ua = ua;
@@ -845,17 +791,9 @@ int download_block(kfsp_ctx *ctx, int k, int kp, const double *col0, int64_t ld,
     return 0;
 }
 
+// the block path's fence at the C boundary
 template <class F>
-int guarded(kfsp_ctx *ctx, F &&body)
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, 4001, "out of host memory");
-    } catch (...) {
-        return fail(ctx, 4000, "exception inside the block path");
-    }
-}
+int guarded(kfsp_ctx *ctx, F &&body) { return no_throw(ctx, body, "exception inside the block path"); }
 
 }  // namespace
 
@@ -947,10 +885,7 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     ctx->blk_info[3] = small ? 1 : 4 * m + 3;
     if (small) {
         SmallArnoldiArgs sa;
-        SpmmArgs tmp;
-        matrix_args(ctx, tmp);
-        sa.A = tmp.A;
-        sa.D = tmp.D;
+        generator_args(ctx, sa.A, sa.D);
         sa.V = nullptr;
         sa.ldv = (int64_t)col_len(ctx, kp);
         sa.nact = ctx->nchunks * kChunk;

@@ -11,7 +11,7 @@
 // block-wide exclusive scan, scatter with per-row slot tickets, and a per-row
 // sort by source index that makes the layout deterministic and identical to the
 // order in which FMATVEC accumulates (KrylovSolver.f90:598-604).
-#include "kfsp_ctx.h"
+#include "kfsp_host.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -492,15 +492,6 @@ __global__ __launch_bounds__(kBlock) void k_gather_i32(int64_t n, const int32_t 
 
 }  // namespace
 
-#define HIP_TRY_B(expr)                                                                    \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return 1000 + (int)e_;                                                         \
-        }                                                                                  \
-    } while (0)
-
 int build_from_ell_device(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, const int32_t *adj,
                           const double *offdiag, const double *diag, int64_t keep)
 {
@@ -516,15 +507,15 @@ int build_from_ell_device(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, cons
     // columns of the appended states travel; the links (ADJ) of old states do change and travel in full.
     if (keep > ctx->ell_cols || keep > n || ld != ctx->ell_ld) keep = 0;
     ctx->ell_cols = 0;
-    HIP_TRY_B(ctx->d_ell_adj.reserve(nent, false));
-    HIP_TRY_B(ctx->d_ell_off.reserve_keep(nent, (size_t)keep * (size_t)ld, st));
-    HIP_TRY_B(ctx->d_ell_diag.reserve_keep((size_t)n, (size_t)keep, st));
-    HIP_TRY_B(hipMemcpyAsync(ctx->d_ell_adj.p, adj, nent * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx->d_ell_adj.reserve(nent, false));
+    HIP_TRY(ctx->d_ell_off.reserve_keep(nent, (size_t)keep * (size_t)ld, st));
+    HIP_TRY(ctx->d_ell_diag.reserve_keep((size_t)n, (size_t)keep, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_ell_adj.p, adj, nent * sizeof(int32_t), hipMemcpyHostToDevice, st));
     const size_t k0 = (size_t)keep * (size_t)ld;
     if (nent > k0)
-        HIP_TRY_B(hipMemcpyAsync(ctx->d_ell_off.p + k0, offdiag + k0, (nent - k0) * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_ell_off.p + k0, offdiag + k0, (nent - k0) * sizeof(double), hipMemcpyHostToDevice, st));
     if (n > keep)
-        HIP_TRY_B(hipMemcpyAsync(ctx->d_ell_diag.p + keep, diag + keep, (size_t)(n - keep) * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_ell_diag.p + keep, diag + keep, (size_t)(n - keep) * sizeof(double), hipMemcpyHostToDevice, st));
     ctx->ell_cols = n;
     ctx->ell_ld = ld;
     ctx->ell_bw = bw;
@@ -553,9 +544,9 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
     if (ctx->perm_on) {
         // columns renumbered and reordered to the internal state order; the
         // transpose below then never knows about the caller's order
-        HIP_TRY_B(ctx->d_ell_adj2.reserve(nent, false));
-        HIP_TRY_B(ctx->d_ell_off2.reserve(nent, false));
-        HIP_TRY_B(ctx->d_ell_diag2.reserve((size_t)n, false));
+        HIP_TRY(ctx->d_ell_adj2.reserve(nent, false));
+        HIP_TRY(ctx->d_ell_off2.reserve(nent, false));
+        HIP_TRY(ctx->d_ell_diag2.reserve((size_t)n, false));
         hipLaunchKernelGGL(k_ell_relabel, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
                            (int)bw, (int)ld, ctx->d_perm.p, ctx->d_iperm.p, ctx->d_ell_adj.p, ctx->d_ell_off.p,
                            ctx->d_ell_diag.p, ctx->d_ell_adj2.p, ctx->d_ell_off2.p, ctx->d_ell_diag2.p);
@@ -564,9 +555,9 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         ell_diag = ctx->d_ell_diag2.p;
     }
 
-    HIP_TRY_B(ctx->d_cnt.reserve((size_t)std::max<int64_t>(nact, 64), false));
-    HIP_TRY_B(ctx->d_scan.reserve(sizeof(ScanOut), false));
-    HIP_TRY_B(hipMemsetAsync(ctx->d_cnt.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
+    HIP_TRY(ctx->d_cnt.reserve((size_t)std::max<int64_t>(nact, 64), false));
+    HIP_TRY(ctx->d_scan.reserve(sizeof(ScanOut), false));
+    HIP_TRY(hipMemsetAsync(ctx->d_cnt.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
     // (the initial statistics come from the pinned block: a copy from pageable memory makes the host wait for everything
     // enqueued before it - one more hidden synchronisation per rebuild)
     static_assert(sizeof(ScanOut) <= 2048, "h_build layout");
@@ -581,7 +572,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         init.bad = 0;
         ctx->h_build_ready = true;
     }
-    HIP_TRY_B(hipMemcpyAsync(ctx->d_scan.p, &init, sizeof(init), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_scan.p, &init, sizeof(init), hipMemcpyHostToDevice, st));
     ScanOut *dscan = reinterpret_cast<ScanOut *>(ctx->d_scan.p);
     const int gsrc = (int)((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_ell_scan, dim3(std::min(gsrc, 1024)), dim3(kBlock), 0, st, (int64_t)n, (int)bw, (int)ld, ell_adj,
@@ -590,9 +581,9 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
                       !(ctx->perm_on && ctx->opt_sell_sigma >= 128) && (double)nact * (double)bw * 12.0 <= 16e9;
     ScanOut res_stack;
     ScanOut &res = spec ? *reinterpret_cast<ScanOut *>(ctx->h_build + kHbStats) : res_stack;
-    HIP_TRY_B(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
     if (!spec) {
-        HIP_TRY_B(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (!state_order_check(ctx)) return kRedoBuild;
         if (res.bad) {
             ctx->err = "adj entry exceeds n";
@@ -601,7 +592,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
     }
     ctx->nchunks = nchunks;
     const int64_t nact2 = round_up(nact, 2 * kChunk);      // the banded kernel works on 128-row groups
-    HIP_TRY_B(ctx->d_diag.reserve((size_t)std::max<int64_t>(nact2, 128), false));
+    HIP_TRY(ctx->d_diag.reserve((size_t)std::max<int64_t>(nact2, 128), false));
     ctx->last_build_sell = false;
 
     // banded?  every used slot is one constant shift, and the diagonals are full enough
@@ -627,23 +618,23 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         ctx->sell_coded = false;
         ctx->sell_reach = -1;
         const int64_t bound = nact * (int64_t)bw;
-        HIP_TRY_B(ctx->d_off.reserve((size_t)nchunks + 1, false));
-        HIP_TRY_B(ctx->d_col.reserve((size_t)std::max<int64_t>(bound, 64), false));
-        HIP_TRY_B(ctx->d_val.reserve((size_t)std::max<int64_t>(bound, 64), false));
-        HIP_TRY_B(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
+        HIP_TRY(ctx->d_off.reserve((size_t)nchunks + 1, false));
+        HIP_TRY(ctx->d_col.reserve((size_t)std::max<int64_t>(bound, 64), false));
+        HIP_TRY(ctx->d_val.reserve((size_t)std::max<int64_t>(bound, 64), false));
+        HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
         // (off[0] = 0 is k_scan_offsets' own first store)
-        HIP_TRY_B(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
         hipLaunchKernelGGL(k_chunk_width, dim3((int)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, nchunks, nloc,
                            ctx->d_cnt.p, ctx->d_off.p);
         hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_off.p);
         int64_t *hslots = reinterpret_cast<int64_t *>(ctx->h_build + kHbSlots);
-        HIP_TRY_B(hipMemcpyAsync(hslots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hslots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0, ctx->d_off.p,
                            ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p);
         hipLaunchKernelGGL(k_sell_fill, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
                            (int)bw, (int)ld, ell_adj, ell_off, row0, nloc, ctx->d_off.p, ctx->d_ticket.p, ctx->d_col.p, ctx->d_val.p);
         launch_sell_sort_rows(ctx, nloc, bw, st);
-        HIP_TRY_B(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         ++ctx->spec_builds;
         if (!state_order_check(ctx)) return kRedoBuild;
         if (res.bad) {
@@ -685,13 +676,13 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         D.nchunks = nchunks;
         D.val = nullptr;
         D.diag = nullptr;
-        HIP_TRY_B(ctx->d_dia.reserve((size_t)nd * (size_t)nact2, false));
-        HIP_TRY_B(ctx->d_slot.reserve(kMaxDiag, false));
-        HIP_TRY_B(hipMemcpyAsync(ctx->d_slot.p, slot_of, sizeof(int) * (size_t)nd, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx->d_dia.reserve((size_t)nd * (size_t)nact2, false));
+        HIP_TRY(ctx->d_slot.reserve(kMaxDiag, false));
+        HIP_TRY(hipMemcpyAsync(ctx->d_slot.p, slot_of, sizeof(int) * (size_t)nd, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_ell_to_dia, dim3((int)((nact2 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
                            (int)ld, ell_adj, ell_off, ell_diag, row0, nloc, nd, D,
                            ctx->d_slot.p, ctx->d_dia.p, ctx->d_diag.p);
-        HIP_TRY_B(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         ctx->nd = nd;
         ctx->dia_ld = nact2;
         for (int d = 0; d < nd; ++d) ctx->delta[d] = D.delta[d];
@@ -714,41 +705,41 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         const int sigma = (int)ctx->opt_sell_sigma;
         ctx->order_n = 0;                                  // (d_perm is about to stop being the lexicographic order)
         const int grid = (int)(((int64_t)n + kBlock - 1) / kBlock);
-        HIP_TRY_B(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
+        HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
         unsigned long long *kin = ctx->d_keys.p, *kout = ctx->d_keys.p + n;     // (reserved by state_order_from_coords)
         int32_t *ord = ctx->d_ticket.p;
         hipLaunchKernelGGL(k_sigma_keys, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, sigma, ctx->d_cnt.p, kin, ctx->d_sortidx.p);
         int bits = 8;
         while ((1ull << bits) < ((unsigned long long)(n / sigma) + 1ull) * 128ull) ++bits;
         size_t tmp_bytes = 0;
-        HIP_TRY_B(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
-        HIP_TRY_B(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-        HIP_TRY_B(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
+        HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
         // perm'[i'] = perm[ord[i']] (internal -> caller), its inverse, the row lengths in the new order
         hipLaunchKernelGGL(k_gather_i32, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ord, ctx->d_perm.p, ctx->d_iperm.p);
-        HIP_TRY_B(hipMemcpyAsync(ctx->d_perm.p, ctx->d_iperm.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_perm.p, ctx->d_iperm.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_invert_perm, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ctx->d_perm.p, ctx->d_iperm.p);
         hipLaunchKernelGGL(k_gather_i32, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ord, ctx->d_cnt.p, ctx->d_sortidx.p);
-        HIP_TRY_B(hipMemcpyAsync(ctx->d_cnt.p, ctx->d_sortidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_cnt.p, ctx->d_sortidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_ell_relabel, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
                            (int)bw, (int)ld, ctx->d_perm.p, ctx->d_iperm.p, ctx->d_ell_adj.p, ctx->d_ell_off.p,
                            ctx->d_ell_diag.p, ctx->d_ell_adj2.p, ctx->d_ell_off2.p, ctx->d_ell_diag2.p);
     }
-    HIP_TRY_B(ctx->d_off.reserve((size_t)nchunks + 1, false));
-    HIP_TRY_B(hipMemsetAsync(ctx->d_off.p, 0, sizeof(int64_t), st));
+    HIP_TRY(ctx->d_off.reserve((size_t)nchunks + 1, false));
+    HIP_TRY(hipMemsetAsync(ctx->d_off.p, 0, sizeof(int64_t), st));
     if (nchunks > 0) {
         hipLaunchKernelGGL(k_chunk_width, dim3((int)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, nchunks,
                            nloc, ctx->d_cnt.p, ctx->d_off.p);
         hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_off.p);
     }
     int64_t slots = 0;
-    HIP_TRY_B(hipMemcpyAsync(&slots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY_B(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&slots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     ctx->slots = slots;
-    HIP_TRY_B(ctx->d_col.reserve((size_t)std::max<int64_t>(slots, 64), false));
-    HIP_TRY_B(ctx->d_val.reserve((size_t)std::max<int64_t>(slots, 64), false));
-    HIP_TRY_B(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
-    HIP_TRY_B(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
+    HIP_TRY(ctx->d_col.reserve((size_t)std::max<int64_t>(slots, 64), false));
+    HIP_TRY(ctx->d_val.reserve((size_t)std::max<int64_t>(slots, 64), false));
+    HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
+    HIP_TRY(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
     if (nchunks > 0) {
         hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0,
                            ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p);
@@ -756,7 +747,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
                            ell_off, row0, nloc, ctx->d_off.p, ctx->d_ticket.p, ctx->d_col.p, ctx->d_val.p);
         launch_sell_sort_rows(ctx, nloc, bw, st);
     }
-    HIP_TRY_B(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     ctx->have_sell = true;
     ctx->last_build_sell = true;
     return build_sell_code(ctx);
@@ -770,16 +761,16 @@ int build_dia_mask(kfsp_ctx *ctx)
     hipStream_t st = ctx->stream;
     const int64_t ngroups = ctx->dia_ld >> 7;
     if (ngroups < 1) return 0;
-    HIP_TRY_B(ctx->d_gmask.reserve((size_t)ngroups + 2, false));
+    HIP_TRY(ctx->d_gmask.reserve((size_t)ngroups + 2, false));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(ctx->d_scan.p);
-    HIP_TRY_B(ctx->d_scan.reserve(sizeof(ScanOut), false));
+    HIP_TRY(ctx->d_scan.reserve(sizeof(ScanOut), false));
     cnt = reinterpret_cast<unsigned long long *>(ctx->d_scan.p);
-    HIP_TRY_B(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_dia_group_mask, dim3((int)((ngroups + 3) / 4)), dim3(kBlock), 0, st, ngroups, ctx->nd,
                        ctx->dia_ld, ctx->d_dia.p, ctx->d_gmask.p, cnt);
     unsigned long long empty = 0;
-    HIP_TRY_B(hipMemcpyAsync(&empty, cnt, sizeof(empty), hipMemcpyDeviceToHost, st));
-    HIP_TRY_B(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&empty, cnt, sizeof(empty), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     // the masked variant trades a little address arithmetic for the skipped bytes: worth it from ~3 % on
     ctx->dia_masked = (double)empty >= 0.03 * (double)ctx->nd * (double)ngroups;
     ctx->dia_empty_segments = (int64_t)empty;
@@ -918,18 +909,18 @@ int build_dia_code(kfsp_ctx *ctx)
     const auto t0 = std::chrono::steady_clock::now();
     const int nd = ctx->nd;
     const int64_t ld = ctx->dia_ld;
-    HIP_TRY_B(ctx->d_dhash.reserve((size_t)2 * kMaxDiag * kDictSlots, false));
-    HIP_TRY_B(ctx->d_scan.reserve(sizeof(ScanOut), false));
+    HIP_TRY(ctx->d_dhash.reserve((size_t)2 * kMaxDiag * kDictSlots, false));
+    HIP_TRY(ctx->d_scan.reserve(sizeof(ScanOut), false));
     static_assert(sizeof(DictCount) + sizeof(unsigned int) <= sizeof(ScanOut), "the counters live in the scan scratch");
     DictCount *dcnt = reinterpret_cast<DictCount *>(ctx->d_scan.p);
     unsigned int *missed = reinterpret_cast<unsigned int *>(dcnt + 1);
-    HIP_TRY_B(hipMemsetAsync(dcnt, 0, sizeof(DictCount) + sizeof(unsigned int), st));
-    HIP_TRY_B(hipMemsetAsync(ctx->d_dhash.p, 0xFF, (size_t)nd * kDictSlots * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(dcnt, 0, sizeof(DictCount) + sizeof(unsigned int), st));
+    HIP_TRY(hipMemsetAsync(ctx->d_dhash.p, 0xFF, (size_t)nd * kDictSlots * sizeof(unsigned long long), st));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ld + kBlock - 1) / kBlock, 1024));
     hipLaunchKernelGGL(k_dia_dict_scan, dim3(grid), dim3(kBlock), 0, st, ld, nd, ctx->d_dia.p, ctx->d_dhash.p, dcnt);
     DictCount h;
-    HIP_TRY_B(hipMemcpyAsync(&h, dcnt, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY_B(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&h, dcnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     bool over = h.stop != 0;
     for (int d = 0; d < nd; ++d) {
         ctx->dia_distinct[d] = h.n[d];
@@ -942,8 +933,8 @@ int build_dia_code(kfsp_ctx *ctx)
         DiaCodeDev C;
         C.doff[0] = 0;
         for (int d = 0; d < kMaxDiag; ++d) C.doff[d + 1] = C.doff[d] + (d < nd ? (int32_t)ctx->dia_distinct[d] : 0);
-        HIP_TRY_B(ctx->d_ddict.reserve((size_t)kDictCap, false));
-        HIP_TRY_B(ctx->d_dcode.reserve((size_t)ld * (size_t)(rec / 8), false));
+        HIP_TRY(ctx->d_ddict.reserve((size_t)kDictCap, false));
+        HIP_TRY(ctx->d_dcode.reserve((size_t)ld * (size_t)(rec / 8), false));
         C.dict = ctx->d_ddict.p;
         C.rec = ctx->d_dcode.p;
         C.w = w;
@@ -957,8 +948,8 @@ int build_dia_code(kfsp_ctx *ctx)
         else if (rec == 8) hipLaunchKernelGGL((k_dia_encode<16, 8>), g, b, lds, st, ld, nd, ctx->d_dia.p, C, ctx->d_dcode.p, missed);
         else hipLaunchKernelGGL((k_dia_encode<16, 16>), g, b, lds, st, ld, nd, ctx->d_dia.p, C, ctx->d_dcode.p, missed);
         unsigned int hm = 0;
-        HIP_TRY_B(hipMemcpyAsync(&hm, missed, sizeof(hm), hipMemcpyDeviceToHost, st));
-        HIP_TRY_B(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&hm, missed, sizeof(hm), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (hm != 0) {
             ctx->err = "coded banded image: a stored value is missing from its dictionary";
             return -1;
@@ -1070,7 +1061,7 @@ int build_sell_code(kfsp_ctx *ctx)
     if (!ctx->have_sell || ctx->nchunks < 1) return 0;
     hipStream_t st = ctx->stream;
     const int64_t nchunks = ctx->nchunks;
-    HIP_TRY_B(ctx->d_scan.reserve(sizeof(ScanOut), false));
+    HIP_TRY(ctx->d_scan.reserve(sizeof(ScanOut), false));
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(ctx->d_scan.p);
     // the reach of the rows (a bounded reach lets a partitioned product exchange halo strips instead of whole vectors):
     // only a communicator asks for it
@@ -1081,28 +1072,28 @@ int build_sell_code(kfsp_ctx *ctx)
     const bool want = ctx->opt_sell_code > 0 ||
                       (ctx->opt_sell_code < 0 && ctx->perm_on && (double)ctx->slots * 12.0 > 256.0 * 1024 * 1024);
     if (!want && !want_reach) return 0;
-    HIP_TRY_B(hipMemsetAsync(stats, 0, 8 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(stats, 0, 8 * sizeof(unsigned long long), st));
     if (want_reach)
         hipLaunchKernelGGL(k_sell_reach, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, ctx->row0, ctx->d_off.p,
                            ctx->d_col.p, stats + 4);
     if (want) {
-        HIP_TRY_B(ctx->d_codeoff.reserve((size_t)nchunks + 1, false));
-        HIP_TRY_B(hipMemsetAsync(ctx->d_codeoff.p, 0, sizeof(int64_t), st));
+        HIP_TRY(ctx->d_codeoff.reserve((size_t)nchunks + 1, false));
+        HIP_TRY(hipMemsetAsync(ctx->d_codeoff.p, 0, sizeof(int64_t), st));
         hipLaunchKernelGGL(k_code_width, dim3((int)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, nchunks, ctx->d_off.p,
                            ctx->d_codeoff.p);
         hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_codeoff.p);
         int64_t words = 0;
-        HIP_TRY_B(hipMemcpyAsync(&words, ctx->d_codeoff.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY_B(hipStreamSynchronize(st));
-        HIP_TRY_B(ctx->d_code.reserve((size_t)std::max<int64_t>(words, 64), false));
-        HIP_TRY_B(ctx->d_dtab.reserve((size_t)nchunks * 64, false));
-        HIP_TRY_B(ctx->d_dtlen.reserve((size_t)nchunks, false));
+        HIP_TRY(hipMemcpyAsync(&words, ctx->d_codeoff.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(ctx->d_code.reserve((size_t)std::max<int64_t>(words, 64), false));
+        HIP_TRY(ctx->d_dtab.reserve((size_t)nchunks * 64, false));
+        HIP_TRY(ctx->d_dtlen.reserve((size_t)nchunks, false));
         hipLaunchKernelGGL(k_sell_code, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, ctx->row0, ctx->d_off.p,
                            ctx->d_col.p, ctx->d_codeoff.p, ctx->d_dtab.p, ctx->d_dtlen.p, ctx->d_code.p, stats);
     }
     unsigned long long h[8];
-    HIP_TRY_B(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY_B(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (want_reach) ctx->sell_reach = (int64_t)h[4];
     if (!want) return 0;
     ctx->coded_chunks = (int64_t)h[0];
@@ -1154,24 +1145,24 @@ int compact_resident_ell(kfsp_ctx *ctx, int64_t n, int bw, int ld, const uint8_t
 {
     hipStream_t st = ctx->stream;
     const size_t nent2 = (size_t)n_keep * (size_t)ld;
-    HIP_TRY_B(ctx->d_ell_adj2.reserve(std::max<size_t>(nent2, 64), false));
-    HIP_TRY_B(ctx->d_ell_off2.reserve(std::max<size_t>(nent2, 64), false));
-    HIP_TRY_B(ctx->d_ell_diag2.reserve(std::max<size_t>((size_t)n_keep, 64), false));
-    if (with_coords) HIP_TRY_B(ctx->d_coords2.reserve((size_t)n_keep * (size_t)lds + 128, false));
-    HIP_TRY_B(ctx->d_sortidx.reserve(2 * (size_t)n + 64, false));
+    HIP_TRY(ctx->d_ell_adj2.reserve(std::max<size_t>(nent2, 64), false));
+    HIP_TRY(ctx->d_ell_off2.reserve(std::max<size_t>(nent2, 64), false));
+    HIP_TRY(ctx->d_ell_diag2.reserve(std::max<size_t>((size_t)n_keep, 64), false));
+    if (with_coords) HIP_TRY(ctx->d_coords2.reserve((size_t)n_keep * (size_t)lds + 128, false));
+    HIP_TRY(ctx->d_sortidx.reserve(2 * (size_t)n + 64, false));
     int32_t *flag32 = ctx->d_sortidx.p, *scan = ctx->d_sortidx.p + n;
     const int grid = (int)((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_u8_to_i32, dim3(grid), dim3(kBlock), 0, st, n, keep, flag32);
     size_t tmp_bytes = 0;
-    HIP_TRY_B(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, flag32, scan, (int)n, st));
-    HIP_TRY_B(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-    HIP_TRY_B(hipcub::DeviceScan::ExclusiveSum(ctx->d_sorttmp.p, tmp_bytes, flag32, scan, (int)n, st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, flag32, scan, (int)n, st));
+    HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->d_sorttmp.p, tmp_bytes, flag32, scan, (int)n, st));
     const int grid_e = (int)((n * (int64_t)ld + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_ell_compact, dim3(grid_e), dim3(kBlock), 0, st, n, bw, ld, lds, lds, keep, scan, ctx->d_ell_adj.p,
                        ctx->d_ell_off.p, ctx->d_ell_diag.p, with_coords ? ctx->d_coords.p : (const int32_t *)nullptr, ctx->d_ell_adj2.p,
                        ctx->d_ell_off2.p, ctx->d_ell_diag2.p, with_coords ? ctx->d_coords2.p : (int32_t *)nullptr);
     // (everything that follows is ordered behind this on the same stream; the rebuild waits once, at its end)
-    if (!ctx->opt_build_speculate || ctx->use_comm) HIP_TRY_B(hipStreamSynchronize(st));
+    if (!ctx->opt_build_speculate || ctx->use_comm) HIP_TRY(hipStreamSynchronize(st));
     std::swap(ctx->d_ell_adj, ctx->d_ell_adj2);
     std::swap(ctx->d_ell_off, ctx->d_ell_off2);
     std::swap(ctx->d_ell_diag, ctx->d_ell_diag2);
@@ -1239,12 +1230,12 @@ int box_materialize(kfsp_ctx *ctx)
 {
     hipStream_t st = ctx->stream;
     const int64_t ld = ctx->dia_ld;
-    HIP_TRY_B(ctx->d_dia.reserve((size_t)ctx->box.nr * (size_t)ld, false));
-    HIP_TRY_B(ctx->d_diag.reserve((size_t)ld + 2 * kChunk, true));
+    HIP_TRY(ctx->d_dia.reserve((size_t)ctx->box.nr * (size_t)ld, false));
+    HIP_TRY(ctx->d_diag.reserve((size_t)ld + 2 * kChunk, true));
     if (ld > 0)
         hipLaunchKernelGGL(k_box_materialize, dim3((int)((ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ctx->box,
                            ctx->d_box.p, ctx->row0, ctx->nloc, ld, ctx->d_dia.p, ctx->d_diag.p);
-    HIP_TRY_B(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -1264,11 +1255,11 @@ int state_order_from_coords(kfsp_ctx *ctx, int32_t n, int32_t ns, int32_t ld, co
     if (ns > 16) return 0;                                 // more species than the key layout holds
     hipStream_t st = ctx->stream;
     const size_t nent = (size_t)n * (size_t)ld, k0 = (size_t)keep * (size_t)ld;
-    HIP_TRY_B(ctx->d_coords.reserve_keep(nent + 64, k0, st));
+    HIP_TRY(ctx->d_coords.reserve_keep(nent + 64, k0, st));
     if (nent > k0)
-        HIP_TRY_B(hipMemcpyAsync(ctx->d_coords.p + k0, state + k0, (nent - k0) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->d_coords.p + k0, state + k0, (nent - k0) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (!order) {                                          // (option keep_coords: resident for the expansion, the caller's order stays)
-        HIP_TRY_B(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         ctx->coords_n = n;
         ctx->coords_ld = ld;
         ctx->coords_ns = ns;
@@ -1308,11 +1299,11 @@ int state_order_from_resident(kfsp_ctx *ctx, int32_t n, int32_t ns, int32_t ld, 
         mm_init[2 * k + 1] = INT_MIN;
     }
     int *dmm = reinterpret_cast<int *>(ctx->d_coords.p + nent);
-    HIP_TRY_B(hipMemcpyAsync(dmm, mm_init, sizeof(int) * 2 * (size_t)ns, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dmm, mm_init, sizeof(int) * 2 * (size_t)ns, hipMemcpyHostToDevice, st));
     const int grid = (int)((count + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_coord_minmax, dim3(std::min(grid, 1024)), dim3(kBlock), 0, st, count, (int)ns, (int)ld,
                        ctx->d_coords.p + (size_t)first * (size_t)ld, dmm);
-    HIP_TRY_B(hipMemcpyAsync(mm, dmm, sizeof(int) * 2 * (size_t)ns, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mm, dmm, sizeof(int) * 2 * (size_t)ns, hipMemcpyDeviceToHost, st));
     KeyLayout L;
     L.ns = ns;
     int bits = 0;
@@ -1324,7 +1315,7 @@ int state_order_from_resident(kfsp_ctx *ctx, int32_t n, int32_t ns, int32_t ld, 
         }
         bits = ctx->kc_bits;
     } else {
-        HIP_TRY_B(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         ctx->kc_ok = false;
         for (int k = 0; k < ns; ++k) {
             const long long range = (long long)mm[2 * k + 1] - (long long)mm[2 * k];
@@ -1347,9 +1338,9 @@ int state_order_from_resident(kfsp_ctx *ctx, int32_t n, int32_t ns, int32_t ld, 
     ctx->coords_n = n;                                     // (the coordinates stay resident: kfsp_ssa_streams may use them)
     ctx->coords_ld = ld;
     ctx->coords_ns = ns;
-    HIP_TRY_B(ctx->d_keys.reserve(2 * (size_t)n, false));
-    HIP_TRY_B(ctx->d_sortidx.reserve(std::max((size_t)n, 2 * (size_t)count), false));
-    HIP_TRY_B(ctx->d_iperm.reserve((size_t)n, false));
+    HIP_TRY(ctx->d_keys.reserve(2 * (size_t)n, false));
+    HIP_TRY(ctx->d_sortidx.reserve(std::max((size_t)n, 2 * (size_t)count), false));
+    HIP_TRY(ctx->d_iperm.reserve((size_t)n, false));
     const int gridn = (int)(((int64_t)n + kBlock - 1) / kBlock);
     unsigned long long *kin = ctx->d_keys.p;
     hipLaunchKernelGGL(k_pack_keys, dim3(grid), dim3(kBlock), 0, st, count, (int)ld, ctx->d_coords.p + (size_t)first * (size_t)ld, L, kin,
@@ -1359,28 +1350,28 @@ int state_order_from_resident(kfsp_ctx *ctx, int32_t n, int32_t ns, int32_t ld, 
         unsigned long long *knew = ctx->d_keys.p + count;
         int32_t *inew = ctx->d_sortidx.p + count;
         size_t tmp_bytes = 0;
-        HIP_TRY_B(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, knew, ctx->d_sortidx.p, inew, (int)count, 0, bits, st));
-        HIP_TRY_B(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-        HIP_TRY_B(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, knew, ctx->d_sortidx.p, inew, (int)count, 0, bits, st));
-        HIP_TRY_B(ctx->d_perm2.reserve((size_t)n, false));
-        HIP_TRY_B(ctx->d_skeys2.reserve((size_t)n, false));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, knew, ctx->d_sortidx.p, inew, (int)count, 0, bits, st));
+        HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, knew, ctx->d_sortidx.p, inew, (int)count, 0, bits, st));
+        HIP_TRY(ctx->d_perm2.reserve((size_t)n, false));
+        HIP_TRY(ctx->d_skeys2.reserve((size_t)n, false));
         hipLaunchKernelGGL(k_merge_sorted, dim3(gridn), dim3(kBlock), 0, st, (int64_t)n_prev, ctx->d_skeys.p, ctx->d_perm.p, count, knew, inew,
                            ctx->d_skeys2.p, ctx->d_perm2.p);
         std::swap(ctx->d_perm, ctx->d_perm2);
         std::swap(ctx->d_skeys, ctx->d_skeys2);
         ++ctx->order_merges;
     } else {
-        HIP_TRY_B(ctx->d_perm.reserve((size_t)n, false));
-        HIP_TRY_B(ctx->d_skeys.reserve((size_t)n, false));
+        HIP_TRY(ctx->d_perm.reserve((size_t)n, false));
+        HIP_TRY(ctx->d_skeys.reserve((size_t)n, false));
         size_t tmp_bytes = 0;
-        HIP_TRY_B(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, ctx->d_skeys.p, ctx->d_sortidx.p, ctx->d_perm.p, (int)n,
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, ctx->d_skeys.p, ctx->d_sortidx.p, ctx->d_perm.p, (int)n,
                                                      0, bits, st));
-        HIP_TRY_B(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-        HIP_TRY_B(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, ctx->d_skeys.p, ctx->d_sortidx.p, ctx->d_perm.p,
+        HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, ctx->d_skeys.p, ctx->d_sortidx.p, ctx->d_perm.p,
                                                      (int)n, 0, bits, st));
     }
     hipLaunchKernelGGL(k_invert_perm, dim3(gridn), dim3(kBlock), 0, st, (int64_t)n, ctx->d_perm.p, ctx->d_iperm.p);
-    if (!spec) HIP_TRY_B(hipStreamSynchronize(st));
+    if (!spec) HIP_TRY(hipStreamSynchronize(st));
     ctx->order_n = n;
     ctx->skeys_n = n;
     *ok = true;

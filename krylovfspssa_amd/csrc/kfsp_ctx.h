@@ -153,7 +153,7 @@ struct kfsp_ctx {
     // partition
     int nranks = 1, rank = 0;
     ncclComm_t comm = nullptr;
-    std::mutex comm_mu;                // held while a collective is ENQUEUED on comm, and by comm_abort (kfsp_api.cpp)
+    std::mutex comm_mu;                // held while a collective is ENQUEUED on comm, and by comm_abort (kfsp_comm.cpp)
     bool comm_aborted = false;         // sticky (under comm_mu): the communicator was aborted, every collective returns 2999
     kfsp::LoopGroup *loop = nullptr;   // loop-back transport instead of RCCL (kfsp_comm_init_loopback)
     double *h_loop = nullptr;          // its pinned scratch
@@ -390,7 +390,7 @@ struct kfsp_ctx {
 
 namespace kfsp {
 // group contexts (kfsp_group.cpp): what each entry point of include/kfsp.h does when it is handed a head
-void comm_abort(kfsp_ctx *ctx);      // kfsp_api.cpp: release a rank blocked in a collective (called from the group's watchdog)
+void comm_abort(kfsp_ctx *ctx);      // kfsp_comm.cpp: release a rank blocked in a collective (called from the group's watchdog)
 int group_selftest(int nranks, int failing_rank, int hanging_rank, int work_ms, int hang_ms, int timeout_ms, int grace_ms,
                    int settle_ms, int *rc_out, int *who_out, double *seconds, int *broken, int *stuck);
 int group_create(int nranks, const int *devices, kfsp_ctx **out);
@@ -491,8 +491,18 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
                      const int32_t *d_state, int32_t lds, const int32_t *d_adj, const double *d_off, int32_t lda, const double *d_diag,
                      int32_t max_count, int32_t cap_new, int32_t ldo, int32_t *n_found, int32_t **sn, double **on, double **dn,
                      bool partitioned = false);
-int comm_gather_doubles(kfsp_ctx *ctx, const double *send, double *recv, size_t count, hipStream_t st);
-int comm_gather_bytes(kfsp_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st);
+// the collectives of the data path and the halo exchange (kfsp_comm.cpp), over RCCL or the loop-back transport, on stream st:
+// buf[0..count) <- sum (or max) over ranks; recv[p*count ..) <- send of rank p, for doubles and for raw bytes
+int comm_allreduce(kfsp_ctx *ctx, double *buf, int count, bool take_max, hipStream_t st);
+int comm_allgather(kfsp_ctx *ctx, const double *send, double *recv, size_t count, hipStream_t st);
+int comm_allgather_bytes(kfsp_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st);
+// the neighbours' boundary strips into the margins of the source column; the whole source column visible before a product
+// (*xg: where global index 0 lies); after a generator was set: agree across ranks on the exchange mode
+int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st);
+int gather_source(kfsp_ctx *ctx, const double *src_local, const double **xg);
+int setup_exchange(kfsp_ctx *ctx);
+// (re)size everything that depends on the number of states (kfsp_api.cpp)
+int resize(kfsp_ctx *ctx, int64_t n);
 // SSA walk + one-step sweep on the resident lists (kfsp_expand.hip)
 int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, int32_t nr, const int32_t *stoich,
                           int32_t max_count, int32_t cap, int64_t *n_out, int64_t *n_ssa);

@@ -24,6 +24,7 @@
 // The sweeps read ADJ (4 nr bytes per state) and gather a few table slots for the boundary states only.
 #include "kfsp_prop_dev.h"
 #include "kfsp_hash_dev.h"
+#include "kfsp_host.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -262,15 +263,6 @@ struct Arena {
 
 inline int blocks(int64_t n) { return (int)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
 
-#define X_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return 1000 + (int)e_;                                                         \
-        }                                                                                  \
-    } while (0)
-
 int fill_model(kfsp_ctx *ctx, XDev &A, int ns, int nr, const int32_t *stoich, int n, int lds, int lda, int max_count)
 {
     std::memset(&A, 0, sizeof(A));
@@ -303,43 +295,43 @@ int sweep_count(kfsp_ctx *ctx, XDev &A, int **cnt_out, int **off_out, int *nu_ou
     const int n = A.n;
     unsigned slots = 64;
     while (slots < 2u * (unsigned)n) slots <<= 1;
-    X_TRY(ctx->d_os1.reserve((size_t)slots * 8 + 2 * ((size_t)n + 1) * 4 + 4096, false));
+    HIP_TRY(ctx->d_os1.reserve((size_t)slots * 8 + 2 * ((size_t)n + 1) * 4 + 4096, false));
     Arena a1{ctx->d_os1.p};
     unsigned long long *d_tab = a1.take<unsigned long long>(slots);
     int *d_cnt = a1.take<int>((size_t)n + 1), *d_off = a1.take<int>((size_t)n + 1);
     unsigned long long *d_ncand = a1.take<unsigned long long>(2);
-    X_TRY(hipMemsetAsync(d_tab, 0, (size_t)slots * 8, st));
-    X_TRY(hipMemsetAsync(d_ncand, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(d_tab, 0, (size_t)slots * 8, st));
+    HIP_TRY(hipMemsetAsync(d_ncand, 0, 16, st));
     launch_table_build64(n, A.ns, A.lds, A.state, d_tab, slots - 1, nullptr, 0, st);
     A.tab = d_tab;
     A.tmask = slots - 1;
     const int64_t nent = (int64_t)n * A.lda;
     hipLaunchKernelGGL(k_x_mark, dim3(blocks(nent)), dim3(kBlock), 0, st, A, d_ncand);
     unsigned long long nc = 0;
-    X_TRY(hipMemcpyAsync(&nc, d_ncand, sizeof(nc), hipMemcpyDeviceToHost, st));
-    X_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&nc, d_ncand, sizeof(nc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *nu_out = 0;
     *cnt_out = d_cnt;
     *off_out = d_off;
     if (nc == 0) return 0;
     unsigned slots2 = 64;
     while (slots2 < 2ull * nc) slots2 <<= 1;
-    X_TRY(ctx->d_os2.reserve((size_t)slots2 * 8 + 1024, false));
+    HIP_TRY(ctx->d_os2.reserve((size_t)slots2 * 8 + 1024, false));
     Arena a2{ctx->d_os2.p};
     A.tab2 = a2.take<int32_t>(slots2);
     A.newidx = a2.take<int32_t>(slots2);
     A.tmask2 = slots2 - 1;
-    X_TRY(hipMemsetAsync(A.tab2, 0x7f, (size_t)slots2 * 4, st));
-    X_TRY(hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * sizeof(int), st));      // (cnt[n] = 0: the scan's last element is the total)
+    HIP_TRY(hipMemsetAsync(A.tab2, 0x7f, (size_t)slots2 * 4, st));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * sizeof(int), st));      // (cnt[n] = 0: the scan's last element is the total)
     hipLaunchKernelGGL(k_x_insert, dim3(blocks(nent)), dim3(kBlock), 0, st, A);
     hipLaunchKernelGGL(k_x_heads, dim3(blocks(nent)), dim3(kBlock), 0, st, A, d_cnt);
     size_t tmp_bytes = 0;
-    X_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt, d_off, n + 1, st));
-    X_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-    X_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->d_sorttmp.p, tmp_bytes, d_cnt, d_off, n + 1, st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt, d_off, n + 1, st));
+    HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->d_sorttmp.p, tmp_bytes, d_cnt, d_off, n + 1, st));
     int nu = 0;
-    X_TRY(hipMemcpyAsync(&nu, d_off + n, sizeof(int), hipMemcpyDeviceToHost, st));
-    X_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&nu, d_off + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *nu_out = nu;
     return 0;
 }
@@ -369,11 +361,11 @@ int onestep_device(kfsp_ctx *ctx, int32_t ns, int32_t nr, const int32_t *stoich,
     hipStream_t st = ctx->stream;
     XDev A;
     if (int rc = fill_model(ctx, A, ns, nr, stoich, n, lds, lda, max_count)) return rc;
-    X_TRY(ctx->d_os3.reserve(((size_t)n * lds + (size_t)n * lda) * 4 + 1024, false));
+    HIP_TRY(ctx->d_os3.reserve(((size_t)n * lds + (size_t)n * lda) * 4 + 1024, false));
     Arena a3{ctx->d_os3.p};
     int32_t *d_state = a3.take<int32_t>((size_t)n * lds), *d_adj = a3.take<int32_t>((size_t)n * lda);
-    X_TRY(hipMemcpyAsync(d_state, state, (size_t)n * lds * 4, hipMemcpyHostToDevice, st));
-    X_TRY(hipMemcpyAsync(d_adj, adj, (size_t)n * lda * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_state, state, (size_t)n * lds * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_adj, adj, (size_t)n * lda * 4, hipMemcpyHostToDevice, st));
     A.state = d_state;
     A.adj = d_adj;
     int *d_cnt = nullptr, *d_off = nullptr, nu = 0;
@@ -384,7 +376,7 @@ int onestep_device(kfsp_ctx *ctx, int32_t ns, int32_t nr, const int32_t *stoich,
     }
     if (nu > 0) {
         const size_t ob = off_new ? (size_t)nu * (size_t)ldo * 8 : 0;
-        X_TRY(ctx->d_os4.reserve((size_t)nu * (lds + lda) * 4 + ob + (size_t)nu * 8 + 2048, false));
+        HIP_TRY(ctx->d_os4.reserve((size_t)nu * (lds + lda) * 4 + ob + (size_t)nu * 8 + 2048, false));
         Arena a4{ctx->d_os4.p};
         A.state_new = a4.take<int32_t>((size_t)nu * lds);
         A.adj_new = a4.take<int32_t>((size_t)nu * lda);
@@ -399,15 +391,15 @@ int onestep_device(kfsp_ctx *ctx, int32_t ns, int32_t nr, const int32_t *stoich,
             if (int rc = prop_check_overflow(ctx)) return rc;
         }
         sweep_link(ctx, A, nu);
-        X_TRY(hipMemcpyAsync(state_new, A.state_new, (size_t)nu * lds * 4, hipMemcpyDeviceToHost, st));
-        X_TRY(hipMemcpyAsync(adj_out + (size_t)n * lda, A.adj_new, (size_t)nu * lda * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(state_new, A.state_new, (size_t)nu * lds * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(adj_out + (size_t)n * lda, A.adj_new, (size_t)nu * lda * 4, hipMemcpyDeviceToHost, st));
         if (off_new) {
-            X_TRY(hipMemcpyAsync(off_new, d_on, ob, hipMemcpyDeviceToHost, st));
-            X_TRY(hipMemcpyAsync(diag_new, d_dn, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(off_new, d_on, ob, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(diag_new, d_dn, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
         }
     }
-    X_TRY(hipMemcpyAsync(adj_out, d_adj, (size_t)n * lda * 4, hipMemcpyDeviceToHost, st));
-    X_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(adj_out, d_adj, (size_t)n * lda * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *n_out = n + nu;
     return 0;
 }
@@ -433,15 +425,15 @@ int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t 
             return rc;
         if (nnew > 0) {
             n1 = n + nnew;
-            X_TRY(ctx->d_coords.reserve_keep((size_t)n1 * lds + 64, (size_t)n * lds, st));
-            X_TRY(ctx->d_ell_adj.reserve_keep((size_t)n1 * lda, (size_t)n * lda, st));
-            X_TRY(ctx->d_ell_off.reserve_keep((size_t)n1 * lda, (size_t)n * lda, st));
-            X_TRY(ctx->d_ell_diag.reserve_keep((size_t)n1, (size_t)n, st));
-            X_TRY(hipMemcpyAsync(ctx->d_coords.p + (size_t)n * lds, d_sn, (size_t)nnew * lds * 4, hipMemcpyDeviceToDevice, st));
-            X_TRY(hipMemcpyAsync(ctx->d_ell_off.p + (size_t)n * lda, d_on, (size_t)nnew * lda * 8, hipMemcpyDeviceToDevice, st));
-            X_TRY(hipMemcpyAsync(ctx->d_ell_diag.p + n, d_dn, (size_t)nnew * 8, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(ctx->d_coords.reserve_keep((size_t)n1 * lds + 64, (size_t)n * lds, st));
+            HIP_TRY(ctx->d_ell_adj.reserve_keep((size_t)n1 * lda, (size_t)n * lda, st));
+            HIP_TRY(ctx->d_ell_off.reserve_keep((size_t)n1 * lda, (size_t)n * lda, st));
+            HIP_TRY(ctx->d_ell_diag.reserve_keep((size_t)n1, (size_t)n, st));
+            HIP_TRY(hipMemcpyAsync(ctx->d_coords.p + (size_t)n * lds, d_sn, (size_t)nnew * lds * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->d_ell_off.p + (size_t)n * lda, d_on, (size_t)nnew * lda * 8, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->d_ell_diag.p + n, d_dn, (size_t)nnew * 8, hipMemcpyDeviceToDevice, st));
             // (their links are left to the sweep: it completes every column that arrives as zeros)
-            X_TRY(hipMemsetAsync(ctx->d_ell_adj.p + (size_t)n * lda, 0, (size_t)nnew * lda * 4, st));
+            HIP_TRY(hipMemsetAsync(ctx->d_ell_adj.p + (size_t)n * lda, 0, (size_t)nnew * lda * 4, st));
             *n_ssa = nnew;
         }
     }
@@ -454,16 +446,16 @@ int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t 
     if (int rc = sweep_count(ctx, A, &d_cnt, &d_off, &nu)) return rc;
     if ((int64_t)n1 + nu > cap) {
         hipLaunchKernelGGL(k_x_unmark, dim3(blocks((int64_t)n * lda)), dim3(kBlock), 0, st, A, (int)n);
-        X_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         ctx->err = "FSP SIZE EXCEEDS MEMORY LIMIT";
         return -11;
     }
     if (nu > 0) {
         const int32_t n2 = n1 + nu;
-        X_TRY(ctx->d_coords.reserve_keep((size_t)n2 * lds + 64, (size_t)n1 * lds, st));
-        X_TRY(ctx->d_ell_adj.reserve_keep((size_t)n2 * lda, (size_t)n1 * lda, st));
-        X_TRY(ctx->d_ell_off.reserve_keep((size_t)n2 * lda, (size_t)n1 * lda, st));
-        X_TRY(ctx->d_ell_diag.reserve_keep((size_t)n2, (size_t)n1, st));
+        HIP_TRY(ctx->d_coords.reserve_keep((size_t)n2 * lds + 64, (size_t)n1 * lds, st));
+        HIP_TRY(ctx->d_ell_adj.reserve_keep((size_t)n2 * lda, (size_t)n1 * lda, st));
+        HIP_TRY(ctx->d_ell_off.reserve_keep((size_t)n2 * lda, (size_t)n1 * lda, st));
+        HIP_TRY(ctx->d_ell_diag.reserve_keep((size_t)n2, (size_t)n1, st));
         A.state = ctx->d_coords.p;
         A.adj = ctx->d_ell_adj.p;
         A.state_new = ctx->d_coords.p + (size_t)n1 * lds;
@@ -474,14 +466,14 @@ int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t 
             // an appended state lies beyond a two-species table: the sweep is taken back (as for -11) - the first n columns are
             // what they were, the caller enlarges the table and repeats the whole step
             hipLaunchKernelGGL(k_x_unmark, dim3(blocks((int64_t)n * lda)), dim3(kBlock), 0, st, A, (int)n);
-            X_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipStreamSynchronize(st));
             return rc;
         }
         sweep_link(ctx, A, nu);
     }
     // (kept although the caller's rebuild follows on the same stream: without it the run is 12 ms of 2 550 shorter, and the
     // trace's DEVICE_ONESTEP / UPLOAD lines no longer say where the device's time went)
-    X_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     *n_out = (int64_t)n1 + nu;
     return 0;
 }

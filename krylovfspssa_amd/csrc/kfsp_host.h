@@ -1,0 +1,100 @@
+// Private: what the host code of every translation unit of libkfsp_hip shares - status codes and texts of failed
+// calls, the exception fence of the C boundary, the phase timer, the launch rules of the generator product and of the
+// streaming kernels, and the generator's part of the kernel arguments.  Plain inline host code: a stand-alone program
+// can call the grid rules without a device (tests/grid_rule_check.cpp).
+#pragma once
+
+#include "kfsp_ctx.h"
+
+#include <chrono>
+#include <exception>
+#include <new>
+#include <string>
+
+namespace kfsp {
+
+// (c may be null: an entry point that fails before it has a context still returns its code)
+inline int fail(kfsp_ctx *c, int code, const char *what)
+{
+    if (c) c->err = what;
+    return code;
+}
+
+inline int hip_fail(kfsp_ctx *c, hipError_t e, const char *where)
+{
+    if (c) c->err = std::string(where) + ": " + hipGetErrorString(e);
+    return 1000 + (int)e;
+}
+
+// for functions that return a status code and call their context `ctx`
+#define HIP_TRY(expr)                                          \
+    do {                                                       \
+        hipError_t e_ = (expr);                                \
+        if (e_ != hipSuccess) return hip_fail(ctx, e_, #expr); \
+    } while (0)
+
+// C++ exceptions (host allocations) end at the C boundary as status codes
+template <class F>
+int no_throw(kfsp_ctx *c, F &&body, const char *other = "unknown exception")
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        return fail(c, 4001, "out of host memory");
+    } catch (const std::exception &e) {
+        if (c) c->err = std::string("exception: ") + e.what();
+        return 4000;
+    } catch (...) {
+        return fail(c, 4000, other);
+    }
+}
+
+struct PhaseTimer {
+    kfsp_ctx *c;
+    int phase;
+    std::chrono::steady_clock::time_point t0;
+    PhaseTimer(kfsp_ctx *c_, int p) : c(c_), phase(p), t0(std::chrono::steady_clock::now()) {}
+    ~PhaseTimer() { c->t_ms[phase] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// ---- the launch rule of the generator product, single vector and block alike
+// a wavefront trip covers 64 rows (one SELL chunk) or 128 rows (banded and matrix-free forms, two rows per lane)
+inline int64_t product_trips(int64_t nchunks, bool dia) { return dia ? (nchunks + 1) / 2 : nchunks; }
+
+// Workgroups (4 wavefronts, one trip each at a time) for `trips` trips: a multiple of 8, at least 8, at most option
+// grid_blocks (opt_grid > 0, rounded up to 8) or else dflt_cap - and never more than kMaxGrid, whatever the option
+// says: a producer's block partials go to a slot of kMaxGrid doubles (next_partial, d_bpart).
+// dflt_cap of a stored generator is 1024: 4 workgroups per CU already saturate HBM with the 5-9 independent loads a
+// lane keeps in flight, and halve the partial sums every consumer has to re-add (measured: profiles/r01_sweep.log).
+inline int product_grid(int64_t trips, int64_t opt_grid, int64_t dflt_cap)
+{
+    const int64_t cap = std::min<int64_t>(opt_grid > 0 ? round_up(opt_grid, 8) : dflt_cap, kMaxGrid);
+    return (int)std::max<int64_t>(std::min<int64_t>(round_up((trips + 3) / 4, 8), cap), 8);
+}
+
+// Streaming kernels over `pairs` 16-byte pairs: every consumer re-sums the producer's partials, so the grid is kept at
+// <= 1024 workgroups (4 per CU; option vec_grid_blocks) with >= 4 pairs per lane; the loops are unrolled so that this
+// still keeps > 16 MB of loads in flight.
+inline int vec_grid(int64_t pairs, int64_t opt_vgrid)
+{
+    const int64_t g = (pairs + 4 * kBlock - 1) / (4 * kBlock);
+    return (int)std::max<int64_t>(std::min<int64_t>(g, std::min<int64_t>(opt_vgrid > 0 ? opt_vgrid : 1024, kMaxGrid)), 1);
+}
+
+// the generator's stored images as the kernels take them
+inline void generator_args(const kfsp_ctx *c, SellDev &A, DiaDev &D)
+{
+    A = SellDev{c->nloc, c->nchunks, c->d_off.p, c->d_col.p, c->d_val.p, c->d_diag.p,
+                c->d_dtab.p, c->d_dtlen.p, c->d_code.p, c->d_codeoff.p};
+    D.nd = c->nd;
+    for (int d = 0; d < kMaxDiag; ++d) D.delta[d] = c->delta[d];
+    D.val = c->d_dia.p;
+    D.ld = c->dia_ld;
+    D.diag = c->d_diag.p;
+    D.nchunks = c->nchunks;
+    D.n = c->n;
+    D.gmask = c->dia_masked ? c->d_gmask.p : nullptr;
+    D.zero = c->d_zero.p;
+}
+
+}  // namespace kfsp

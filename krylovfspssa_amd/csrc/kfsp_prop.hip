@@ -19,6 +19,7 @@
 // 0 .. tab_len - 1 and the device looks it up; populations beyond the table fall back to the interpreter.
 // Propensities of several species built from + - * / alone (mass action c X Y) are exact either way.
 #include "kfsp_prop_dev.h"
+#include "kfsp_host.h"
 
 #include <cstring>
 
@@ -45,15 +46,6 @@ __global__ __launch_bounds__(kBlock) void k_propensities(PropDev P, int64_t n, c
 }
 
 }  // namespace
-
-#define HIP_TRY_P(expr)                                                                    \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return 1000 + (int)e_;                                                         \
-        }                                                                                  \
-    } while (0)
 
 int prop_set_program(kfsp_ctx *ctx, int32_t ns, int32_t nr, int32_t np, const double *params, const int32_t *code_off,
                      const int32_t *code, const int32_t *imm_off, const double *imm, const int32_t *tab_species, int32_t tab_len,
@@ -178,15 +170,15 @@ int prop_set_program(kfsp_ctx *ctx, int32_t ns, int32_t nr, int32_t np, const do
     ib.insert(ib.end(), mono.begin(), mono.end());
     ctx->prop_monoc_off = db.size();
     db.insert(db.end(), mono_c.begin(), mono_c.end());
-    HIP_TRY_P(ctx->d_prop_i.reserve(ib.size(), false));
-    HIP_TRY_P(ctx->d_prop_d.reserve(db.size(), false));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_i.p, ib.data(), ib.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_d.p, db.data(), db.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(ctx->d_prop_fast_i.reserve(fast_i.size(), false));
-    HIP_TRY_P(ctx->d_prop_fast_d.reserve(fast_d.size(), false));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_fast_i.p, fast_i.data(), fast_i.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_fast_d.p, fast_d.data(), fast_d.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(hipStreamSynchronize(st));
+    HIP_TRY(ctx->d_prop_i.reserve(ib.size(), false));
+    HIP_TRY(ctx->d_prop_d.reserve(db.size(), false));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_i.p, ib.data(), ib.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_d.p, db.data(), db.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx->d_prop_fast_i.reserve(fast_i.size(), false));
+    HIP_TRY(ctx->d_prop_fast_d.reserve(fast_d.size(), false));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_fast_i.p, fast_i.data(), fast_i.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_fast_d.p, fast_d.data(), fast_d.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     ctx->prop_fast = fast_ok;
     ctx->prop_ns = ns;
     ctx->prop_nr = nr;
@@ -231,15 +223,15 @@ int prop_set_tables2(kfsp_ctx *ctx, int32_t nr, const int32_t *s1, const int32_t
     }
     if (!any) return 0;
     hipStream_t st = ctx->stream;
-    HIP_TRY_P(ctx->d_prop_t2i.reserve(ti.size(), false));
-    HIP_TRY_P(ctx->d_prop_t2o.reserve(to.size(), false));
-    HIP_TRY_P(ctx->d_prop_t2d.reserve((size_t)std::max<int64_t>(len, 1), false));
-    HIP_TRY_P(ctx->d_prop_oob.reserve(32, false));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_t2i.p, ti.data(), ti.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_t2o.p, to.data(), to.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(hipMemcpyAsync(ctx->d_prop_t2d.p, tab2, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY_P(hipMemsetAsync(ctx->d_prop_oob.p, 0, 32 * sizeof(int32_t), st));
-    HIP_TRY_P(hipStreamSynchronize(st));
+    HIP_TRY(ctx->d_prop_t2i.reserve(ti.size(), false));
+    HIP_TRY(ctx->d_prop_t2o.reserve(to.size(), false));
+    HIP_TRY(ctx->d_prop_t2d.reserve((size_t)std::max<int64_t>(len, 1), false));
+    HIP_TRY(ctx->d_prop_oob.reserve(32, false));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_t2i.p, ti.data(), ti.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_t2o.p, to.data(), to.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->d_prop_t2d.p, tab2, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ctx->d_prop_oob.p, 0, 32 * sizeof(int32_t), st));
+    HIP_TRY(hipStreamSynchronize(st));
     ctx->prop_has_tab2 = true;
     return 0;
 }
@@ -249,11 +241,11 @@ int prop_check_overflow(kfsp_ctx *ctx)
     if (!ctx->prop_has_tab2) return 0;
     int32_t h[17];
     hipStream_t st = ctx->stream;
-    HIP_TRY_P(hipMemcpyAsync(h, ctx->d_prop_oob.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY_P(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_prop_oob.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (!h[0]) return 0;
     std::memcpy(ctx->prop_missed, h + 1, sizeof(ctx->prop_missed));
-    HIP_TRY_P(hipMemsetAsync(ctx->d_prop_oob.p, 0, 32 * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(ctx->d_prop_oob.p, 0, 32 * sizeof(int32_t), st));
     ctx->err = "a population lies beyond a two-species propensity table (kfsp_propensity_overflow says which; enlarge and repeat)";
     return -16;
 }
@@ -272,16 +264,16 @@ int prop_eval_host(kfsp_ctx *ctx, int32_t n, const int32_t *state, int32_t lds, 
 {
     hipStream_t st = ctx->stream;
     const size_t ns_b = (size_t)n * (size_t)lds * 4, no_b = (size_t)n * (size_t)ldo * 8, nd_b = (size_t)n * 8;
-    HIP_TRY_P(ctx->d_os1.reserve(ns_b + no_b + nd_b + 1024, false));
+    HIP_TRY(ctx->d_os1.reserve(ns_b + no_b + nd_b + 1024, false));
     char *base = ctx->d_os1.p;
     double *d_off = reinterpret_cast<double *>(base);
     double *d_diag = reinterpret_cast<double *>(base + no_b);
     int32_t *d_state = reinterpret_cast<int32_t *>(base + no_b + nd_b);
-    HIP_TRY_P(hipMemcpyAsync(d_state, state, ns_b, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_state, state, ns_b, hipMemcpyHostToDevice, st));
     if (int rc = prop_eval_device(ctx, n, d_state, lds, d_off, ldo, d_diag)) return rc;
-    HIP_TRY_P(hipMemcpyAsync(offdiag, d_off, no_b, hipMemcpyDeviceToHost, st));
-    HIP_TRY_P(hipMemcpyAsync(diag, d_diag, nd_b, hipMemcpyDeviceToHost, st));
-    HIP_TRY_P(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(offdiag, d_off, no_b, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(diag, d_diag, nd_b, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return prop_check_overflow(ctx);
 }
 

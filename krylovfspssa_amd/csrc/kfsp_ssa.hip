@@ -20,6 +20,7 @@
 // index (the set of survivors does not depend on the order of the insertions).
 #include "kfsp_prop_dev.h"
 #include "kfsp_hash_dev.h"
+#include "kfsp_host.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -659,15 +660,6 @@ struct Arena {
 
 }  // namespace
 
-#define SSA_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return 1000 + (int)e_;                                                         \
-        }                                                                                  \
-    } while (0)
-
 void launch_table_build64(int n, int ns, int lds, const int32_t *state, unsigned long long *tab, unsigned mask, unsigned *bitmap, unsigned bmask,
                           hipStream_t st)
 {
@@ -701,16 +693,16 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
     const unsigned bwords = slots / 8;
     const bool filter = fast && ctx->opt_ssa_filter != 0;
     const size_t need1 = (size_t)nr * ns * 4 + (size_t)slots * 8 + (size_t)bwords * 4 + 4096;
-    SSA_TRY(ctx->d_os2.reserve(need1, false));
+    HIP_TRY(ctx->d_os2.reserve(need1, false));
     Arena a1{ctx->d_os2.p};
     int32_t *d_nu = a1.take<int32_t>((size_t)nr * ns);
     unsigned long long *d_tab64 = a1.take<unsigned long long>(slots);
     unsigned *d_bitmap = a1.take<unsigned>(bwords);
     int32_t *d_tab = reinterpret_cast<int32_t *>(d_tab64);
     unsigned long long *d_total = a1.take<unsigned long long>(2);
-    SSA_TRY(hipMemcpyAsync(d_nu, stoich, (size_t)nr * ns * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_nu, stoich, (size_t)nr * ns * 4, hipMemcpyHostToDevice, st));
     // (table and filter are neighbours in the arena: one memset)
-    SSA_TRY(hipMemsetAsync(d_tab64, 0, fast ? (size_t)((char *)(d_bitmap + bwords) - (char *)d_tab64) : (size_t)slots * 4, st));
+    HIP_TRY(hipMemsetAsync(d_tab64, 0, fast ? (size_t)((char *)(d_bitmap + bwords) - (char *)d_tab64) : (size_t)slots * 4, st));
     if (fast) {
         launch_table_build64(n, ns, lds, d_state, d_tab64, slots - 1, filter ? d_bitmap : (unsigned *)nullptr, bwords - 1, st);
     } else {
@@ -753,12 +745,12 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
     unsigned long long *d_keys = nullptr;
     int32_t *d_rec = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        SSA_TRY(ctx->d_os4.reserve((size_t)cap * 8 + (size_t)cap * ns * 4 + 1024, false));
+        HIP_TRY(ctx->d_os4.reserve((size_t)cap * 8 + (size_t)cap * ns * 4 + 1024, false));
         Arena a2{ctx->d_os4.p};
         d_keys = a2.take<unsigned long long>((size_t)cap);
         d_rec = a2.take<int32_t>((size_t)cap * ns);
-        SSA_TRY(hipMemsetAsync(d_total, 0, 2 * sizeof(unsigned long long), st));
-        SSA_TRY(hipMemsetAsync(d_keys, 0xff, (size_t)cap * 8, st));
+        HIP_TRY(hipMemsetAsync(d_total, 0, 2 * sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(d_keys, 0xff, (size_t)cap * 8, st));
         // (the program's library functions, if any, sit behind tables that cover every population a legal state can have)
         const bool light = (ctx->prop_light || (ctx->prop_light_tab && ctx->prop_tab_len > max_count)) && ctx->prop_ncode <= kSsaLdsCode &&
                            ctx->prop_nimm <= kSsaLdsDbl && ctx->prop_np <= kSsaLdsDbl;
@@ -784,8 +776,8 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
         else
             hipLaunchKernelGGL(k_ssa_walk_any, dim3(wgrid), dim3(kBlock), 0, st, A, d_total, cap, d_keys, d_rec);
         unsigned long long got[2] = {0, 0};
-        SSA_TRY(hipMemcpyAsync(got, d_total, sizeof(got), hipMemcpyDeviceToHost, st));
-        SSA_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(got, d_total, sizeof(got), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         int over = prop_check_overflow(ctx);                        // (a path left a two-species table: nothing was changed)
         if (over && over != -16) return over;
         nrec = (long long)got[0];                                   // slots taken (empty ones included)
@@ -794,16 +786,16 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
             // what every rank must agree on before the next collective: the largest slot count (the list's size, and the
             // length of the pieces gathered below), the records in all, and whether ANY rank's paths left a table
             const int P = ctx->nranks;
-            SSA_TRY(ctx->d_os1.reserve((size_t)(P + 1) * 20 * sizeof(double) + 256, false));
+            HIP_TRY(ctx->d_os1.reserve((size_t)(P + 1) * 20 * sizeof(double) + 256, false));
             double *d_s = reinterpret_cast<double *>(ctx->d_os1.p), *d_r = d_s + 20, hs[20], hr[64 * 20];
             hs[0] = (double)nrec;
             hs[1] = (double)nvalid;
             hs[2] = over ? 1.0 : 0.0;
             for (int s_ = 0; s_ < 16; ++s_) hs[3 + s_] = over ? (double)ctx->prop_missed[s_] : 0.0;
-            SSA_TRY(hipMemcpyAsync(d_s, hs, sizeof(hs), hipMemcpyHostToDevice, st));
-            if (int rc = comm_gather_doubles(ctx, d_s, d_r, 20, st)) return rc;
-            SSA_TRY(hipMemcpyAsync(hr, d_r, (size_t)P * 20 * sizeof(double), hipMemcpyDeviceToHost, st));
-            SSA_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(d_s, hs, sizeof(hs), hipMemcpyHostToDevice, st));
+            if (int rc = comm_allgather(ctx, d_s, d_r, 20, st)) return rc;
+            HIP_TRY(hipMemcpyAsync(hr, d_r, (size_t)P * 20 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             long long maxrec = 0, sumvalid = 0;
             bool any_over = false;
             for (int p = 0; p < P; ++p) {
@@ -830,13 +822,13 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
             }
             // the pieces: maxrec slots of every rank (slots a rank did not take keep the empty key), rank after rank
             const long long tot = maxrec * P;
-            SSA_TRY(ctx->d_os5.reserve((size_t)tot * 8 + (size_t)tot * ns * 4 + 1024, false));
+            HIP_TRY(ctx->d_os5.reserve((size_t)tot * 8 + (size_t)tot * ns * 4 + 1024, false));
             Arena a5{ctx->d_os5.p};
             unsigned long long *d_keys_all = a5.take<unsigned long long>((size_t)tot);
             int32_t *d_rec_all = a5.take<int32_t>((size_t)tot * ns);
             if (maxrec > 0) {
-                if (int rc = comm_gather_bytes(ctx, d_keys, d_keys_all, (size_t)maxrec * 8, st)) return rc;
-                if (int rc = comm_gather_bytes(ctx, d_rec, d_rec_all, (size_t)maxrec * ns * 4, st)) return rc;
+                if (int rc = comm_allgather_bytes(ctx, d_keys, d_keys_all, (size_t)maxrec * 8, st)) return rc;
+                if (int rc = comm_allgather_bytes(ctx, d_rec, d_rec_all, (size_t)maxrec * ns * 4, st)) return rc;
             }
             d_keys = d_keys_all;
             d_rec = d_rec_all;
@@ -860,7 +852,7 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
     unsigned slots2 = 64;
     while (slots2 < 2u * (unsigned)nvalid) slots2 <<= 1;
     const size_t need3 = (size_t)nrec * (8 + 4 + 4) + (size_t)nvalid * (4 + 1) + (size_t)slots2 * 8 + 4096 + 10 * 256;
-    SSA_TRY(ctx->d_os3.reserve(need3, false));
+    HIP_TRY(ctx->d_os3.reserve(need3, false));
     Arena a3x{ctx->d_os3.p};
     unsigned long long *d_keys2 = a3x.take<unsigned long long>((size_t)nrec);
     int32_t *d_iota = a3x.take<int32_t>((size_t)nrec), *d_perm = a3x.take<int32_t>((size_t)nrec), *d_sel = a3x.take<int32_t>((size_t)nvalid);
@@ -869,27 +861,27 @@ int ssa_streams_core(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, i
     int *d_nsel = a3x.take<int>(4);
     hipLaunchKernelGGL(k_iota, dim3(blocks(nrec)), dim3(kBlock), 0, st, nrec, d_iota);
     size_t tmp_bytes = 0;
-    SSA_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_iota, d_perm, (int)nrec, 0, 31 + kSsaPosBits, st));
-    SSA_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-    SSA_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, d_keys, d_keys2, d_iota, d_perm, (int)nrec, 0, 31 + kSsaPosBits, st));
-    SSA_TRY(hipMemsetAsync(d_tab2, 0, (size_t)slots2 * 4, st));
-    SSA_TRY(hipMemsetAsync(d_min, 0x7f, (size_t)slots2 * 4, st));
-    SSA_TRY(hipMemsetAsync(d_first, 0, (size_t)nvalid, st));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_iota, d_perm, (int)nrec, 0, 31 + kSsaPosBits, st));
+    HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, d_keys, d_keys2, d_iota, d_perm, (int)nrec, 0, 31 + kSsaPosBits, st));
+    HIP_TRY(hipMemsetAsync(d_tab2, 0, (size_t)slots2 * 4, st));
+    HIP_TRY(hipMemsetAsync(d_min, 0x7f, (size_t)slots2 * 4, st));
+    HIP_TRY(hipMemsetAsync(d_first, 0, (size_t)nvalid, st));
     hipLaunchKernelGGL(k_rec_insert, dim3(blocks(nvalid)), dim3(kBlock), 0, st, nvalid, ns, d_rec, d_perm, d_tab2, d_min, slots2 - 1);
     hipLaunchKernelGGL(k_rec_first, dim3(blocks(slots2)), dim3(kBlock), 0, st, slots2, d_tab2, d_min, d_first);
-    SSA_TRY(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, d_iota, d_first, d_sel, d_nsel, (int)nvalid, st));
-    SSA_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-    SSA_TRY(hipcub::DeviceSelect::Flagged(ctx->d_sorttmp.p, tmp_bytes, d_iota, d_first, d_sel, d_nsel, (int)nvalid, st));
+    HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, d_iota, d_first, d_sel, d_nsel, (int)nvalid, st));
+    HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+    HIP_TRY(hipcub::DeviceSelect::Flagged(ctx->d_sorttmp.p, tmp_bytes, d_iota, d_first, d_sel, d_nsel, (int)nvalid, st));
     int nnew = 0;
-    SSA_TRY(hipMemcpyAsync(&nnew, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
-    SSA_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&nnew, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (nnew > cap_new) {
         ctx->err = "FSP SIZE EXCEEDS MEMORY LIMIT";
         return -11;
     }
     // the new states in (seed state, position on the path) order of their first occurrence, and their columns
     const size_t sb = (size_t)nnew * lds * 4;
-    SSA_TRY(ctx->d_pstage.reserve(((size_t)nnew * ldo + (size_t)nnew + (sb + 7) / 8) + 256, false));
+    HIP_TRY(ctx->d_pstage.reserve(((size_t)nnew * ldo + (size_t)nnew + (sb + 7) / 8) + 256, false));
     double *d_on = ctx->d_pstage.p, *d_dn = d_on + (size_t)nnew * ldo;
     int32_t *d_sn = reinterpret_cast<int32_t *>(d_dn + nnew);
     hipLaunchKernelGGL(k_rec_gather, dim3(blocks(nnew)), dim3(kBlock), 0, st, nnew, ns, lds, d_sel, d_perm, d_rec, d_sn);
@@ -914,21 +906,21 @@ int ssa_streams_device(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns,
     const bool res_gen = ctx->opt_ssa_resident != 0 && ctx->ell_cols == n && ctx->ell_ld == lda;
     const bool res_st = ctx->opt_ssa_resident != 0 && ctx->coords_n == n && ctx->coords_ld == lds;
     const size_t need1 = (res_st ? 0 : (size_t)n * lds * 4) + (res_gen ? 0 : (size_t)n * lda * 12 + (size_t)n * 8) + 4096;
-    SSA_TRY(ctx->d_os1.reserve(need1, false));
+    HIP_TRY(ctx->d_os1.reserve(need1, false));
     Arena a1{ctx->d_os1.p};
     const int32_t *d_state = ctx->d_coords.p, *d_adj = ctx->d_ell_adj.p;
     const double *d_off = ctx->d_ell_off.p, *d_diag = ctx->d_ell_diag.p;
     if (!res_st) {
         int32_t *p = a1.take<int32_t>((size_t)n * lds);
-        SSA_TRY(hipMemcpyAsync(p, state, (size_t)n * lds * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(p, state, (size_t)n * lds * 4, hipMemcpyHostToDevice, st));
         d_state = p;
     }
     if (!res_gen) {
         int32_t *pa = a1.take<int32_t>((size_t)n * lda);
         double *po = a1.take<double>((size_t)n * lda), *pd = a1.take<double>((size_t)n);
-        SSA_TRY(hipMemcpyAsync(pa, adj, (size_t)n * lda * 4, hipMemcpyHostToDevice, st));
-        SSA_TRY(hipMemcpyAsync(po, offdiag, (size_t)n * lda * 8, hipMemcpyHostToDevice, st));
-        SSA_TRY(hipMemcpyAsync(pd, diag, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pa, adj, (size_t)n * lda * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(po, offdiag, (size_t)n * lda * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pd, diag, (size_t)n * 8, hipMemcpyHostToDevice, st));
         d_adj = pa;
         d_off = po;
         d_diag = pd;
@@ -940,10 +932,10 @@ int ssa_streams_device(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns,
                                   ldo, &nnew, &d_sn, &d_on, &d_dn))
         return rc;
     if (nnew == 0) return 0;
-    SSA_TRY(hipMemcpyAsync(state_new, d_sn, (size_t)nnew * lds * 4, hipMemcpyDeviceToHost, st));
-    SSA_TRY(hipMemcpyAsync(off_new, d_on, (size_t)nnew * ldo * 8, hipMemcpyDeviceToHost, st));
-    SSA_TRY(hipMemcpyAsync(diag_new, d_dn, (size_t)nnew * 8, hipMemcpyDeviceToHost, st));
-    SSA_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(state_new, d_sn, (size_t)nnew * lds * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(off_new, d_on, (size_t)nnew * ldo * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(diag_new, d_dn, (size_t)nnew * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *n_found = nnew;
     return 0;
 }

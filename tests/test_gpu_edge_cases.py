@@ -279,3 +279,30 @@ def test_random_banded_generators(ctx, seed):
         assert np.all(np.abs(out[fmt] - ref) <= 1e-13 * mag + 1e-300)
     ctx.set_option("format", 0)
     assert np.array_equal(out[0], out[1])
+
+
+def test_grid_blocks_beyond_a_partial_slot_is_clamped():
+    """Option grid_blocks above 2048 must not let a fused-reduction product write its block partials past its slot of
+    2048 doubles.  A SELL generator of 8208 chunks (> 4 * 2048 trips) asks for 2056 workgroups when the option allows
+    them; with grid_blocks = 4096 and with grid_blocks = 2048 the product runs the same 2048 workgroups, so the partial
+    sums are the same sums: H and basis column 2 of one Arnoldi pass are bitwise equal."""
+    from krylovfspssa_amd import KfspContext, synth
+    mdl = synth.toggle(1024, 513)
+    adj, off, diag = mdl.ell()
+    p0 = synth.poisson_p0(mdl, 20.0)
+    out = {}
+    with KfspContext(0) as c:
+        c.set_option("format", 1)                    # stays SELL: a trip is one 64-row chunk
+        c.set_matrix_ell(adj, off, diag)
+        info = c.layout_info()
+        assert info["format"] in (0, 5) and info["chunks"] == 8208
+        for grid in (4096, 2048):
+            c.set_option("grid_blocks", grid)
+            c.set_vector(p0)
+            c.begin_step()
+            H, mb, k1, av = c.arnoldi(2)
+            out[grid] = (H.copy(), mb, k1, av, c.get_basis(2))
+    a, b = out[4096], out[2048]
+    assert np.isfinite(a[0]).all() and a[0][1, 0] > 0.0
+    assert np.array_equal(a[0], b[0]) and a[1:4] == b[1:4]
+    assert np.array_equal(a[4], b[4])
