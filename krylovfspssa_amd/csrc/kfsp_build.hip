@@ -31,6 +31,7 @@ struct ScanOut {            // device scratch, one instance
     unsigned long long dcount[kMaxBw];   // valid links with the target in this rank's rows
     unsigned long long nnz_off;          // off-diagonal entries of the local rows
     int bad;                // an ADJ entry exceeded n
+    int over;               // a SELL chunk ends beyond the reserved entries: it was left unwritten (k_sell_init / k_sell_fill)
 };
 
 __device__ __forceinline__ int wave_min_i(int v)
@@ -331,30 +332,36 @@ __global__ __launch_bounds__(1024) void k_scan_offsets(int64_t nchunks, int64_t 
     }
 }
 
-// padded slots: val = 0, column = the row itself (always a valid gather)
+// padded slots: val = 0, column = the row itself (always a valid gather).  cap = the entries col / val were reserved for:
+// the speculative rebuild sizes them before it knows the slot count, so a chunk that ends beyond cap is left unwritten -
+// by this kernel, by k_sell_fill and by the row sort - and *over tells the host that the build is to be repeated.
 __global__ __launch_bounds__(kBlock) void k_sell_init(int64_t nchunks, int64_t nloc, int64_t row0,
-                                                      const int64_t *__restrict__ off, int32_t *__restrict__ col,
+                                                      const int64_t *__restrict__ off, int64_t cap, int32_t *__restrict__ col,
                                                       double *__restrict__ val, const double *__restrict__ diag_in,
-                                                      double *__restrict__ diag_out)
+                                                      double *__restrict__ diag_out, int *__restrict__ over)
 {
     const int lane = threadIdx.x & 63;
     const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= nchunks) return;
     const int64_t o = off[c];
-    const int w = (int)((off[c + 1] - o) >> 6);
     const int64_t r = c * kChunk + lane;
+    diag_out[r] = r < nloc ? diag_in[row0 + r] : 0.0;
+    if (off[c + 1] > cap) {
+        if (lane == 0) *over = 1;
+        return;
+    }
+    const int w = (int)((off[c + 1] - o) >> 6);
     const int64_t rr = r < nloc ? r : (nloc > 0 ? nloc - 1 : 0);
     for (int k = 0; k < w; ++k) {
         col[sell_pos(o, w, k, lane)] = (int32_t)(row0 + rr);
         val[sell_pos(o, w, k, lane)] = 0.0;
     }
-    diag_out[r] = r < nloc ? diag_in[row0 + r] : 0.0;
 }
 
 __global__ __launch_bounds__(kBlock) void k_sell_fill(int64_t n, int bw, int ld, const int32_t *__restrict__ adj,
                                                       const double *__restrict__ offd, int64_t row0, int64_t nloc,
-                                                      const int64_t *__restrict__ off, int32_t *__restrict__ ticket,
-                                                      int32_t *__restrict__ col, double *__restrict__ val)
+                                                      const int64_t *__restrict__ off, int64_t cap, int32_t *__restrict__ ticket,
+                                                      int32_t *__restrict__ col, double *__restrict__ val, int *__restrict__ over)
 {
     // one lane per entry of the reference arrays (consecutive lanes, consecutive words)
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -365,9 +372,13 @@ __global__ __launch_bounds__(kBlock) void k_sell_fill(int64_t n, int bw, int ld,
     if (k < 1) return;
     const int64_t r = (int64_t)k - 1 - row0;
     if (r < 0 || r >= nloc) return;
+    const int64_t o = off[r >> 6], o1 = off[(r >> 6) + 1];
+    if (o1 > cap) {                                        // (not reserved: see k_sell_init)
+        *over = 1;
+        return;
+    }
     const int p = atomicAdd(&ticket[r], 1);
-    const int64_t o = off[r >> 6];
-    const int64_t pos = sell_pos(o, (int)((off[(r >> 6) + 1] - o) >> 6), p, (int)(r & 63));
+    const int64_t pos = sell_pos(o, (int)((o1 - o) >> 6), p, (int)(r & 63));
     col[pos] = (int32_t)i;
     val[pos] = offd[e];
 }
@@ -376,18 +387,12 @@ __global__ __launch_bounds__(kBlock) void k_sell_fill(int64_t n, int bw, int ld,
 // in which the reference's scatter loop adds them.  Under the internal state order the key is the
 // CALLER's index of the source (perm: internal -> caller), so that a row is summed in FMATVEC's
 // order (KrylovSolver.f90:598-604) whatever order the device keeps the states in.
-__global__ __launch_bounds__(kBlock) void k_sell_sort_rows(int64_t nloc, const int32_t *__restrict__ cnt,
-                                                           const int64_t *__restrict__ off, int32_t *__restrict__ col,
-                                                           double *__restrict__ val, const int32_t *__restrict__ perm)
+// Entries of equal key and value keep the order they were found in (stable): such entries are the same
+// operand twice, so the sum does not depend on which ticket each of them drew.
+__device__ __forceinline__ void sell_insertion_sort_row(int m, int64_t o, int w, int l, int32_t *__restrict__ col,
+                                                        double *__restrict__ val, const int32_t *__restrict__ perm)
 {
-    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (r >= nloc) return;
-    const int m = cnt[r];
-    if (m < 2) return;
-    const int64_t o = off[r >> 6];
-    const int w = (int)((off[(r >> 6) + 1] - o) >> 6);
-    const int l = (int)(r & 63);
-    for (int a = 1; a < m; ++a) {                          // insertion sort, m <= #reactions
+    for (int a = 1; a < m; ++a) {                          // m = the row's in-degree
         const int32_t ca = col[sell_pos(o, w, a, l)];
         const double va = val[sell_pos(o, w, a, l)];
         const int32_t ka = perm ? perm[ca] : ca;
@@ -406,23 +411,45 @@ __global__ __launch_bounds__(kBlock) void k_sell_sort_rows(int64_t nloc, const i
     }
 }
 
-// The same order for rows of at most CAP entries, from registers: every entry is read once, ranked against the others
-// (rank = how many entries sort before it under the insertion sort's rule - key, then value, then position: a stable
-// ascending order, so the result is the insertion sort's, entry for entry) and written once to its place.  The insertion
-// sort re-reads and re-writes the row from memory for every entry it places (96 us for the 10^6 rows of the Goutsias run,
-// the longest kernel of a rebuild); loops over CAP are unrolled so nothing is indexed dynamically.
-template <int CAP>
-__global__ __launch_bounds__(kBlock) void k_sell_rank_rows(int64_t nloc, const int32_t *__restrict__ cnt,
-                                                           const int64_t *__restrict__ off, int32_t *__restrict__ col,
+// (cap: a chunk that ends beyond the reserved entries was never written - k_sell_init - and is not read here)
+__global__ __launch_bounds__(kBlock) void k_sell_sort_rows(int64_t nloc, const int32_t *__restrict__ cnt,
+                                                           const int64_t *__restrict__ off, int64_t cap, int32_t *__restrict__ col,
                                                            double *__restrict__ val, const int32_t *__restrict__ perm)
 {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= nloc) return;
     const int m = cnt[r];
     if (m < 2) return;
-    const int64_t o = off[r >> 6];
-    const int w = (int)((off[(r >> 6) + 1] - o) >> 6);
+    const int64_t o = off[r >> 6], o1 = off[(r >> 6) + 1];
+    if (o1 > cap) return;
+    sell_insertion_sort_row(m, o, (int)((o1 - o) >> 6), (int)(r & 63), col, val, perm);
+}
+
+// The same order for rows of at most CAP entries, from registers: every entry is read once, ranked against the others
+// (rank = how many entries sort before it under the insertion sort's rule - key, then value, then position: a stable
+// ascending order, so the result is the insertion sort's, entry for entry) and written once to its place.  The insertion
+// sort re-reads and re-writes the row from memory for every entry it places (96 us for the 10^6 rows of the Goutsias run,
+// the longest kernel of a rebuild); loops over CAP are unrolled so nothing is indexed dynamically.
+// A row of MORE than CAP entries - none in an FSP, where a row has one link per reaction at most, any number in a general
+// upload, where a row's length is its in-degree - takes the insertion sort, all of it: ranking its first CAP entries only
+// would leave the others where their tickets put them, in an order that changes from build to build.
+template <int CAP>
+__global__ __launch_bounds__(kBlock) void k_sell_rank_rows(int64_t nloc, const int32_t *__restrict__ cnt,
+                                                           const int64_t *__restrict__ off, int64_t cap, int32_t *__restrict__ col,
+                                                           double *__restrict__ val, const int32_t *__restrict__ perm)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= nloc) return;
+    const int m = cnt[r];
+    if (m < 2) return;
+    const int64_t o = off[r >> 6], o1 = off[(r >> 6) + 1];
+    if (o1 > cap) return;
+    const int w = (int)((o1 - o) >> 6);
     const int l = (int)(r & 63);
+    if (m > CAP) {
+        sell_insertion_sort_row(m, o, w, l, col, val, perm);
+        return;
+    }
     int32_t c[CAP], k[CAP];
     double v[CAP];
 #pragma unroll
@@ -455,20 +482,20 @@ __global__ __launch_bounds__(kBlock) void k_sell_rank_rows(int64_t nloc, const i
     }
 }
 
-void launch_sell_sort_rows(kfsp_ctx *ctx, int64_t nloc, int bw, hipStream_t st)
+void launch_sell_sort_rows(kfsp_ctx *ctx, int64_t nloc, int bw, int64_t cap, hipStream_t st)
 {
     if (nloc < 1) return;
     const dim3 grid((int)((nloc + kBlock - 1) / kBlock)), block(kBlock);
     const int32_t *perm = ctx->perm_on ? ctx->d_perm.p : (const int32_t *)nullptr;
-    // (a row holds at most one entry per reaction)
+    // (a row of an FSP holds at most one entry per reaction; longer rows are sorted by the kernel's own fallback)
     if (bw <= 8 && ctx->opt_build_speculate)
-        hipLaunchKernelGGL(k_sell_rank_rows<8>, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, perm);
+        hipLaunchKernelGGL(k_sell_rank_rows<8>, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, cap, ctx->d_col.p, ctx->d_val.p, perm);
     else if (bw <= 12 && ctx->opt_build_speculate)
-        hipLaunchKernelGGL(k_sell_rank_rows<12>, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, perm);
+        hipLaunchKernelGGL(k_sell_rank_rows<12>, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, cap, ctx->d_col.p, ctx->d_val.p, perm);
     else if (bw <= 16 && ctx->opt_build_speculate)
-        hipLaunchKernelGGL(k_sell_rank_rows<16>, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, perm);
+        hipLaunchKernelGGL(k_sell_rank_rows<16>, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, cap, ctx->d_col.p, ctx->d_val.p, perm);
     else
-        hipLaunchKernelGGL(k_sell_sort_rows, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, perm);
+        hipLaunchKernelGGL(k_sell_sort_rows, grid, block, 0, st, nloc, ctx->d_cnt.p, ctx->d_off.p, cap, ctx->d_col.p, ctx->d_val.p, perm);
 }
 
 // SELL-sigma: inside windows of `sigma` rows of the internal order, the longest rows first (stable), so
@@ -570,6 +597,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         }
         init.nnz_off = 0;
         init.bad = 0;
+        init.over = 0;
         ctx->h_build_ready = true;
     }
     HIP_TRY(hipMemcpyAsync(ctx->d_scan.p, &init, sizeof(init), hipMemcpyHostToDevice, st));
@@ -581,8 +609,8 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
                       !(ctx->perm_on && ctx->opt_sell_sigma >= 128) && (double)nact * (double)bw * 12.0 <= 16e9;
     ScanOut res_stack;
     ScanOut &res = spec ? *reinterpret_cast<ScanOut *>(ctx->h_build + kHbStats) : res_stack;
-    HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
-    if (!spec) {
+    if (!spec) {                                           // (the speculative build copies them when fill and sort have had their say)
+        HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (!state_order_check(ctx)) return kRedoBuild;
         if (res.bad) {
@@ -629,11 +657,15 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_off.p);
         int64_t *hslots = reinterpret_cast<int64_t *>(ctx->h_build + kHbSlots);
         HIP_TRY(hipMemcpyAsync(hslots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        // (bound holds for an FSP; a general generator has rows of any in-degree and may need more: nothing is stored
+        // beyond it, and the flag sends such a build to the slow path, which sizes the arrays by the slot count)
         hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0, ctx->d_off.p,
-                           ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p);
+                           bound, ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p, &dscan->over);
         hipLaunchKernelGGL(k_sell_fill, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
-                           (int)bw, (int)ld, ell_adj, ell_off, row0, nloc, ctx->d_off.p, ctx->d_ticket.p, ctx->d_col.p, ctx->d_val.p);
-        launch_sell_sort_rows(ctx, nloc, bw, st);
+                           (int)bw, (int)ld, ell_adj, ell_off, row0, nloc, ctx->d_off.p, bound, ctx->d_ticket.p, ctx->d_col.p,
+                           ctx->d_val.p, &dscan->over);
+        launch_sell_sort_rows(ctx, nloc, bw, bound, st);
+        HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         ++ctx->spec_builds;
         if (!state_order_check(ctx)) return kRedoBuild;
@@ -641,6 +673,7 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
             ctx->err = "adj entry exceeds n";
             return -5;
         }
+        if (res.over) return kRedoBuild;                      // (rows longer than the reactions allow: not an FSP's generator)
         std::pair<int, int> dl[kMaxBw];
         int nd = 0;
         if (banded_form(dl, nd)) return kRedoBuild;           // (the slow path would store diagonals: let it)
@@ -742,10 +775,10 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
     HIP_TRY(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
     if (nchunks > 0) {
         hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0,
-                           ctx->d_off.p, ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p);
+                           ctx->d_off.p, slots, ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p, &dscan->over);
         hipLaunchKernelGGL(k_sell_fill, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n, (int)bw, (int)ld, ell_adj,
-                           ell_off, row0, nloc, ctx->d_off.p, ctx->d_ticket.p, ctx->d_col.p, ctx->d_val.p);
-        launch_sell_sort_rows(ctx, nloc, bw, st);
+                           ell_off, row0, nloc, ctx->d_off.p, slots, ctx->d_ticket.p, ctx->d_col.p, ctx->d_val.p, &dscan->over);
+        launch_sell_sort_rows(ctx, nloc, bw, slots, st);
     }
     HIP_TRY(hipStreamSynchronize(st));
     ctx->have_sell = true;

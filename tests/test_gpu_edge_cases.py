@@ -245,11 +245,9 @@ def test_growing_fsp_uploads_only_the_new_propensity_columns(oracle, golden_dir)
         assert np.all(np.abs(c.spmv(x) - yref) <= 1e-13 * scale)
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_random_banded_generators(ctx, seed):
-    """Banded rows with random offsets (odd and even, +-1, some longer than the matrix) and ragged
-    sizes: the banded kernel's paired x gathers at both ends of x (first and last rows, offsets that
-    leave the vector), against numpy; the same rows forced through SELL-64 give the same bits."""
+def _random_banded_csr(seed):
+    """banded rows with random offsets (odd and even, +-1, some longer than the matrix) and a ragged size, as CSR
+    ascending by column: (n, rowptr, col, val, rng) - rng goes on to draw the vector"""
     rng = np.random.default_rng(1000 + seed)
     n = int(rng.integers(130, 5000))
     nd = int(rng.integers(1, 13))
@@ -267,7 +265,15 @@ def test_random_banded_generators(ctx, seed):
     C, V = np.take_along_axis(C, order, 1), np.take_along_axis(V, order, 1)
     valid = C >= 0
     rowptr = np.concatenate(([0], np.cumsum(valid.sum(1)))).astype(np.int64)
-    col, val = C[valid].astype(np.int32), V[valid]
+    return n, rowptr, C[valid].astype(np.int32), V[valid], rng
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_random_banded_generators(ctx, seed):
+    """Banded rows with random offsets (odd and even, +-1, some longer than the matrix) and ragged
+    sizes: the banded kernel's paired x gathers at both ends of x (first and last rows, offsets that
+    leave the vector), against numpy; the same rows forced through SELL-64 give the same bits."""
+    n, rowptr, col, val, rng = _random_banded_csr(seed)
     x = rng.standard_normal(n)
     ref = np.array([val[rowptr[r]:rowptr[r + 1]] @ x[col[rowptr[r]:rowptr[r + 1]]] for r in range(n)])
     mag = np.array([np.abs(val[rowptr[r]:rowptr[r + 1]]) @ np.abs(x[col[rowptr[r]:rowptr[r + 1]]]) for r in range(n)])

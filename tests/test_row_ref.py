@@ -1,0 +1,161 @@
+"""tests/row_ref.py, the plain restatement of one row of the product, checked without a device: against row sums in
+extended precision, against the oracle's product at the tolerance the device tests use - and that every case of
+tests/test_gpu_build_rows.py can tell a wrong order from the right one (a comparison of bits that no wrong order
+would change proves nothing)."""
+import numpy as np
+import pytest
+
+from tests import row_cases as RC
+from tests import row_ref as RR
+
+
+def _changed(case, rows):
+    """rows whose bits change when `rows` are summed instead of the case's"""
+    y = np.array(RR.spmv_exact(rows, case["diag"], case["x"]))
+    return int((RC.bits(y) != RC.bits(case["y"])).sum())
+
+
+def _longdouble(rows, diag, x):
+    ld = np.longdouble
+    y = np.array([sum((ld(v) * ld(x[c]) for c, v in row), ld(0)) - ld(diag[r]) * ld(x[r]) for r, row in enumerate(rows)])
+    mag = np.array([sum(abs(v * x[c]) for c, v in row) + abs(diag[r] * x[r]) for r, row in enumerate(rows)])
+    return y, mag
+
+
+def test_fma_rounds_once():
+    a, b = 1.0 + 2.0 ** -30, 1.0 - 2.0 ** -30           # a * b = 1 - 2^-60: rounds to 1, so a * b - 1 == 0 in two steps
+    assert a * b - 1.0 == 0.0 and RR.fma(a, b, -1.0) == -(2.0 ** -60)
+    assert 0.1 * 10.0 - 1.0 == 0.0 and RR.fma(0.1, 10.0, -1.0) == 2.0 ** -54      # the double 0.1 is 2^-54 / 10 above a tenth
+
+
+def test_rows_are_gathered_in_the_promised_order():
+    # states 1..4; state 3 links twice to state 1 (values 5 and 2), state 2 links to state 1, state 4 to itself
+    adj = [[0, 3], [1, -1], [1, 1], [4, 0]]
+    off = [[9.0, 7.0], [4.0, 9.0], [5.0, 2.0], [6.0, 9.0]]
+    rows = RR.gather_rows(adj, off, [0.0] * 4)
+    assert rows == [[(1, 4.0), (2, 2.0), (2, 5.0)], [], [(0, 7.0)], [(3, 6.0)]]
+    assert RR.gather_rows(adj, off, [0.0] * 4, row0=2, nloc=2) == rows[2:]
+    # equal source and value: the slot decides (shown through the sort key, the pairs are the same)
+    assert RR.gather_rows([[2, 2], [0, 0]], [[3.0, 3.0], [1.0, 1.0]], [0.0, 0.0])[1] == [(0, 3.0), (0, 3.0)]
+    r, d = RR.rows_from_csr(3, [0, 2, 4, 6], [0, 2, 0, 1, 1, 2], [-1.5, 2.0, 3.0, -4.0, 5.0, -6.0])
+    assert r == [[(2, 2.0)], [(0, 3.0)], [(1, 5.0)]] and d == [1.5, 4.0, 6.0]
+    y = RR.spmv_exact(r, d, [1.0, 10.0, 100.0])
+    assert y == [198.5, -37.0, -550.0]
+    assert RR.spmv_exact(r[1:], d[1:], [1.0, 10.0, 100.0], row0=1) == y[1:]
+
+
+@pytest.mark.parametrize("name", list(RC.ELL))
+def test_restatement_against_extended_precision_and_the_oracle(oracle, name):
+    c = RC.ell_case(name)
+    y_ld, mag = _longdouble(c["rows"], c["diag"], c["x"])
+    assert np.all(np.abs(c["y"] - y_ld) <= 1e-15 * mag)
+    A = oracle.EllMatrix(c["adj"], c["off"], c["diag"])
+    assert sum(len(r) for r in c["rows"]) + c["n"] == A.nnz()
+    ref = oracle.spmv_ell(A, c["x"])
+    scale = oracle.spmv_ell(oracle.EllMatrix(c["adj"], np.abs(c["off"]), -np.abs(c["diag"])), np.abs(c["x"]))
+    assert np.all(np.abs(c["y"] - ref) <= 1e-13 * scale + 1e-300)
+    # inputs in the range where nothing is subnormal
+    assert np.abs(c["off"][c["adj"] > 0]).min() * np.abs(c["x"]).min() > 1e-30
+    assert np.abs(c["off"]).max() < 1e3 and np.abs(c["diag"]).max() < 1e3 and np.abs(c["x"]).max() < 1e3
+
+
+@pytest.mark.parametrize("name", RC.CSR)
+def test_restatement_of_csr_rows_against_extended_precision(oracle, name):
+    c = RC.csr_case(name)
+    y_ld, mag = _longdouble(c["rows"], c["diag"], c["x"])
+    assert np.all(np.abs(c["y"] - y_ld) <= 1e-15 * mag)
+    ref = oracle.spmv_csr(c["rowptr"], c["col"], c["val"], c["x"])
+    assert np.all(np.abs(c["y"] - ref) <= 1e-13 * mag + 1e-300)
+
+
+# ---- every device case can fail ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", RC.LONG_ROWS)
+def test_long_row_cases_have_rows_beyond_their_cap_whose_order_shows(name):
+    """>= 20 rows longer than the CAP the slot count selects, and >= 10 of them with other bits when the entries
+    from position CAP on - the ones a sort of the first CAP entries never looks at - come in reverse order"""
+    c = RC.ell_case(name)
+    cap = RC.sort_cap(c["bw"])
+    assert cap is not None
+    long_rows = sum(len(r) > cap for r in c["rows"])
+    changed = _changed(c, RR.reverse_from(c["rows"], cap))
+    print(f"{name}: CAP {cap}, {long_rows} rows longer, longest {max(map(len, c['rows']))}, {changed} change bits")
+    assert long_rows >= 20 and changed >= 10
+    if name == "4097x8":
+        assert (long_rows, changed, max(map(len, c["rows"]))) == (474, 57, 18)
+
+
+def test_the_speculative_bound_is_too_small_for_the_general_generators():
+    """rows x slots, what the speculative rebuild reserves, against the SELL slots (64 x the longest row of every
+    chunk): the rebuild cases go beyond it, so their rebuild has to be repeated the slow way"""
+    for name, want in (("4097x8", (48512, 33280)), ("1000x4", None)):
+        c = RC.ell_case(name)
+        ln = np.array([len(r) for r in c["rows"]] + [0] * (-c["n"] % 64)).reshape(-1, 64)
+        slots, bound = int(ln.max(axis=1).sum()) * 64, ln.size * c["bw"]
+        assert slots > bound
+        if want:
+            assert (slots, bound) == want
+
+
+def test_the_short_and_wide_cases_show_a_reversed_row():
+    """1000 x 4: 140 rows longer than the slot count (none beyond CAP = 8: the case is about the partition and the
+    reserved bound); (65, 20) and (1000, 33): the insertion sort.  A row summed backwards has other bits."""
+    c = RC.ell_case("1000x4")
+    assert sum(len(r) > 4 for r in c["rows"]) == 140 and max(map(len, c["rows"])) <= 8
+    for name in ("1000x4", "65x20", "1000x33"):
+        c = RC.ell_case(name)
+        assert RC.sort_cap(c["bw"]) is None or name == "1000x4"
+        assert _changed(c, RR.reverse_from(c["rows"], 0)) >= 10
+
+
+def test_the_duplicated_links_tie_on_the_key():
+    c = RC.ell_case("duplicated links 600x8")
+    tied = [r for r, row in enumerate(c["rows"]) if any(a[0] == b[0] for a, b in zip(row, row[1:]))]
+    same = [r for r, row in enumerate(c["rows"]) if any(a == b for a, b in zip(row, row[1:]))]
+    assert len(tied) >= 20 and len(same) >= 10
+    # the tie broken the other way (larger value first) shows in the bits
+    other = [sorted(row, key=lambda e: (e[0], -e[1])) for row in c["rows"]]
+    assert _changed(c, other) >= 10
+
+
+@pytest.mark.parametrize("which", ["goutsias", "made up"])
+def test_state_order_cases_show_a_row_summed_in_the_internal_order(which):
+    """the device keeps the states in lexicographic order of their coordinates; a row sorted by THAT numbering
+    instead of the caller's has other bits in >= 10 rows"""
+    c = RC.golden_case() if which == "goutsias" else RC.ell_case("4097x8")
+    state = c["state"] if which == "goutsias" else RC.made_up_coords(c["n"])
+    assert len(np.unique(state, axis=0)) == c["n"]
+    rank = RC.lexicographic_rank(state)
+    assert not np.array_equal(rank, np.arange(c["n"]))
+    internal = [sorted(row, key=lambda e: (rank[e[0]], e[1])) for row in c["rows"]]
+    assert _changed(c, internal) >= 10
+
+
+@pytest.mark.parametrize("name", RC.CSR)
+def test_banded_cases_show_a_reversed_row(name):
+    c = RC.csr_case(name)
+    assert _changed(c, RR.reverse_from(c["rows"], 0)) >= 10
+
+
+def test_partition_blocks_are_blocks_of_the_whole():
+    for name in ("1000x4", "2000x12"):
+        c = RC.ell_case(name)
+        h = c["n"] // 2 + 7
+        rows = RR.gather_rows(c["adj"], c["off"], c["diag"], row0=h, nloc=c["n"] - h)
+        assert rows == c["rows"][h:]
+        assert RR.spmv_exact(rows, c["diag"][h:], c["x"], row0=h) == c["y"][h:].tolist()
+
+
+def test_the_drop_vector_flags_about_a_twentieth_and_leaves_long_rows():
+    c = RC.ell_case("4097x8")
+    n = c["n"]
+    w = RC.drop_vector(c["adj"], n)
+    aw = np.array(RR.spmv_exact(c["rows"], c["diag"], w))
+    assert np.abs(aw - 1e-8).min() > 1e-10                   # no decision hinges on rounding
+    flags = (w < 1e-8) & ~(aw > 1e-8)
+    assert 0.03 * n <= flags.sum() <= 0.08 * n
+    adj2, off2, diag2 = RC.compact(c["adj"], c["off"], c["diag"], ~flags)
+    rows = RR.gather_rows(adj2, off2, diag2)
+    x = c["x"][~flags]
+    y = np.array(RR.spmv_exact(rows, diag2, x))
+    y2 = np.array(RR.spmv_exact(RR.reverse_from(rows, 8), diag2, x))
+    assert sum(len(r) > 8 for r in rows) >= 20 and int((RC.bits(y) != RC.bits(y2)).sum()) >= 10
