@@ -123,18 +123,37 @@ class _Column:
             return (p1 * p2) / (p1 - p2)
         return p1
 
-    def combine(self):
-        """W = max(BETA V(:, 1:MX) exp(t H) e_1, 0) over MX = MBRKDWN + MAX(0, K1 - 1) (:438, :444-449)"""
+    def combine(self, clamp=True):
+        """W = max(BETA V(:, 1:MX) exp(t H) e_1, 0) over MX = MBRKDWN + MAX(0, K1 - 1) (:438, :444-449); clamp=False
+        keeps the signed entries (option block_clamp = 0)"""
         mx = self.mbrk + max(0, self.k1 - 1)
-        return np.maximum(self.beta * (self.V[:, :mx] @ self.E[:mx, 0]), 0.0)
+        w = self.beta * (self.V[:, :mx] @ self.E[:mx, 0])
+        return np.maximum(w, 0.0) if clamp else w
 
 
 def _log(x):
     return math.log(x) if x > 0 else (-math.inf if x == 0 else math.nan)
 
 
-def expv_block(A, W, t, tol, m):
-    """A: oracle.EllMatrix, W: (n, k) start columns -> (W(t) (n, k), wsum[k], BlockStats)"""
+def transpose_ell(adj, off, diag):
+    """A^T in the reference's arrays, for the backward solves (option adjoint).  The arrays are column-oriented: column i
+    of a matrix holds -DIAG(i) and OFFDIAG(:, i) at the rows ADJ(:, i).  Column i of A^T is row i of A, so adj_T[i] =
+    1 + the columns of the off-diagonal entries of row i (ascending by column, then value, then slot: the order of
+    tests/row_ref.py), off_T[i] their values, diag_T = diag; the slot count is the longest row's."""
+    from tests import row_ref
+    rows = row_ref.gather_rows(adj, off, diag)
+    n, bw = len(rows), max(1, max(len(r) for r in rows))
+    adj_t = np.zeros((n, bw), dtype=np.int32)
+    off_t = np.zeros((n, bw))
+    for i, row in enumerate(rows):
+        for j, (c, v) in enumerate(row):
+            adj_t[i, j], off_t[i, j] = c + 1, v
+    return adj_t, off_t, np.array(diag, dtype=np.float64)
+
+
+def expv_block(A, W, t, tol, m, clamp=True):
+    """A: oracle.EllMatrix, W: (n, k) start columns -> (W(t) (n, k), wsum[k], BlockStats).  clamp=False: the combine
+    keeps signed entries and wsum is the l1 norm of the column (option block_clamp = 0: signed observables)"""
     n = A.n
     W = np.array(W, dtype=np.float64, copy=True)
     k = W.shape[1]
@@ -200,8 +219,8 @@ def expv_block(A, W, t, tol, m):
         if err < 1.0e-16:                            # :437
             t_new = max(t_new, 2.0 * t_step)
         for c in live:
-            W[:, c] = cols[c].combine()
-            wsum[c] = W[:, c].sum()                  # DASUM :450 of a clamped column
+            W[:, c] = cols[c].combine(clamp)
+            wsum[c] = W[:, c].sum() if clamp else np.abs(W[:, c]).sum()   # DASUM :450 of a clamped column / the l1 norm
         t_now += t_step
         st.steps.append(t_step)
         if t_now >= t:                               # :503: the last step enters no statistics

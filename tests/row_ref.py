@@ -10,7 +10,11 @@ Python floats (IEEE binary64) and fractions.Fraction for the one rounding of the
 come in as numpy arrays are turned into lists first.
 
 Inputs are expected in roughly [1e-3, 1e3] in magnitude: no product is subnormal there, so the device's handling of
-subnormal numbers cannot enter a comparison."""
+subnormal numbers cannot enter a comparison.
+
+The second half restates one row of the TRANSPOSED block product Y = A^T X (option adjoint) for each of the three forms
+the generator can be resident in, as the header of kfsp_block_adj.hip defines them: banded_t_exact, ell_t_exact,
+box_t_exact.  fma() does not carry the sign of a zero result, so a result that is zero here is compared by value."""
 from fractions import Fraction
 
 
@@ -76,6 +80,100 @@ def spmv_exact(rows, diag, x, row0=0):
             s = fma(v, x[c], s)
         y.append(s)
     return y
+
+
+# ---- the transposed rows (Y = A^T X, option adjoint): the three definitions in the header of kfsp_block_adj.hip -------
+# X is a list of rows (or an (n, k) array), the result a list of n rows of k floats.  `descending` takes the entries in
+# the opposite order and `diag_last` applies the diagonal term after them (fma(-diag, x_r, s) from s = +0.0): two wrong
+# kernels, used to show that a test case can tell them from the right one.  A padded entry - a source outside [0, n), a
+# missing target, a target outside the box - is an fma of 0.0 against the row's own X row, as the kernels do it.
+def _t_row(entries, dg, X, r, descending, diag_last):
+    """entries: [(value, X row)] of row r in the promised order -> the row of k results"""
+    if descending:
+        entries = entries[::-1]
+    out = []
+    for c in range(len(X[r])):
+        s = 0.0 if diag_last else -(dg * X[r][c])
+        for v, src in entries:
+            s = fma(v, X[src][c], s)
+        if diag_last:
+            s = fma(-dg, X[r][c], s)
+        out.append(s)
+    return out
+
+
+def banded_t_exact(delta, val, diag, X, descending=False, diag_last=False):
+    """banded: val[d][r] = A(r, r + delta[d]) as the image stores it.  Row r: s = -(diag[r] x_r), then one fma per
+    diagonal, d ascending, of val[d][r - delta[d]] against X row r - delta[d]"""
+    delta, val, diag, X = _lists(delta), _lists(val), _lists(diag), _lists(X)
+    n = len(diag)
+    Y = []
+    for r in range(n):
+        ent = []
+        for d in range(len(delta)):
+            src = r - delta[d]
+            ent.append((val[d][src], src) if 0 <= src < n else (0.0, r))
+        Y.append(_t_row(ent, diag[r], X, r, descending, diag_last))
+    return Y
+
+
+def ell_t_exact(adj, off, diag, X, descending=False, diag_last=False):
+    """the reference arrays: row c: s = -(diag[c] x_c), then one fma per slot k ascending of off[c][k] against X row
+    adj[c][k] - 1 (a target outside [1, n] is missing)"""
+    adj, off, diag, X = _lists(adj), _lists(off), _lists(diag), _lists(X)
+    n = len(diag)
+    Y = []
+    for c in range(n):
+        ent = [(off[c][k], adj[c][k] - 1) if 1 <= adj[c][k] <= n else (0.0, c) for k in range(len(adj[c]))]
+        Y.append(_t_row(ent, diag[c], X, c, descending, diag_last))
+    return Y
+
+
+def box_slots(mdl):
+    """the slots of a single-factor box in the order the device fills them: [species][slot] -> (reaction, its factor
+    table), the reactions whose propensity depends on the species by ascending source offset (ties: by reaction).  The
+    tables are model.factors()' - the very doubles the device receives."""
+    ndep, dep, tab = mdl.factors()
+    ndep, dep, tab = _lists(ndep), _lists(dep), _lists(tab)
+    assert all(nd == 1 for nd in ndep), "single-factor boxes only"
+    at, tables = 0, []
+    for k in range(mdl.R):
+        tables.append(tab[at:at + mdl.dims[dep[k][0]]])
+        at += mdl.dims[dep[k][0]]
+    order = sorted(range(mdl.R), key=lambda k: (-int(mdl.offsets[k]), k))
+    return [[(k, tables[k]) for k in order if dep[k][0] == s] for s in range(mdl.d)]
+
+
+def box_t_exact(mdl, X, descending=False):
+    """matrix-free box: the accumulator starts at +0.0; by species, then by slot, one fma of a_k(x) - the slot's table
+    at the row's own coordinate - against X row r + delta_k when x + nu_k lies in the box (else 0.0 against the row's
+    own row); then fma(-dsum, x_r, acc), dsum the species' shares (each the sum of its slots' a_k(x) from 0.0, in slot
+    order) added in species order"""
+    X = _lists(X)
+    slots = box_slots(mdl)
+    stoich, offsets, dims, strides = _lists(mdl.stoich), _lists(mdl.offsets), mdl.dims, _lists(mdl.strides)
+    Y = []
+    for r in range(mdl.n):
+        x = [(r // strides[s]) % dims[s] for s in range(mdl.d)]
+        ent, dsum = [], None
+        for s in range(mdl.d):
+            share = 0.0
+            for k, table in slots[s]:
+                a = table[x[s]]
+                share += a
+                inside = all(0 <= x[q] + stoich[q][k] < dims[q] for q in range(mdl.d))
+                ent.append((a, r + offsets[k]) if inside else (0.0, r))
+            dsum = share if dsum is None else dsum + share
+        if descending:
+            ent = ent[::-1]
+        row = []
+        for c in range(len(X[r])):
+            acc = 0.0
+            for a, src in ent:
+                acc = fma(a, X[src][c], acc)
+            row.append(fma(-dsum, X[r][c], acc))
+        Y.append(row)
+    return Y
 
 
 def reverse_from(rows, cap):

@@ -154,3 +154,42 @@ def test_zero_and_absorbing_columns(oracle):
     assert np.abs(R[:, 2] - ref[:, 2]).sum() <= BR.DELTA * 1e-10 * 0.5 * np.sqrt(N)
     Z, wz, sz = BR.expv_block(A, np.zeros((N, 2)), 0.5, 1e-10, 10)
     assert not Z.any() and not wz.any() and (sz.nstep, sz.t_now) == (0, 0.5)
+
+
+def test_transpose_is_the_transpose(oracle):
+    """block_ref.transpose_ell against the dense transpose, entry by entry, on an FSP with links that leave it"""
+    from tests import block_generators
+    from tests.conftest import GOLDEN
+    g = block_generators.golden_toggle(GOLDEN)
+    ell = (g["adj"], g["offdiag"], g["diag"])
+    assert (ell[0] < 1).any()
+    assert np.array_equal(_dense(BR.transpose_ell(*ell)), _dense(ell).T)
+    x = np.random.default_rng(1).standard_normal(len(g["diag"]))
+    assert np.allclose(oracle.spmv_ell(oracle.EllMatrix(*BR.transpose_ell(*ell)), x), _dense(ell).T @ x, rtol=1e-13, atol=1e-13)
+
+
+def test_backward_restatement_matches_dense_expm(oracle):
+    """exp(tA^T) F for signed observables: the restatement on A^T with the clamp off against scipy's dense exponential,
+    at the bound of the device's backward test (tests/test_gpu_block_adjoint.py: backward the roles of l1 and max norm
+    swap, so column c is held to max|R_c - ref_c| <= 10 tol max|F_c|); wsum is the l1 norm; the clamped default would
+    have wiped the negative column out"""
+    from krylovfspssa_amd import synth
+    mdl = synth.toggle(23, 19)
+    t, tol, m = 0.3, 1e-8, 30
+    ell = mdl.ell()
+    x1, x2 = (c.astype(np.float64) for c in mdl.coords(np.arange(mdl.n, dtype=np.int64)))
+    ind = np.zeros(mdl.n)
+    ind[mdl.n // 2 + 3] = 1.0
+    F = np.column_stack([np.ones(mdl.n), x1, x2, x1 * x2, ind, -x1])
+    AT = oracle.EllMatrix(*BR.transpose_ell(*ell))
+    R, ws, st = BR.expv_block(AT, F, t, tol, m, clamp=False)
+    ref = sl.expm(t * _dense(ell)).T @ F
+    assert st.t_now == pytest.approx(t, rel=1e-15) and st.nstep >= 2
+    for c in range(F.shape[1]):
+        err = np.abs(R[:, c] - ref[:, c]).max()
+        print("column", c, "max err", err, "bound", 10 * tol * np.abs(F[:, c]).max())
+        assert err <= 10 * tol * np.abs(F[:, c]).max(), c
+        assert ws[c] == np.abs(R[:, c]).sum()
+    assert np.all(R[:, 5] <= 0.0) and (R[:, 5] < 0.0).any()
+    Rc, wc, _ = BR.expv_block(AT, F, t, tol, m)
+    assert not Rc[:, 5].any() and wc[5] == 0.0 and np.all(Rc >= 0.0)

@@ -5,8 +5,10 @@ would change proves nothing)."""
 import numpy as np
 import pytest
 
+from tests import adjoint_cases as AC
 from tests import row_cases as RC
 from tests import row_ref as RR
+from tests.test_block_adjoint_host import banded_form, banded_t, bound, box_t, ell_t
 
 
 def _changed(case, rows):
@@ -159,3 +161,66 @@ def test_the_drop_vector_flags_about_a_twentieth_and_leaves_long_rows():
     y = np.array(RR.spmv_exact(rows, diag2, x))
     y2 = np.array(RR.spmv_exact(RR.reverse_from(rows, 8), diag2, x))
     assert sum(len(r) > 8 for r in rows) >= 20 and int((RC.bits(y) != RC.bits(y2)).sum()) >= 10
+
+
+# ---- the transposed rows (option adjoint) ---------------------------------------------------------------------------
+def test_transposed_rows_by_hand():
+    X = [[1.0, 0.5], [10.0, 0.25], [100.0, 2.0]]
+    # banded, delta = (-1, 2): A(1, 0) = 2, A(2, 1) = 3 on the first diagonal, A(0, 2) = 4 on the second
+    val = [[9.0, 2.0, 3.0], [4.0, 9.0, 9.0]]
+    Y = RR.banded_t_exact([-1, 2], val, [1.5, 2.5, 3.5], X)
+    assert Y == [[-1.5 + 2.0 * 10.0, -0.75 + 2.0 * 0.25], [-25.0 + 3.0 * 100.0, -0.625 + 3.0 * 2.0], [-350.0 + 4.0, -7.0 + 4.0 * 0.5]]
+    # the same matrix as reference arrays: state 0 -> state 2 (rate 4), state 1 -> 0 (2), state 2 -> 1 (3) and a link outside
+    adj, off = [[3, 0], [-1, 1], [2, 7]], [[4.0, 9.0], [9.0, 2.0], [3.0, 9.0]]
+    Z = RR.ell_t_exact(adj, off, [1.5, 2.5, 3.5], X)
+    assert Z == [[-1.5 + 4.0 * 100.0, -0.75 + 4.0 * 2.0], [-25.0 + 2.0 * 1.0, -0.625 + 2.0 * 0.5], [-350.0 + 3.0 * 10.0, -7.0 + 3.0 * 0.25]]
+    assert np.array_equal(np.array(Z), ell_t(np.array(adj), np.array(off), np.array([1.5, 2.5, 3.5]), np.array(X)))
+    assert RR.ell_t_exact(adj, off, [1.5, 2.5, 3.5], X, diag_last=True) == Z          # exact in both orders at these values
+
+
+@pytest.mark.parametrize("name", AC.CASES)
+def test_transposed_rows_against_the_assembled_transpose_and_can_tell(name):
+    """The exact rows against A^T X of the assembled generator and against the numpy statement of the same row (separate
+    multiply and add) at the bound of the device tests - and the case can tell a wrong kernel: the rows with their
+    entries in descending order, and (banded, ELL) with the diagonal term applied last, differ on the bits from the right
+    ones in at least one row and column.  (No case needed another X or shape for that: with magnitudes over six decades
+    nearly every row of a random column shows either.)"""
+    c = AC.case(name)
+    A, X, Y = c["A"], c["X"], c["Y"]
+    tol = bound(A, X)
+    assert np.all(np.abs(Y - A.T @ X) <= tol)
+    if name in AC.BANDED:
+        mdl = AC.model(name)
+        loose = banded_t(*banded_form(mdl), X)
+        delta = banded_form(mdl)[0]
+        assert delta.min() < 0 < delta.max() and mdl.n % 128 != 0       # sources on both sides, a ragged last group
+    elif name in AC.ELL:
+        adj, off, diag = AC.ell_arrays(name)
+        loose = ell_t(adj, off, diag, X)
+        if name != "ell_coded":
+            assert (adj < 1).any() and len(diag) % 64 != 0
+        if name == "ell_wide":
+            mid = (adj[:, 1] == 0) & (adj[:, 2] > 0)
+            assert mid.sum() >= 10                                      # ADJ = 0 with a link behind it in the row
+    else:
+        loose = box_t(AC.model(name), X)
+    assert np.all(np.abs(Y - loose) <= tol)
+    assert np.abs(X[X != 0.0]).min() >= 1e-3 and np.abs(X).max() <= 1e3 and (X < 0).any() and (X > 0).any()
+    assert np.count_nonzero(X[:, 1]) == 1
+    wrong = {"descending": AC.exact(name, X, descending=True)}
+    if name not in AC.BOXES:
+        wrong["diagonal last"] = AC.exact(name, X, diag_last=True)
+    for what, Z in wrong.items():
+        bad = AC.mismatches(Z, Y)
+        print(f"{name}: {what}: {int(bad.any(axis=1).sum())} of {c['n']} rows change, per column {bad.sum(axis=0).tolist()}")
+        assert bad.any(), (name, what)
+        assert np.all(np.abs(Z - A.T @ X) <= tol)                      # ... and the loose bound passes both
+
+
+def test_the_small_boxes_reach_their_edges():
+    """one box below a wavefront's 64 rows, one with a dimension of 2, one with nu = +-2"""
+    assert AC.model("box_one_species").n < 64
+    assert 2 in AC.model("box_repressilator_3x2").dims
+    assert np.abs(AC.model("box_four_slot_6x4").stoich).max() == 2
+    slots = {name: RR.box_slots(AC.model(name)) for name in AC.BOXES}
+    assert [(len(s), max(map(len, s))) for s in slots.values()] == [(2, 2), (3, 2), (6, 2), (2, 4), (1, 2)]
