@@ -460,7 +460,7 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
 /* exp(tA) W for k start vectors on ONE pass over the generator per product: transition probabilities from several
  * observed states, several initial distributions of one model.  The generator must be a stored one (SELL-64, coded
  * SELL, banded, masked banded): a matrix-free box (kernel formats 3, 4, 6, 7, 8; option box_store = 1 stores it) and a
- * context with a communicator or a group head return -12.
+ * context with a communicator or a group head return -12 (unless option "block_partition" = 1, see ROW PARTITIONS below).
  * Option "block_box" = 1 (default 0) lets the block calls take a MATRIX-FREE box as well: the row of a single-factor box
  * (the form kernel format 4 multiplies with) is rebuilt once and applied to all columns, so a product moves the block
  * alone, and column j of kfsp_spmm is bit-identical to kfsp_spmv of column j on the same context (formats 4 and 7).
@@ -489,9 +489,32 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
  * columns in one block and the Fortran binding are not provided.
  * Option "block_clamp" = 0 (default 1, independent of "adjoint"): kfsp_block_combine and the steps of kfsp_expv_block do
  * not clamp at 0 - W_c = sum_i coef_i u_i from the same chain of fused multiply-adds - and wsum[c] = sum_i |W_ic|: an
- * observable may be signed, and the backward solution of a signed f is no probability vector. */
+ * observable may be signed, and the backward solution of a signed f is no probability vector.
+ * ROW PARTITIONS.  Option "block_partition" = 1 (default 0; read by every block call, forwarded by a group head to its
+ * ranks like any option) lets the block calls run on a context with a communicator (RCCL or loop-back) and on a group
+ * head, for the stored forms (SELL-64, coded SELL, banded, masked banded) and both exchange modes kfsp_layout_info v[1]
+ * reports (halo strips, all-gather of the whole source).  The capability is OPT-IN: with 0 every such context refuses
+ * every block call with -12, as it always has, and callers that rely on that refusal see no change.  Still -12 with 1,
+ * on every rank and before any collective: option "adjoint" (the transposed banded product reads the neighbour's
+ * generator rows, not only its rows of X) and a matrix-free box, with or without "block_box"; "block_small" is simply
+ * not taken.  The conventions are those of kfsp_set_vector / kfsp_spmv:
+ *   On a context with a communicator all ranks call in the same order.  kfsp_set_block / kfsp_get_block: n is this
+ *   rank's nlocal (kfsp_row_block) and W holds the rank's row block of the caller's order, ldw >= n; a null W is
+ *   allowed when nlocal = 0; under the global internal state order every column travels as a vector does in
+ *   kfsp_set_vector / kfsp_get_vector.  kfsp_spmm: X is the WHOLE n x k block in the caller's order on every rank
+ *   (ld >= n), Y the rank's rows in the same ld; no exchange takes place.  kfsp_block_begin / _arnoldi / _combine /
+ *   kfsp_expv_block: every host-visible scalar - beta, hb, nrm, brk, avnorm, wsum, kfsp_block_stats - is all-reduced and
+ *   comes back with the same bits on every rank; the collectives of a call depend on k, m, the options and the agreed
+ *   exchange mode only, never on a column's beta or breakdown or on the rows a rank owns (a rank without rows takes
+ *   part with neutral sums).  kfsp_spmm_bench exchanges the source before every product, as the solver does.
+ *   On a group head: whole arrays and global sizes in and out, as on one context; 4002 when the ranks disagree on any
+ *   scalar; the step loop of kfsp_expv_block runs once, on the head's thread; kfsp_block_info answers for rank 0.
+ * w is never touched and a generator change discards the block, as on one context.  A device allocation that fails on
+ * one rank only is not agreed on: that rank returns its error and the others are released by the transport's deadline
+ * (or a head's watchdog). */
 /* k start vectors (1 <= k <= 16), W column-major host memory W[j*ldw + i], i in the caller's order (the internal state
- * order is applied as in kfsp_set_vector); n = the number of states of the generator */
+ * order is applied as in kfsp_set_vector); n = the number of states of the generator (a rank of a row partition: its
+ * nlocal rows, see ROW PARTITIONS) */
 int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W);
 /* the resident block back; k must be the k of kfsp_set_block.  -1 when no block is resident */
 int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W);
@@ -534,7 +557,10 @@ int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *ws
 /* kfsp_block_info: how the last block calls ran: v[0] = 1 when the last kfsp_block_arnoldi (or pass of kfsp_expv_block) was one launch,
  * v[1] its kernel variant (0 SELL from global memory, 1 banded, 2 SELL from LDS), v[2], v[3], v[4] = kernel launches
  * enqueued by the last begin, arnoldi, combine, v[5] = dynamic LDS bytes of the pass kernel, v[6] = 1 when the last
- * kfsp_block_arnoldi, kfsp_spmm or kfsp_spmm_bench multiplied with A^T (option "adjoint"), v[7] = 0 */
+ * kfsp_block_arnoldi, kfsp_spmm or kfsp_spmm_bench multiplied with A^T (option "adjoint"), v[7] = how the source of the
+ * last block product became visible under a row partition: 0 no exchange (one rank; kfsp_spmm, whose X is whole), 1 halo
+ * strips, 2 all-gather of the whole source block, + 4 when the product was split into an interior launch beside the
+ * exchange and one boundary launch (option "overlap") */
 int kfsp_block_info(kfsp_ctx *ctx, int64_t v[8]);
 
 /* ---- lock-step diagnostics ---------------------------------------------- */
@@ -667,7 +693,7 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
- * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
+ * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
  * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other

@@ -115,13 +115,11 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     // (a SELL generator takes part when its reach is bounded - the internal state order - and the halo mode was agreed)
     bool split = !src_is_global && !force_sell && ctx->use_halo && ctx->opt_overlap != 0 && ctx->comm_stream != nullptr;
     if (split) {
-        lo = (H + trip_rows - 1) / trip_rows;                        // first trip whose rows all lie >= H
-        hi = std::min<int64_t>((L - H) / trip_rows, trips);          // trips [lo, hi) end below L - H
-        // Three launches and two cross-stream waits cost ~10-15 us; that only pays once
-        // the product itself is several times longer (>= ~2M rows per rank), or when
-        // the caller insists (overlap = 2, used by the tests)
-        const int64_t min_trips = ctx->opt_overlap >= 2 ? 64 : 16384;
-        if (hi - lo < min_trips) split = false;
+        // interior trips [lo, hi) read no halo row; whether launching them on their own pays: product_split (kfsp_host.h)
+        const ProductSplit ps = product_split(H, L, trips, trip_rows, ctx->opt_overlap);
+        lo = ps.lo;
+        hi = ps.hi;
+        split = ps.split;
     }
     if (!split) {
         const double *xg = src;
@@ -413,8 +411,11 @@ int gather_to_full(kfsp_ctx *ctx, const double *dev_local, const double **full)
     return 0;
 }
 
-// Host array (this rank's block of the caller's order) -> device vector and back.
-int upload_states(kfsp_ctx *ctx, const double *host, double *dev, int64_t count)
+}  // namespace
+
+// Host array (this rank's block of the caller's order) -> device vector and back (the block path packs its columns
+// through the same two, kfsp_block.hip).
+int kfsp::upload_states(kfsp_ctx *ctx, const double *host, double *dev, int64_t count)
 {
     if (!ctx->perm_on) {
         if (count > 0)
@@ -437,7 +438,7 @@ int upload_states(kfsp_ctx *ctx, const double *host, double *dev, int64_t count)
     return scatter_from_full(ctx, ctx->d_xg.p, dev);
 }
 
-int download_states(kfsp_ctx *ctx, const double *dev, double *host, int64_t count)
+int kfsp::download_states(kfsp_ctx *ctx, const double *dev, double *host, int64_t count)
 {
     if (!ctx->perm_on) {
         if (count > 0)
@@ -457,6 +458,8 @@ int download_states(kfsp_ctx *ctx, const double *dev, double *host, int64_t coun
         HIP_TRY(hipMemcpyAsync(host, full + ctx->row0, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     return 0;
 }
+
+namespace {
 
 // A vector compacted on the device (kfsp_drop_compact) becomes the resident w of the generator
 // that was just set: caller's order -> the order the device keeps this generator in.  With a communicator the
@@ -2218,6 +2221,7 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "box_tile") ctx->opt_box_tile = value;
     else if (k == "block_box") ctx->opt_block_box = value;
     else if (k == "block_small") ctx->opt_block_small = value;
+    else if (k == "block_partition") ctx->opt_block_partition = value != 0;
     else if (k == "adjoint") ctx->opt_adjoint = value != 0;
     else if (k == "block_clamp") ctx->opt_block_clamp = value != 0;
     else if (k == "box_pencil") ctx->opt_box_pencil = value;

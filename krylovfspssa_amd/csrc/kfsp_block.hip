@@ -27,6 +27,19 @@
 // one-launch pass (<= kSmallRows rows, a banded or plain SELL image, no partition), a block step is three launches of
 // one 1024-lane workgroup per block column: k_bbegin_small, k_barnoldi_small (kfsp_kernels.hip: the pass of
 // k_arnoldi_small, compiled from the same lines) and k_bcombine_small.
+//
+// Row partitions (option block_partition; DESIGN.md 12, "Row partitions").  OPT-IN: with the option at its default 0 a
+// context with a communicator, a loop-back rank and a group head refuse every block call with -12, as they always have
+// (existing callers and tests rely on that refusal).  With 1 the forward block product of the stored forms runs on the
+// rank's rows: k_spmm takes local rows and addresses X by global row (SpmmArgs::row0), the source column is made visible
+// before every product the way the single-vector path does it - the neighbours' strips of halo * kp doubles into the
+// column's own margins (exchange_strips with a width), or an all-gather of L * kp doubles into d_bxg - and in halo mode
+// the product is split into an interior launch beside the exchange and one boundary launch (product_split, kfsp_host.h).
+// Every block-partial sum is all-reduced before the bookkeeping reads it: k_bfinal sums the rank's partials in its fixed
+// order into 2 K staging doubles, one comm_allreduce, k_bfinal again with G = 1 on the reduced sums.  The sequence of
+// collectives of a call depends on k, m, the options and the agreed exchange mode only - never on a column's beta, its
+// breakdown or the rows a rank owns.  Still refused (-12): option adjoint (the transposed banded product reads the
+// neighbour's generator rows) and matrix-free boxes; block_small is not taken (small_path excludes partitions).
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
@@ -43,7 +56,6 @@ namespace kfsp {
 namespace {
 
 constexpr int K = kBlockMaxK;
-constexpr int kMargin = 64;   // zero rows in front of and behind every block column
 
 // per-column scalars of a pass (d_bscal), K entries each
 constexpr int kHB = 0;                          // [(kMMax + 2) * 3][K]: H(j-1,j), H(j,j), H(j+1,j) of column j
@@ -60,16 +72,17 @@ constexpr int kSmallBlock = 1024;               // lanes of a small-path workgro
 
 // SELL-64 row (plain or dictionary-coded columns), the slot order and addresses of row_sell / row_sell_coded
 template <int KP, bool CODED>
-__device__ __forceinline__ void row_sell_blk(const SellDev &A, const double *__restrict__ X, int64_t c, int lane,
+__device__ __forceinline__ void row_sell_blk(const SellDev &A, const double *__restrict__ X, int64_t row0, int64_t c, int lane,
                                              double (&s)[KP])
 {
     const int64_t off = A.off[c];
     const int w = (int)((A.off[c + 1] - off) >> 6);
     const int w2 = w >> 1;
-    const int64_t r = (c << 6) + lane;
+    const int64_t lr = (c << 6) + lane;           // the row among the rank's rows: where its generator lies
+    const int64_t r = row0 + lr;                  // ... and among all rows: where its x lies (columns are global)
     double x0[KP], x1[KP];
     ld_row<KP>(X, r, x0);
-    diag_row<KP>(A.diag[r], x0, s);
+    diag_row<KP>(A.diag[lr], x0, s);
     const double *vp = A.val + off + 2 * lane;
     const int dtl = CODED ? __builtin_amdgcn_readfirstlane(A.dtlen[c]) : 0;
     if (CODED && dtl != 0) {
@@ -117,13 +130,15 @@ __device__ __forceinline__ void row_sell_blk(const SellDev &A, const double *__r
 }
 
 // Banded row r: the operands rows_dia gives the row as the .x (even r) or .y (odd r) half of its pair - the pair
-// start clamped to [-1, n - 1], an empty masked segment read as 0 against the row's own x.
+// start clamped to [-1, n - 1], an empty masked segment read as 0 against the row's own x.  r counts the rank's rows
+// (generator), row0 + r all rows (x): the clamp is the one of the GLOBAL index against the global D.n, as in rows_dia.
 template <int KP, bool MASKED>
-__device__ __forceinline__ void row_dia_blk(const DiaDev &D, const double *__restrict__ X, int64_t r, unsigned m,
+__device__ __forceinline__ void row_dia_blk(const DiaDev &D, const double *__restrict__ X, int64_t row0, int64_t r, unsigned m,
                                             double (&s)[KP])
 {
-    const int64_t ge = r & ~(int64_t)1;
-    const int par = (int)(r & 1);
+    const int64_t g = row0 + r;
+    const int64_t ge = g & ~(int64_t)1;
+    const int par = (int)(g & 1);
     const int64_t last = D.n - 1;
     auto xr = [&](int64_t p) -> int64_t { return (p < -1 ? -1 : (p > last ? last : p)) + par; };
     double x0[KP], x1[KP];
@@ -149,9 +164,15 @@ __device__ __forceinline__ void row_dia_blk(const DiaDev &D, const double *__res
 
 // FMT: 0 SELL-64, 5 SELL-64 with coded columns, 1 banded, 2 banded with group masks.  XCD-aware trip mapping and
 // trip order of k_spmv; a banded trip is a 128-row group taken as two 64-row halves.
-template <int KP, int FMT, bool DOTS>
+// PART: the launch of a rank of a row partition - local rows against a globally addressed X (a.row0) and a range of
+// linear trips (a.trip_begin .. a.trip_jump).  The one-rank launch is its own instantiation with row 0 and the whole
+// range compiled in: with the ranged form alone the k = 8 banded product on c3 came out 19 % slower on the device
+// (the compiler's schedule changed: 64 VGPRs instead of 76), DESIGN.md 12 "Row partitions".
+template <int KP, int FMT, bool DOTS, bool PART>
 __global__ __launch_bounds__(kBlock) void k_spmm(SpmmArgs a)
 {
+    const int64_t row0 = PART ? a.row0 : 0;
+    const int64_t tbeg = PART ? a.trip_begin : 0, tend = PART ? a.trip_end : a.trips;
     constexpr bool DIA = FMT == 1 || FMT == 2;
     __shared__ double red[4 * KP];
     const int lane = threadIdx.x & 63;
@@ -159,21 +180,22 @@ __global__ __launch_bounds__(kBlock) void k_spmm(SpmmArgs a)
     const int xcd = blockIdx.x & 7;
     const int slot = blockIdx.x >> 3;
     const int bx = gridDim.x >> 3;
-    const int64_t cpx = (a.trips + 7) >> 3;
-    const int64_t cbeg = (int64_t)xcd * cpx;
-    const int64_t cend = (cbeg + cpx < a.trips) ? cbeg + cpx : a.trips;
+    // the linear trips [trip_begin, trip_end) of this launch, dealt to the XCDs like the whole range [0, trips)
+    const int64_t cpx = (tend - tbeg + 7) >> 3;
+    const int64_t cbeg = tbeg + (int64_t)xcd * cpx;
+    const int64_t cend = (cbeg + cpx < tend) ? cbeg + cpx : tend;
     const int64_t cstep = (int64_t)bx * 4;
     double da[KP], db[KP];
 #pragma unroll
     for (int c = 0; c < KP; ++c) da[c] = db[c] = 0.0;
     for (int64_t t = cbeg + (int64_t)slot * 4 + wave; t < cend; t += cstep) {
-        const int64_t ct = a.trip_order ? (int64_t)__builtin_amdgcn_readfirstlane(a.trip_order[t]) : t;
+        const int64_t ct = a.trip_order ? (int64_t)__builtin_amdgcn_readfirstlane(a.trip_order[t]) : (PART && t >= a.trip_split ? t + a.trip_jump : t);
         const unsigned gm = FMT == 2 ? __builtin_amdgcn_readfirstlane(a.D.gmask[ct]) : 0xFFFFFFFFu;
         for (int h = 0; h < (DIA ? 2 : 1); ++h) {
             const int64_t r = DIA ? (ct << 7) + h * 64 + lane : (ct << 6) + lane;
             double s[KP];
-            if (DIA) row_dia_blk<KP, FMT == 2>(a.D, a.X, r, gm, s);
-            else row_sell_blk<KP, FMT == 5>(a.A, a.X, ct, lane, s);
+            if (DIA) row_dia_blk<KP, FMT == 2>(a.D, a.X, row0, r, gm, s);
+            else row_sell_blk<KP, FMT == 5>(a.A, a.X, row0, ct, lane, s);
             st_row<KP>(a.Y, r, s);
             if (DOTS && r < a.rows_red) {
                 double u[KP];
@@ -422,22 +444,23 @@ __global__ __launch_bounds__(kBlock) void k_bcombine(int64_t npairs, int half, c
 }
 
 // caller's column-major block (stage[c * n + i]) -> row-interleaved rows of the internal order, and back
-__global__ __launch_bounds__(kBlock) void k_bpack(int64_t n, int k, int kp, const double *__restrict__ stage,
+// (lds: doubles between the columns of stage, >= n)
+__global__ __launch_bounds__(kBlock) void k_bpack(int64_t n, int k, int kp, const double *__restrict__ stage, int64_t lds,
                                                   const int32_t *__restrict__ perm, double *__restrict__ X)
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n * kp; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / kp;
         const int c = (int)(i - r * kp);
-        X[i] = c < k ? stage[(int64_t)c * n + (perm ? perm[r] : r)] : 0.0;
+        X[i] = c < k ? stage[(int64_t)c * lds + (perm ? perm[r] : r)] : 0.0;
     }
 }
 
 __global__ __launch_bounds__(kBlock) void k_bunpack(int64_t n, int k, int kp, const double *__restrict__ X,
-                                                    const int32_t *__restrict__ iperm, double *__restrict__ stage)
+                                                    const int32_t *__restrict__ iperm, double *__restrict__ stage, int64_t lds)
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n * k; i += (int64_t)gridDim.x * kBlock) {
         const int64_t c = i / n, r = i - c * n;
-        stage[i] = X[(iperm ? (int64_t)iperm[r] : r) * kp + c];
+        stage[c * lds + r] = X[(iperm ? (int64_t)iperm[r] : r) * kp + c];
     }
 }
 
@@ -445,21 +468,30 @@ enum { kFinBegin = 0, kFinDots = 1, kFinNorm = 2, kFinAvn = 3, kFinWsum = 4 };
 
 // The per-column scalar work of a pass, one workgroup: 256 / K threads per column sum the block partials of the
 // two quantities in a fixed order, then one thread per column applies the Arnoldi bookkeeping of `stage`.
-__global__ __launch_bounds__(kBlock) void k_bfinal(int stage, int j, int kp, int G, const double *__restrict__ part,
-                                                   double *__restrict__ sc, double break_tol)
+// The second quantity's partials start off1 doubles behind the first's.  sums != null (a row partition): the sum stage
+// alone - the 2 K column sums go to sums[0..K) and sums[K..2K) for the all-reduce, and the bookkeeping follows as a
+// second launch on the reduced sums (part = sums, G = 1, off1 = K).
+__global__ __launch_bounds__(kBlock) void k_bfinal(int stage, int j, int kp, int G, const double *__restrict__ part, int64_t off1,
+                                                   double *__restrict__ sc, double break_tol, double *__restrict__ sums)
 {
     constexpr int T = kBlock / K;
     const int c = threadIdx.x / T, i = threadIdx.x % T;
     double s0 = 0.0, s1 = 0.0;
     for (int g = i; g < G; g += T) {
         s0 += part[(size_t)g * K + c];
-        s1 += part[((size_t)kMaxGrid + g) * K + c];
+        s1 += part[(size_t)off1 + (size_t)g * K + c];
     }
     for (int o = T / 2; o >= 1; o >>= 1) {
         s0 += __shfl_xor(s0, o);
         s1 += __shfl_xor(s1, o);
     }
-    if (i != 0 || c >= kp) return;
+    if (i != 0) return;
+    if (sums) {
+        sums[c] = s0;
+        sums[K + c] = s1;
+        return;
+    }
+    if (c >= kp) return;
     double *hb = sc + kHB, *nrm = sc + kNRM, *co = sc + kCO;
     double &brk = sc[kBRK + c], &gg = sc[kGG + c];
     switch (stage) {
@@ -575,12 +607,21 @@ int kp_of(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)); }
 
 int spmm_fmt(const kfsp_ctx *c) { return c->use_dia ? (c->dia_masked ? 2 : 1) : (c->sell_coded ? 5 : 0); }
 int64_t spmm_trips(const kfsp_ctx *c) { return product_trips(c->nchunks, c->use_dia); }
-// rows a product writes, and rows of a block column (margins included)
+// rows a product writes, and rows of a block column (margins included).  Under a row partition a column holds the
+// block length L plus one 128-row group whatever the rank owns (every rank sends L rows to an all-gather and its last
+// halo rows to a neighbour; the padded half-group of a banded rank writes rows [L, L + 64)), and margins that take the
+// neighbours' strips (block_margin: the rule of setup_exchange) - sizes every rank agrees on.
 int64_t rows_act(const kfsp_ctx *c) { return spmm_trips(c) * (c->use_dia ? 128 : 64); }
-int64_t col_rows(const kfsp_ctx *c) { return rows_act(c) + 2 * kMargin; }
+int64_t margin_rows(const kfsp_ctx *c) { return block_margin(c->margin); }
+int64_t col_rows(const kfsp_ctx *c) { return (c->use_comm ? c->L + 2 * kChunk : rows_act(c)) + 2 * margin_rows(c); }
 // doubles of one block column, and its first row
 size_t col_len(const kfsp_ctx *c, int kp) { return (size_t)col_rows(c) * (size_t)kp; }
-double *bcol(double *base, const kfsp_ctx *c, int kp, int j) { return base + (size_t)j * col_len(c, kp) + (size_t)kMargin * kp; }
+double *bcol(double *base, const kfsp_ctx *c, int kp, int j) { return base + (size_t)j * col_len(c, kp) + (size_t)margin_rows(c) * kp; }
+// the gathered source block of a row partition: nranks * L rows between margins; global row 0
+size_t xg_len(const kfsp_ctx *c, int kp) { return (size_t)(c->L * c->nranks + 2 * margin_rows(c)) * (size_t)kp; }
+double *xg_row0(const kfsp_ctx *c, int kp) { return c->d_bxg.p + (size_t)margin_rows(c) * kp; }
+// the context whose block state answers for ctx: rank 0 of a group head, else ctx itself
+kfsp_ctx *lead(kfsp_ctx *c) { return c->group ? group_rank0(c) : c; }
 // 16-byte pairs the streaming kernels cover: the rows of the SELL-padded block, like act_pairs
 int64_t red_pairs(const kfsp_ctx *c, int kp) { return c->nchunks * kChunk * (int64_t)kp / 2; }
 
@@ -598,12 +639,12 @@ bool small_path(const kfsp_ctx *c)
 // grid of the streaming kernels over a block column
 int flat_grid(const kfsp_ctx *c, int kp) { return vec_grid(red_pairs(c, kp), c->opt_vgrid); }
 
-template <int KP>
+template <int KP, bool PART>
 void launch_spmm_kp(int fmt, bool dots, int g, const SpmmArgs &a, hipStream_t st)
 {
 #define KFSP_SPMM(F)                                                                                   \
-    if (dots) hipLaunchKernelGGL((k_spmm<KP, F, true>), dim3(g), dim3(kBlock), 0, st, a);              \
-    else hipLaunchKernelGGL((k_spmm<KP, F, false>), dim3(g), dim3(kBlock), 0, st, a);
+    if (dots) hipLaunchKernelGGL((k_spmm<KP, F, true, PART>), dim3(g), dim3(kBlock), 0, st, a);        \
+    else hipLaunchKernelGGL((k_spmm<KP, F, false, PART>), dim3(g), dim3(kBlock), 0, st, a);
     switch (fmt) {
     case 1: KFSP_SPMM(1) break;
     case 2: KFSP_SPMM(2) break;
@@ -709,12 +750,15 @@ int spmm_adjoint(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
     return g;
 }
 
-// Y = A X, or A^T X under option adjoint (block columns of width kp); dots: partials of ua . Y and ub . Y.  Returns the grid.
-int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, const double *ub, bool dots)
+// Y = A X, or A^T X under option adjoint (block columns of width kp); dots: partials of ua . Y and ub . Y in *G slots.
+// x: row 0 of the source column.  Under a row partition (forward stored forms only, block_supported) the source is made
+// visible first - the strips into x's own margins, or all blocks gathered into d_bxg - unless x_global says that x is
+// row 0 of a whole block every rank already holds (kfsp_spmm).  blk_info[7] records how.
+int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, const double *ub, bool dots, int *G, bool x_global = false)
 {
     SpmmArgs a;
     generator_args(ctx, a.A, a.D);
-    a.X = X;
+    a.X = x;
     a.Y = Y;
     a.ua = ua;
     a.ub = ub;
@@ -725,29 +769,124 @@ int spmm(kfsp_ctx *ctx, int kp, const double *X, double *Y, const double *ua, co
     a.box_tab = nullptr;
     a.box_ntab = 0;
     a.box_fast = nullptr;
-    if (ctx->opt_adjoint) return spmm_adjoint(ctx, kp, dots, a);
-    if (ctx->use_box) return spmm_box(ctx, kp, dots, a);
-    const int g = spmm_grid(ctx);
-    const int fmt = spmm_fmt(ctx);
-    switch (kp) {
-    case 2: launch_spmm_kp<2>(fmt, dots, g, a, ctx->stream); break;
-    case 4: launch_spmm_kp<4>(fmt, dots, g, a, ctx->stream); break;
-    case 8: launch_spmm_kp<8>(fmt, dots, g, a, ctx->stream); break;
-    default: launch_spmm_kp<16>(fmt, dots, g, a, ctx->stream); break;
+    a.row0 = 0;
+    a.trip_begin = 0;
+    a.trip_end = a.trips;
+    a.trip_split = INT64_MAX;
+    a.trip_jump = 0;
+    ctx->blk_info[7] = 0;
+    if (ctx->opt_adjoint || ctx->use_box) {
+        const int g = ctx->opt_adjoint ? spmm_adjoint(ctx, kp, dots, a) : spmm_box(ctx, kp, dots, a);
+        if (g < 0) return fail(ctx, -12, kAdjFormMsg);
+        *G = g;
+        return 0;
     }
-    return g;
+    hipStream_t st = ctx->stream;
+    const int fmt = spmm_fmt(ctx);
+    const bool part = ctx->use_comm;
+    auto launch = [&](int g) {
+        switch (kp) {
+        case 2: part ? launch_spmm_kp<2, true>(fmt, dots, g, a, st) : launch_spmm_kp<2, false>(fmt, dots, g, a, st); break;
+        case 4: part ? launch_spmm_kp<4, true>(fmt, dots, g, a, st) : launch_spmm_kp<4, false>(fmt, dots, g, a, st); break;
+        case 8: part ? launch_spmm_kp<8, true>(fmt, dots, g, a, st) : launch_spmm_kp<8, false>(fmt, dots, g, a, st); break;
+        default: part ? launch_spmm_kp<16, true>(fmt, dots, g, a, st) : launch_spmm_kp<16, false>(fmt, dots, g, a, st); break;
+        }
+    };
+    const int g = spmm_grid(ctx);
+    *G = g;
+    if (!ctx->use_comm) {
+        launch(g);
+        return 0;
+    }
+    a.row0 = ctx->row0;
+    if (x_global) {
+        launch(g);
+        return 0;
+    }
+    if (!ctx->use_halo) {
+        if (int rc = comm_allgather(ctx, x, xg_row0(ctx, kp), (size_t)ctx->L * kp, st)) return rc;
+        a.X = xg_row0(ctx, kp);
+        ctx->blk_info[7] = 2;
+        launch(g);
+        return 0;
+    }
+    a.X = x - (size_t)ctx->row0 * kp;                        // global row g lies at x[(g - row0) * kp]
+    ctx->blk_info[7] = 1;
+    const ProductSplit ps = product_split(ctx->halo, ctx->L, a.trips, ctx->use_dia ? 128 : 64, ctx->opt_overlap);
+    if (!ps.split || ctx->comm_stream == nullptr) {
+        if (int rc = exchange_strips(ctx, x, st, kp)) return rc;
+        launch(g);
+        return 0;
+    }
+    // the strips travel on the communication stream, behind everything that produced x, while the interior trips run
+    HIP_TRY(hipEventRecord(ctx->ev_src, st));
+    HIP_TRY(hipStreamWaitEvent(ctx->comm_stream, ctx->ev_src, 0));
+    if (int rc = exchange_strips(ctx, x, ctx->comm_stream, kp)) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev_halo, ctx->comm_stream));
+    a.trip_order = nullptr;
+    // interior: no halo row is read (the boundary launch keeps 512 of a slot's kMaxGrid partials, as run_product does)
+    const int g1 = std::min(product_grid(ps.hi - ps.lo, ctx->opt_grid, 1024), kMaxGrid - 512);
+    a.trip_begin = ps.lo;
+    a.trip_end = ps.hi;
+    launch(g1);
+    HIP_TRY(hipStreamWaitEvent(st, ctx->ev_halo, 0));
+    // one launch for both boundary ranges: linear trips [0, lo) are themselves, [lo, lo + trips - hi) stand for [hi, trips)
+    const int64_t nb = ps.lo + (a.trips - ps.hi);
+    const int g2 = product_grid(nb, 0, 512);
+    a.part = ctx->d_bpart.p + (size_t)g1 * K;
+    a.trip_begin = 0;
+    a.trip_end = nb;
+    a.trip_split = ps.lo;
+    a.trip_jump = ps.hi - ps.lo;
+    launch(g2);
+    *G = g1 + g2;
+    ctx->blk_info[7] = 5;
+    return 0;
 }
 
-void finalize(kfsp_ctx *ctx, int stage, int j, int kp, int G, double break_tol = 0.0)
+// The scalar stage behind a producer of G block partials.  One rank: one launch, as ever.  Row partition: the rank's
+// column sums in the same fixed order, one all-reduce of the 2 K sums, the bookkeeping on the reduced sums - on every
+// rank, whatever its columns did.
+int finalize(kfsp_ctx *ctx, int stage, int j, int kp, int G, double break_tol = 0.0)
 {
-    hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, G, ctx->d_bpart.p, ctx->d_bscal.p, break_tol);
+    const int64_t off1 = (int64_t)kMaxGrid * K;
+    if (!ctx->use_comm) {
+        hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, G, ctx->d_bpart.p, off1, ctx->d_bscal.p, break_tol,
+                           (double *)nullptr);
+        return 0;
+    }
+    double *sums = ctx->d_bpart.p + (size_t)2 * kMaxGrid * K;
+    hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, G, ctx->d_bpart.p, off1, ctx->d_bscal.p, break_tol, sums);
+    if (int rc = comm_allreduce(ctx, sums, 2 * K, false, ctx->stream)) return rc;
+    hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, 1, sums, (int64_t)K, ctx->d_bscal.p, break_tol,
+                       (double *)nullptr);
+    return 0;
 }
 
 // the scalar and partial buffers of the block path
 int ensure_scalars(kfsp_ctx *ctx)
 {
     HIP_TRY(ctx->d_bscal.reserve(kScal, true));
-    HIP_TRY(ctx->d_bpart.reserve((size_t)2 * kMaxGrid * K, true));
+    HIP_TRY(ctx->d_bpart.reserve((size_t)2 * kMaxGrid * K + 2 * K, true));    // + the 2 K column sums a row partition all-reduces
+    return 0;
+}
+
+// what a row partition exchanges block columns through: the strip buffer at block width, the gathered block (zeroed
+// when allocated and whenever the width changes: its margins and the rows behind n must read 0)
+int ensure_exchange(kfsp_ctx *ctx, int kp)
+{
+    if (!ctx->use_comm) return 0;
+    if (ctx->use_halo) HIP_TRY(ctx->d_strip.reserve((size_t)(2 * ctx->halo) * (size_t)(ctx->nranks + 1) * (size_t)kp, true));
+    const size_t need = xg_len(ctx, kp);
+    if (need > ctx->d_bxg.cap) {
+        ctx->d_bxg.release();
+        HIP_TRY(ctx->d_bxg.reserve(need, true));
+        ctx->bxg_kp = kp;
+    }
+    if (ctx->bxg_kp != kp) {
+        HIP_TRY(hipMemsetAsync(ctx->d_bxg.p, 0, ctx->d_bxg.cap * sizeof(double), ctx->stream));
+        ctx->bxg_kp = kp;
+    }
     return 0;
 }
 
@@ -764,30 +903,58 @@ int ensure_basis(kfsp_ctx *ctx, int kp, int ncols)
         HIP_TRY(hipMemsetAsync(ctx->d_bv.p, 0, ctx->d_bv.cap * sizeof(double), ctx->stream));
         ctx->bv_kp = kp;
     }
+    if (int rc = ensure_exchange(ctx, kp)) return rc;
     return ensure_scalars(ctx);
 }
 
-// host column-major (caller's order) -> zeroed block column dst (width kp, internal order)
-int upload_block(kfsp_ctx *ctx, int k, int kp, int64_t ld, const double *W, double *col0)
+// host column-major (caller's order) -> zeroed block column dst (width kp, internal order).  One rank, and the whole
+// block every rank of a partition holds (whole: kfsp_spmm's X into d_bxg): n rows through the permutation.  A rank's
+// own rows (kfsp_set_block under a communicator): column by column the way kfsp_set_vector takes a vector
+// (upload_states: under the internal state order one all-gather per column, on every rank), then packed as they lie.
+int upload_block(kfsp_ctx *ctx, int k, int kp, int64_t ld, const double *W, double *col0, bool whole = false)
 {
+    hipStream_t st = ctx->stream;
+    if (ctx->use_comm && !whole) {
+        const int64_t nl = ctx->nloc, L = ctx->L;
+        HIP_TRY(ctx->d_bstage.reserve((size_t)L * k, false));
+        HIP_TRY(hipMemsetAsync(col0 - (size_t)margin_rows(ctx) * kp, 0, col_len(ctx, kp) * sizeof(double), st));
+        for (int c = 0; c < k; ++c)
+            if (int rc = upload_states(ctx, W ? W + (size_t)c * ld : W, ctx->d_bstage.p + (size_t)c * L, nl)) return rc;
+        const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (nl * kp + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL(k_bpack, dim3(g), dim3(kBlock), 0, st, nl, k, kp, ctx->d_bstage.p, L, (const int32_t *)nullptr, col0);
+        return 0;
+    }
     const int64_t n = ctx->n;
     HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
-    HIP_TRY(hipMemsetAsync(col0 - (size_t)kMargin * kp, 0, col_len(ctx, kp) * sizeof(double), ctx->stream));
+    if (whole) HIP_TRY(hipMemsetAsync(ctx->d_bxg.p, 0, xg_len(ctx, kp) * sizeof(double), st));
+    else HIP_TRY(hipMemsetAsync(col0 - (size_t)margin_rows(ctx) * kp, 0, col_len(ctx, kp) * sizeof(double), st));
     HIP_TRY(hipMemcpy2DAsync(ctx->d_bstage.p, (size_t)n * sizeof(double), W, (size_t)ld * sizeof(double), (size_t)n * sizeof(double),
-                             (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+                             (size_t)k, hipMemcpyHostToDevice, st));
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n * kp + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_bpack, dim3(g), dim3(kBlock), 0, ctx->stream, n, k, kp, ctx->d_bstage.p, ctx->perm_on ? ctx->d_perm.p : nullptr, col0);
+    hipLaunchKernelGGL(k_bpack, dim3(g), dim3(kBlock), 0, st, n, k, kp, ctx->d_bstage.p, n, ctx->perm_on ? ctx->d_perm.p : nullptr, col0);
     return 0;
 }
 
+// ... and back; under a communicator the rank's rows column by column through download_states (L rows staged per
+// column: that is what its all-gather sends)
 int download_block(kfsp_ctx *ctx, int k, int kp, const double *col0, int64_t ld, double *W)
 {
+    hipStream_t st = ctx->stream;
+    if (ctx->use_comm) {
+        const int64_t L = ctx->L;
+        HIP_TRY(ctx->d_bstage.reserve((size_t)L * k, false));
+        const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (L * k + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL(k_bunpack, dim3(g), dim3(kBlock), 0, st, L, k, kp, col0, (const int32_t *)nullptr, ctx->d_bstage.p, L);
+        for (int c = 0; c < k; ++c)
+            if (int rc = download_states(ctx, ctx->d_bstage.p + (size_t)c * L, W ? W + (size_t)c * ld : W, ctx->nloc)) return rc;
+        return 0;
+    }
     const int64_t n = ctx->n;
     HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n * k + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_bunpack, dim3(g), dim3(kBlock), 0, ctx->stream, n, k, kp, col0, ctx->perm_on ? ctx->d_iperm.p : nullptr, ctx->d_bstage.p);
+    hipLaunchKernelGGL(k_bunpack, dim3(g), dim3(kBlock), 0, st, n, k, kp, col0, ctx->perm_on ? ctx->d_iperm.p : nullptr, ctx->d_bstage.p, n);
     HIP_TRY(hipMemcpy2DAsync(W, (size_t)ld * sizeof(double), ctx->d_bstage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                             (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+                             (size_t)k, hipMemcpyDeviceToHost, st));
     return 0;
 }
 
@@ -804,16 +971,37 @@ void block_release(kfsp_ctx *ctx)
     ctx->d_bstage.release();
     ctx->d_bscal.release();
     ctx->d_bpart.release();
-    ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->blk_begin_m = 0;
+    ctx->d_bxg.release();
+    ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->bxg_kp = ctx->blk_begin_m = 0;
     std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
     std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
     std::memset(ctx->blk_box_t_occ, 0, sizeof(ctx->blk_box_t_occ));
 }
 
+// Every refusal below is made from what all ranks of a partition share (options, the kind of generator), before the
+// first collective of any block call: a rank that returned alone would leave its peers waiting in one.
 int block_supported(kfsp_ctx *ctx)
 {
-    if (ctx->group || ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm)
-        return fail(ctx, -12, "several vectors at once: not with a row partition (communicator or group context)");
+    static const char *const kPartMsg = "several vectors at once: not with a row partition (communicator or group context) "
+                                        "unless option block_partition = 1";
+    if (ctx->group) {
+        kfsp_ctx *r0 = group_rank0(ctx);
+        if (!r0 || !r0->opt_block_partition) return fail(ctx, -12, kPartMsg);
+        const int rc = block_supported(r0);
+        if (rc) ctx->err = std::string(r0->err);
+        return rc;
+    }
+    if (ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm) {
+        if (!ctx->opt_block_partition) return fail(ctx, -12, kPartMsg);
+        if (!ctx->use_comm) return fail(ctx, -12, "several vectors at once: this rank's communicator carries no collectives");
+        if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
+        if (ctx->opt_adjoint)
+            return fail(ctx, -12, "several vectors at once, option adjoint: not under a row partition (the transposed banded "
+                                  "product reads the neighbour's generator rows, not only its rows of X)");
+        if (ctx->use_box)
+            return fail(ctx, -12, "several vectors at once: not for a matrix-free generator under a row partition "
+                                  "(option box_store = 1 stores it)");
+    }
     if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
     if (ctx->use_box) {
         if (!ctx->opt_block_box)
@@ -836,15 +1024,20 @@ int block_supported(kfsp_ctx *ctx)
 
 int block_shape(kfsp_ctx *ctx, int *k, int64_t *n)
 {
-    *k = ctx->blk_k;
+    *k = lead(ctx)->blk_k;
     *n = ctx->n;
     return 0;
 }
 
-int block_mmax(kfsp_ctx *ctx) { return (int)(ctx->v_mmax ? std::min(ctx->v_mmax, ctx->opt_mmax) : ctx->opt_mmax); }
+int block_mmax(kfsp_ctx *ctx)
+{
+    ctx = lead(ctx);
+    return (int)(ctx->v_mmax ? std::min(ctx->v_mmax, ctx->opt_mmax) : ctx->opt_mmax);
+}
 
 int block_begin(kfsp_ctx *ctx, int m, double *beta)
 {
+    if (ctx->group) return group_block_begin(ctx, m, beta);
     PhaseTimer timer(ctx, KFSP_T_BEGIN);
     HIP_TRY(hipSetDevice(ctx->device));
     const int kp = ctx->blk_kp;
@@ -859,7 +1052,7 @@ int block_begin(kfsp_ctx *ctx, int m, double *beta)
         hipLaunchKernelGGL(k_bcopy_nrm, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2,
                            reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)),
                            ctx->d_bpart.p);
-        finalize(ctx, kFinBegin, 1, kp, g);
+        if (int rc = finalize(ctx, kFinBegin, 1, kp, g)) return rc;
         ctx->blk_info[2] = 2;
     }
     HIP_TRY(hipMemcpyAsync(beta, ctx->d_bscal.p + kNRM + K, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -869,6 +1062,7 @@ int block_begin(kfsp_ctx *ctx, int m, double *beta)
 
 int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nrm, int *brk, double *avnorm)
 {
+    if (ctx->group) return group_block_arnoldi(ctx, m, break_tol, hb, nrm, brk, avnorm);
     PhaseTimer timer(ctx, KFSP_T_ARNOLDI);
     HIP_TRY(hipSetDevice(ctx->device));
     const int kp = ctx->blk_kp;
@@ -905,19 +1099,20 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
         ctx->blk_info[5] = (int64_t)lds;
     }
     for (int j = 1; j <= m && !small; ++j) {
-        const int g = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true);
-        if (g < 0) return fail(ctx, -12, kAdjFormMsg);
-        finalize(ctx, kFinDots, j, kp, g);
+        int g = 0;
+        if (int rc = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true, &g)) return rc;
+        if (int rc = finalize(ctx, kFinDots, j, kp, g)) return rc;
         hipLaunchKernelGGL(k_bortho, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
                            reinterpret_cast<const d2 *>(j >= 2 ? u(j - 1) : nullptr), reinterpret_cast<const d2 *>(u(j)),
                            ctx->d_bscal.p + kCO, ctx->d_bpart.p);
-        finalize(ctx, kFinNorm, j, kp, gv, break_tol);
+        if (int rc = finalize(ctx, kFinNorm, j, kp, gv, break_tol)) return rc;
     }
     if (!small) {
         // the extra product for AVNORM (:261-263) into the scratch column
-        if (spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false) < 0) return fail(ctx, -12, kAdjFormMsg);
+        int g = 0;
+        if (int rc = spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false, &g)) return rc;
         hipLaunchKernelGGL(k_bnorm, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p);
-        finalize(ctx, kFinAvn, m + 1, kp, gv);
+        if (int rc = finalize(ctx, kFinAvn, m + 1, kp, gv)) return rc;
     }
     std::vector<double> h((size_t)kScal);
     HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_bscal.p, (size_t)kCMB * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -931,6 +1126,7 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
 
 int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
 {
+    if (ctx->group) return group_block_combine(ctx, mx, coef, wsum);
     PhaseTimer timer(ctx, KFSP_T_COMBINE);
     HIP_TRY(hipSetDevice(ctx->device));
     const int kp = ctx->blk_kp;
@@ -946,7 +1142,7 @@ int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
         hipLaunchKernelGGL(k_bcombine, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
                            (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
                            ctx->d_bpart.p, ctx->opt_block_clamp ? 1 : 0);
-        finalize(ctx, kFinWsum, 0, kp, g);
+        if (int rc = finalize(ctx, kFinWsum, 0, kp, g)) return rc;
         ctx->blk_info[4] = 2;
     }
     HIP_TRY(hipMemcpyAsync(wsum, ctx->d_bscal.p + kWS, K * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -966,9 +1162,18 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
     return guarded(ctx, [&]() -> int {
         if (int rc = block_supported(ctx)) return rc;
         if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
-        if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
-        if (ldw < n) return fail(ctx, -4, "ldw < n");
-        if (!W) return fail(ctx, -5, "null W");
+        if (ctx->group) return group_set_block(ctx, k, n, ldw, W);
+        // (a rank's arguments are its own: a caller that gets them wrong on one rank only leaves the others waiting, as in
+        // kfsp_set_vector)
+        if (ctx->use_comm) {
+            if (n != ctx->nloc) return fail(ctx, -3, "n is not this rank's block size");
+            if (ldw < n) return fail(ctx, -4, "ldw < n");
+            if (!W && n > 0) return fail(ctx, -5, "null W");
+        } else {
+            if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
+            if (ldw < n) return fail(ctx, -4, "ldw < n");
+            if (!W) return fail(ctx, -5, "null W");
+        }
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
         if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
@@ -990,11 +1195,18 @@ int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W)
     if (!ctx) return -1;
     return guarded(ctx, [&]() -> int {
         if (int rc = block_supported(ctx)) return rc;
-        if (ctx->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
-        if (k != ctx->blk_k) return fail(ctx, -2, "k is not the number of columns of the resident block");
-        if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
-        if (ldw < n) return fail(ctx, -4, "ldw < n");
-        if (!W) return fail(ctx, -5, "null W");
+        if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
+        if (k != lead(ctx)->blk_k) return fail(ctx, -2, "k is not the number of columns of the resident block");
+        if (ctx->group) return group_get_block(ctx, k, n, ldw, W);
+        if (ctx->use_comm) {
+            if (n != ctx->nloc) return fail(ctx, -3, "n is not this rank's block size");
+            if (ldw < n) return fail(ctx, -4, "ldw < n");
+            if (!W && n > 0) return fail(ctx, -5, "null W");
+        } else {
+            if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
+            if (ldw < n) return fail(ctx, -4, "ldw < n");
+            if (!W) return fail(ctx, -5, "null W");
+        }
         HIP_TRY(hipSetDevice(ctx->device));
         if (int rc = download_block(ctx, k, ctx->blk_kp, bcol(ctx->d_blk.p, ctx, ctx->blk_kp, 0), ldw, W)) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1010,14 +1222,19 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
         if (ld < ctx->n) return fail(ctx, -3, "ld < n");
         if (!X) return fail(ctx, -4, "null X");
-        if (!Y) return fail(ctx, -5, "null Y");
+        if (ctx->group) return group_spmm(ctx, k, ld, X, Y);
+        if (!Y && !(ctx->use_comm && ctx->nloc == 0)) return fail(ctx, -5, "null Y");
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
         if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         if (int rc = ensure_basis(ctx, kp, 2)) return rc;
-        double *x = bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
-        if (int rc = upload_block(ctx, k, kp, ld, X, x)) return rc;
-        if (spmm(ctx, kp, x, y, nullptr, nullptr, false) < 0) return fail(ctx, -12, kAdjFormMsg);
+        // under a row partition X is the whole block on every rank (the kfsp_spmv convention): it goes to the gathered
+        // block buffer, global row 0 first, and no exchange follows
+        const bool whole = ctx->use_comm;
+        double *x = whole ? xg_row0(ctx, kp) : bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
+        if (int rc = upload_block(ctx, k, kp, ld, X, x, whole)) return rc;
+        int g = 0;
+        if (int rc = spmm(ctx, kp, x, y, nullptr, nullptr, false, &g, whole)) return rc;
         ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
         if (int rc = download_block(ctx, k, kp, y, ld, Y)) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1029,7 +1246,7 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
 static int block_call_ok(kfsp_ctx *ctx)
 {
     if (int rc = block_supported(ctx)) return rc;
-    if (ctx->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
+    if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
     return 0;
 }
 
@@ -1052,8 +1269,8 @@ int kfsp_block_arnoldi(kfsp_ctx *ctx, int32_t m, double break_tol, double *hb, d
         if (int rc = block_call_ok(ctx)) return rc;
         if (m < 1 || m > kMMax) return fail(ctx, -2, "bad m (need 1 <= m <= 100)");
         if (m > block_mmax(ctx)) return fail(ctx, -2, "m exceeds option m_max");
-        if (ctx->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
-        if (m > ctx->blk_begin_m) return fail(ctx, -2, "m exceeds the m of kfsp_block_begin (the basis is laid out for that one)");
+        if (lead(ctx)->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
+        if (m > lead(ctx)->blk_begin_m) return fail(ctx, -2, "m exceeds the m of kfsp_block_begin (the basis is laid out for that one)");
         if (!hb || !nrm || !brk || !avnorm) return fail(ctx, -4, "null output");
         return block_arnoldi(ctx, m, break_tol, hb, nrm, brk, avnorm);
     });
@@ -1064,8 +1281,8 @@ int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *ws
     if (!ctx) return -1;
     return guarded(ctx, [&]() -> int {
         if (int rc = block_call_ok(ctx)) return rc;
-        if (ctx->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
-        if (mx < 1 || mx > ctx->blk_begin_m + 2) return fail(ctx, -2, "bad mx (need 1 <= mx <= m + 2 of kfsp_block_begin)");
+        if (lead(ctx)->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
+        if (mx < 1 || mx > lead(ctx)->blk_begin_m + 2) return fail(ctx, -2, "bad mx (need 1 <= mx <= m + 2 of kfsp_block_begin)");
         if (!coef) return fail(ctx, -4, "null coef");
         if (!wsum) return fail(ctx, -5, "null wsum");
         return block_combine(ctx, mx, coef, wsum);
@@ -1076,6 +1293,7 @@ int kfsp_block_info(kfsp_ctx *ctx, int64_t *v)
 {
     if (!ctx) return -1;
     if (!v) return fail(ctx, -2, "null v");
+    if (ctx->group) return group_block_info(ctx, v);
     for (int i = 0; i < 8; ++i) v[i] = ctx->blk_info[i];
     return 0;
 }
@@ -1085,9 +1303,10 @@ int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)
     if (!ctx) return -1;
     return guarded(ctx, [&]() -> int {
         if (int rc = block_supported(ctx)) return rc;
-        if (ctx->blk_k == 0) return fail(ctx, -1, "no block resident");
+        if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident");
         if (reps < 1) return fail(ctx, -2, "reps < 1");
         if (!ms_total) return fail(ctx, -3, "null ms_total");
+        if (ctx->group) return group_spmm_bench(ctx, reps, ms_total);
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = ctx->blk_kp;
         if (int rc = ensure_basis(ctx, kp, 1)) return rc;
@@ -1095,8 +1314,11 @@ int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)
         double *y = bcol(ctx->d_bv.p, ctx, kp, 0);
         HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
         ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
-        for (int r = 0; r < reps; ++r)
-            if (spmm(ctx, kp, x, y, nullptr, nullptr, false) < 0) return fail(ctx, -12, kAdjFormMsg);
+        // (under a row partition the source is exchanged before every product, as in the solver)
+        for (int r = 0; r < reps; ++r) {
+            int g = 0;
+            if (int rc = spmm(ctx, kp, x, y, nullptr, nullptr, false, &g)) return rc;
+        }
         HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
         HIP_TRY(hipEventSynchronize(ctx->ev1));
         HIP_TRY(hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));

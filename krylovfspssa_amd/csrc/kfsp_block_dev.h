@@ -62,6 +62,14 @@ struct SpmmArgs {
     const double *box_tab;   // matrix-free box: the table image (staged to LDS), its length in doubles and the
     int box_ntab;            // single-factor descriptor behind it
     const BoxFast *box_fast;
+    // Row partition (option block_partition; read by k_spmm<.., PART = true> only - the one-rank instantiations, the box
+    // and the transposed kernels cover [0, trips) of one rank): rows are local, X is addressed by GLOBAL row - local
+    // row r is row row0 + r of X.  The launch covers the linear trips [trip_begin, trip_end); linear trip t stands for
+    // trip (t < trip_split ? t : t + trip_jump), so that one launch takes both boundary ranges of a split product
+    // (SpmvArgs, kfsp_internal.h).
+    int64_t row0;
+    int64_t trip_begin, trip_end;
+    int64_t trip_split, trip_jump;
 };
 
 #if defined(__HIPCC__)

@@ -24,8 +24,8 @@ int nccl_fail(kfsp_ctx *c, ncclResult_t r, const char *where)
     } while (0)
 
 // ---- the collectives of the data path, over RCCL or the loop-back transport ----
-constexpr int kLoopVals = 16;                              // values one all-reduce may carry (the 16 FIND_DROPTOL sums)
-constexpr int kLoopScratch = 64 * kLoopVals + kLoopVals;   // doubles: up to 64 ranks x 16 scalars (+ result)
+constexpr int kLoopVals = 32;                              // values one all-reduce may carry (the 16 FIND_DROPTOL sums; 2 x 16 column sums of the block path)
+constexpr int kLoopScratch = 64 * kLoopVals + kLoopVals;   // doubles: up to 64 ranks x 32 scalars (+ result)
 
 }  // namespace
 
@@ -119,10 +119,12 @@ void comm_abort(kfsp_ctx *ctx)
 // Banded generator: only the `halo` boundary rows of the two neighbours are ever
 // read.  Every rank contributes [its first halo rows | its last halo rows]; one
 // all-gather of these strips, then the two strips this rank needs are dropped
-// into the margins of the source column itself.  All on stream st.
-int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st)
+// into the margins of the source column itself.  All on stream st.  width: doubles
+// per row (1: a vector; kp: a row-interleaved block column, whose caller sized d_strip).
+int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st, int width)
 {
-    const int64_t H = ctx->halo, L = ctx->L;
+    // (in doubles: a strip of halo rows of a block column is one run of halo * width doubles)
+    const int64_t H = ctx->halo * width, L = ctx->L * width;
     double *col = const_cast<double *>(src_local);
     if (ctx->opt_halo_p2p != 0) {
         // Neighbours only, and straight between the columns: a rank's first H rows go into the margin
@@ -219,7 +221,7 @@ int setup_exchange(kfsp_ctx *ctx)
         // the next begin_step anyway)
         // + 128: the banded kernel works on 128-row groups, whose padded rows read up
         // to one group beyond the block end
-        ctx->margin = round_up(H + H / 4 + 2 * kChunk, 64);
+        ctx->margin = halo_margin(H);
         ctx->relayout = true;
         if (int rc = resize(ctx, ctx->n)) return rc;
     }

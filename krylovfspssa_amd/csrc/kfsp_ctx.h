@@ -322,6 +322,8 @@ struct kfsp_ctx {
     // several vectors at once (kfsp_block.hip): the resident block (kp doubles per row), the block basis / scratch
     // columns, the caller-layout staging area, per-column scalars and partials; all released when the generator changes
     DevBuf<double> d_blk, d_bv, d_bstage, d_bscal, d_bpart;
+    DevBuf<double> d_bxg;        // row partition: the gathered source block (all-gather mode) / the whole X of kfsp_spmm, margins included
+    int bxg_kp = 0;              // width d_bxg is laid out for
     int blk_k = 0, blk_kp = 0;   // columns of the resident block (0: none) and its width
     int bv_kp = 0;               // width d_bv is laid out for
     int blk_begin_m = 0;         // Krylov dimension the last block_begin laid the basis out for (0: none since kfsp_set_block)
@@ -379,6 +381,7 @@ struct kfsp_ctx {
     int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12)
     int64_t opt_block_small = 0;          // 1: the block path takes its one-launch kernels where the single-vector path takes k_arnoldi_small
     int64_t opt_adjoint = 0;              // 1: the block calls multiply with A^T (kfsp_block_adj.hip): backward solves exp(tA^T) F
+    int64_t opt_block_partition = 0;      // 1: the block calls run under a row partition (communicator, loop-back rank, group head); 0: -12
     int64_t opt_block_clamp = 1;          // 0: the block combine does not clamp at 0 and wsum is the l1 norm (signed observables)
     int64_t opt_state_order = 1;          // 1: use kfsp_set_state_coords for large, long-lived generators (0: never)
     int64_t opt_ssa_general = 0;          // 1: the SSA walk always runs its general kernel (A/B of the register-resident one)
@@ -433,6 +436,16 @@ int group_set_propensity_program(kfsp_ctx *h, int32_t ns, int32_t nr, int32_t np
                                  const int32_t *code, const int32_t *imm_off, const double *imm, const int32_t *tab_species,
                                  int32_t tab_len, const double *tab);
 kfsp_ctx *group_rank0(const kfsp_ctx *h);
+// several vectors at once on a head (option block_partition): whole arrays and global sizes in and out; 4002 when the
+// ranks disagree on a scalar
+int group_set_block(kfsp_ctx *h, int32_t k, int64_t n, int64_t ldw, const double *W);
+int group_get_block(kfsp_ctx *h, int32_t k, int64_t n, int64_t ldw, double *W);
+int group_spmm(kfsp_ctx *h, int32_t k, int64_t ld, const double *X, double *Y);
+int group_block_begin(kfsp_ctx *h, int m, double *beta);
+int group_block_arnoldi(kfsp_ctx *h, int m, double break_tol, double *hb, double *nrm, int *brk, double *avnorm);
+int group_block_combine(kfsp_ctx *h, int mx, const double *coef, double *wsum);
+int group_block_info(kfsp_ctx *h, int64_t *v);
+int group_spmm_bench(kfsp_ctx *h, int reps, float *ms_total);
 // generator build on the device from the reference layout (kfsp_build.hip)
 // keep: leading columns whose OFFDIAG / DIAG are resident and unchanged (only the rest is uploaded)
 int build_from_ell_device(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, const int32_t *adj,
@@ -498,9 +511,13 @@ int comm_allgather(kfsp_ctx *ctx, const double *send, double *recv, size_t count
 int comm_allgather_bytes(kfsp_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st);
 // the neighbours' boundary strips into the margins of the source column; the whole source column visible before a product
 // (*xg: where global index 0 lies); after a generator was set: agree across ranks on the exchange mode
-int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st);
+int exchange_strips(kfsp_ctx *ctx, const double *src_local, hipStream_t st, int width = 1);
 int gather_source(kfsp_ctx *ctx, const double *src_local, const double **xg);
 int setup_exchange(kfsp_ctx *ctx);
+// host array (this rank's block of the caller's order) <-> device vector of the internal order (kfsp_api.cpp); under the
+// internal state order and a communicator one all-gather each, so every rank calls them in the same order
+int upload_states(kfsp_ctx *ctx, const double *host, double *dev, int64_t count);
+int download_states(kfsp_ctx *ctx, const double *dev, double *host, int64_t count);
 // (re)size everything that depends on the number of states (kfsp_api.cpp)
 int resize(kfsp_ctx *ctx, int64_t n);
 // SSA walk + one-step sweep on the resident lists (kfsp_expand.hip)

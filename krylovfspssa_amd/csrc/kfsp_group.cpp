@@ -582,6 +582,97 @@ int group_set_propensity_tables2(kfsp_ctx *h, int32_t nr, const int32_t *s1, con
 
 kfsp_ctx *group_rank0(const kfsp_ctx *h) { return h->group->sub[0]; }
 
+// ---- several vectors at once (kfsp_block.hip, option block_partition): the head hands every rank its row block of the
+// caller's arrays and answers with the scalars all ranks agree on
+namespace {
+constexpr int kBK = 16;   // kBlockMaxK: entries per row of every per-column scalar array
+}
+
+int group_set_block(kfsp_ctx *h, int32_t k, int64_t n, int64_t ldw, const double *W)
+{
+    if (n != h->n) return gfail(h, -3, "n is not the number of states of the generator");
+    if (ldw < n) return gfail(h, -4, "ldw < n");
+    if (!W) return gfail(h, -5, "null W");
+    return gall(h, [&](kfsp_ctx *c, int p) {
+        const Block b = block_of(h, n, p);
+        return kfsp_set_block(c, k, b.nrows, ldw, W + b.row0);      // column j of the rank's rows starts at W[row0 + j ldw]
+    });
+}
+
+int group_get_block(kfsp_ctx *h, int32_t k, int64_t n, int64_t ldw, double *W)
+{
+    if (n != h->n) return gfail(h, -3, "n is not the number of states of the generator");
+    if (ldw < n) return gfail(h, -4, "ldw < n");
+    if (!W) return gfail(h, -5, "null W");
+    return gall(h, [&](kfsp_ctx *c, int p) {
+        const Block b = block_of(h, n, p);
+        return kfsp_get_block(c, k, b.nrows, ldw, W + b.row0);
+    });
+}
+
+int group_spmm(kfsp_ctx *h, int32_t k, int64_t ld, const double *X, double *Y)
+{
+    if (!Y) return gfail(h, -5, "null Y");
+    return gall(h, [&](kfsp_ctx *c, int p) { return kfsp_spmm(c, k, ld, X, Y + block_of(h, h->n, p).row0); });
+}
+
+int group_block_begin(kfsp_ctx *h, int m, double *beta)
+{
+    Group *g = h->group;
+    std::vector<double> b((size_t)g->n * kBK, 0.0);
+    if (int rc = gall(h, [&](kfsp_ctx *c, int p) { return kfsp_block_begin(c, m, &b[(size_t)p * kBK]); })) return rc;
+    for (int p = 1; p < g->n; ++p)
+        if (!same_bits(&b[0], &b[(size_t)p * kBK], kBK)) return gfail(h, 4002, "ranks disagree on the betas of a block");
+    std::memcpy(beta, b.data(), kBK * sizeof(double));
+    return 0;
+}
+
+int group_block_arnoldi(kfsp_ctx *h, int m, double break_tol, double *hb, double *nrm, int *brk, double *avnorm)
+{
+    Group *g = h->group;
+    const size_t nh = (size_t)(kMMax + 2) * 3 * kBK, nn = (size_t)(kMMax + 3) * kBK, np = (size_t)g->n;
+    std::vector<double> H(np * nh, 0.0), N(np * nn, 0.0), A(np * kBK, 0.0);
+    std::vector<int> B(np * kBK, 0);
+    if (int rc = gall(h, [&](kfsp_ctx *c, int p) {
+            return kfsp_block_arnoldi(c, m, break_tol, &H[(size_t)p * nh], &N[(size_t)p * nn], &B[(size_t)p * kBK], &A[(size_t)p * kBK]);
+        }))
+        return rc;
+    for (size_t p = 1; p < np; ++p)
+        if (!same_bits(&H[0], &H[p * nh], nh) || !same_bits(&N[0], &N[p * nn], nn) || !same_bits(&A[0], &A[p * kBK], kBK) ||
+            std::memcmp(&B[0], &B[p * kBK], kBK * sizeof(int)) != 0)
+            return gfail(h, 4002, "ranks disagree on the Hessenberg bands of a block");
+    std::memcpy(hb, H.data(), nh * sizeof(double));
+    std::memcpy(nrm, N.data(), nn * sizeof(double));
+    std::memcpy(avnorm, A.data(), kBK * sizeof(double));
+    std::memcpy(brk, B.data(), kBK * sizeof(int));
+    return 0;
+}
+
+int group_block_combine(kfsp_ctx *h, int mx, const double *coef, double *wsum)
+{
+    Group *g = h->group;
+    std::vector<double> ws((size_t)g->n * kBK, 0.0);
+    if (int rc = gall(h, [&](kfsp_ctx *c, int p) { return kfsp_block_combine(c, mx, coef, &ws[(size_t)p * kBK]); })) return rc;
+    for (int p = 1; p < g->n; ++p)
+        if (!same_bits(&ws[0], &ws[(size_t)p * kBK], kBK)) return gfail(h, 4002, "ranks disagree on the WSUMs of a block");
+    std::memcpy(wsum, ws.data(), kBK * sizeof(double));
+    return 0;
+}
+
+// how the last block calls ran: rank 0 answers (the exchange is agreed; the launch counts are the same on every rank)
+int group_block_info(kfsp_ctx *h, int64_t *v) { return kfsp_block_info(h->group->sub[0], v); }
+
+int group_spmm_bench(kfsp_ctx *h, int reps, float *ms_total)
+{
+    Group *g = h->group;
+    std::vector<float> ms((size_t)g->n, 0.f);
+    if (int rc = gall(h, [&](kfsp_ctx *c, int p) { return kfsp_spmm_bench(c, reps, &ms[(size_t)p]); })) return rc;
+    float t = 0.f;
+    for (float x : ms) t = std::max(t, x);
+    *ms_total = t;
+    return 0;
+}
+
 int group_layout_info(const kfsp_ctx *h, int64_t *v)
 {
     // format, exchange and halo of rank 0 (agreed by all ranks); reach = max, chunks / coded chunks / code words = sums

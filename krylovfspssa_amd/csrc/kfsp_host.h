@@ -72,6 +72,34 @@ inline int product_grid(int64_t trips, int64_t opt_grid, int64_t dflt_cap)
     return (int)std::max<int64_t>(std::min<int64_t>(round_up((trips + 3) / 4, 8), cap), 8);
 }
 
+// ---- the split of a product under the halo exchange, single vector (run_product) and block (kfsp_block.hip) alike
+// A rank's block has L rows and reads H rows of either neighbour; a trip covers trip_rows rows.  Trips [lo, hi) read no
+// halo row: lo is the first trip whose rows all lie >= H, trips below hi end at or below L - H.  They are launched on
+// their own, while the strips travel, only when that pays: three launches and two cross-stream waits cost ~10-15 us, so
+// the interior must be several times longer (>= 16384 trips, ~2M rows per rank) - or the caller insists (option
+// overlap = 2, used by the tests: >= 64 trips).  overlap = 0: never.
+struct ProductSplit {
+    int64_t lo, hi;
+    bool split;
+};
+inline ProductSplit product_split(int64_t H, int64_t L, int64_t trips, int64_t trip_rows, int64_t overlap)
+{
+    ProductSplit s;
+    s.lo = (H + trip_rows - 1) / trip_rows;
+    s.hi = std::min<int64_t>((L - H) / trip_rows, trips);
+    s.split = overlap != 0 && s.hi - s.lo >= (overlap >= 2 ? 64 : 16384);
+    return s;
+}
+
+// Rows of margin on either side of every basis column once strips of H rows are exchanged (setup_exchange): the strip,
+// a quarter of head room, and 128 rows because the banded kernel works on 128-row groups whose padded half reads up to
+// one group beyond the block end.  A multiple of 64.
+inline int64_t halo_margin(int64_t H) { return round_up(H + H / 4 + 2 * kChunk, 64); }
+// ... and of a block column (kfsp_block.hip): the context's margin, never less than the 64 zero rows the one-rank block
+// path has always had round its columns.
+constexpr int64_t kBlockMargin = 64;
+inline int64_t block_margin(int64_t ctx_margin) { return std::max<int64_t>(kBlockMargin, ctx_margin); }
+
 // Streaming kernels over `pairs` 16-byte pairs: every consumer re-sums the producer's partials, so the grid is kept at
 // <= 1024 workgroups (4 per CU; option vec_grid_blocks) with >= 4 pairs per lane; the loops are unrolled so that this
 // still keeps > 16 MB of loads in flight.

@@ -676,19 +676,26 @@ class KfspContext:
         return dict(zip(T_NAMES, t.tolist()))
 
     # -- several vectors at once
+    def _block_rows(self):
+        """rows of a block on this context: the rank's nloc; one rank and a head hold all n"""
+        return getattr(self, "nloc", self.n)
+
     def set_block(self, W):
         """k start vectors as the columns of W (shape n x k, 1 <= k <= 16), caller's state order.
-        Stored generators; a matrix-free box (set_matrix_box(..., store=False)) only after set_option("block_box", 1)."""
-        Wf, k = _block_columns(W, self.n)
-        self._chk(self._lib.kfsp_set_block(self._h, k, self.n, self.n, _p(Wf)), "kfsp_set_block")
+        Stored generators; a matrix-free box (set_matrix_box(..., store=False)) only after set_option("block_box", 1).
+        On a rank of a row partition (set_option("block_partition", 1) first): this rank's nloc rows, as in set_vector."""
+        nloc = self._block_rows()
+        Wf, k = _block_columns(W, nloc)
+        self._chk(self._lib.kfsp_set_block(self._h, k, nloc, max(nloc, 1), _p(Wf)), "kfsp_set_block")
         self.block_k = k
 
     def get_block(self):
         k = getattr(self, "block_k", 0)
         if not 1 <= k <= BLOCK_K_MAX:
             raise KfspError("no block was set on this context")
-        W = np.empty((self.n, k), dtype=np.float64, order="F")
-        self._chk(self._lib.kfsp_get_block(self._h, k, self.n, self.n, _p(W)), "kfsp_get_block")
+        nloc = self._block_rows()
+        W = np.empty((nloc, k), dtype=np.float64, order="F")
+        self._chk(self._lib.kfsp_get_block(self._h, k, nloc, max(nloc, 1), _p(W)), "kfsp_get_block")
         return W
 
     def _with_block_options(self, call, adjoint, clamp):
@@ -710,12 +717,14 @@ class KfspContext:
 
     def spmm(self, X, adjoint=False):
         """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j]) - also on a
-        matrix-free box under set_option("block_box", 1).  adjoint=True: A^T X (option "adjoint" round the call)."""
+        matrix-free box under set_option("block_box", 1).  adjoint=True: A^T X (option "adjoint" round the call).
+        On a rank of a row partition X is the whole block (n rows) and the rank's nloc rows of A X come back, as in spmv."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
         self._with_block_options(lambda: self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm"),
                                  adjoint, True)
-        return Y
+        nloc = self._block_rows()
+        return Y if nloc == self.n else np.asfortranarray(Y[:nloc])
 
     def expv_block(self, t, tol, m=30, adjoint=False, clamp=True):
         """W <- exp(t A) W for the resident block -> (wsum[k], BlockStats).  adjoint=True: the backward solve
@@ -773,8 +782,8 @@ class KfspContext:
         """how the last block calls ran (kfsp_block_info)"""
         v = np.zeros(8, dtype=np.int64)
         self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info")
-        return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes", "adjoint"),
-                        (int(x) for x in v[:7])))
+        return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes", "adjoint", "exchange"),
+                        (int(x) for x in v[:8])))
 
     def spmm_bench(self, reps):
         """ms for reps block products on the resident block"""
