@@ -14,7 +14,11 @@ subnormal numbers cannot enter a comparison.
 
 The second half restates one row of the TRANSPOSED block product Y = A^T X (option adjoint) for each of the three forms
 the generator can be resident in, as the header of kfsp_block_adj.hip defines them: banded_t_exact, ell_t_exact,
-box_t_exact.  fma() does not carry the sign of a zero result, so a result that is zero here is compared by value."""
+box_t_exact.  fma() does not carry the sign of a zero result, so a result that is zero here is compared by value.
+
+The third part restates one row of the FORWARD matrix-free product, which sums a row in orders no stored form has:
+box_exact (the single-factor fast path, kernel formats 4, 6, 7, 8 and k_spmm_box) and box_generic_exact (the interpreted
+kernel, format 3, and the generator option box_store has the device write out)."""
 from fractions import Fraction
 
 
@@ -174,6 +178,129 @@ def box_t_exact(mdl, X, descending=False):
             row.append(fma(-dsum, X[r][c], acc))
         Y.append(row)
     return Y
+
+
+# ---- the forward matrix-free rows (y = A x on a box that stores no entries) -------------------------------------------
+# Two definitions, because the device has two: the single-factor fast path (formats 4, 6, 7, 8 and k_spmm_box; header of
+# rows_box1 in kfsp_kernels.hip, header of row_box_blk in kfsp_block.hip) groups a row's entries by species and applies
+# the diagonal LAST; the interpreted kernel (format 3, row_box) and the generator that box_store writes out
+# (k_box_materialize, then an ordinary banded product) take the entries by sorted position and the diagonal FIRST.  Each
+# is split in two: *_rows lists, per row, the entries in the promised order and the double that stands for DIAG - no
+# arithmetic on x; *_exact does the fused multiply-adds.  The keyword flags are WRONG kernels, used only to show that a
+# test case can tell them from the right one (tests/test_row_ref.py).
+def _box_geometry(mdl, row0, nloc):
+    stoich, offsets = _lists(mdl.stoich), [int(o) for o in _lists(mdl.offsets)]
+    dims, strides = list(mdl.dims), [int(s) for s in _lists(mdl.strides)]
+    return stoich, offsets, dims, strides, (mdl.n - row0 if nloc is None else nloc)
+
+
+def box_rows(mdl, row0=0, nloc=None, by_position=False, tie_swapped=False, shares_reversed=False):
+    """single-factor box -> per local row ([(a, source)] in species-then-slot order, dsum).  Slot order: box_slots (ascending
+    source offset delta_k = -offsets[k], ties by reaction: the host's fill order).  a = table_k[c_s - nu_k[s]] when the
+    source state c - nu_k lies in the box in EVERY species, else the entry is (0.0, the row itself).  dsum = share_0 +
+    share_1 + ... in species order, share_s the sum from 0.0, in slot order, of table_k[c_s].
+    Wrong: by_position - the entries in format 3's order (sorted position, whatever the species); tie_swapped - equal
+    offsets within a species filled in descending reaction order; shares_reversed - the shares added last species first."""
+    stoich, offsets, dims, strides, nloc = _box_geometry(mdl, row0, nloc)
+    slots = box_slots(mdl)
+    if tie_swapped:
+        slots = [sorted(sp, key=lambda e: (-offsets[e[0]], -e[0])) for sp in slots]
+    out = []
+    for g in range(row0, row0 + nloc):
+        c = [(g // strides[s]) % dims[s] for s in range(mdl.d)]
+        ent, shares = [], []
+        for s in range(mdl.d):
+            share = 0.0
+            for k, table in slots[s]:
+                share += table[c[s]]
+                inside = all(0 <= c[q] - stoich[q][k] < dims[q] for q in range(mdl.d))
+                ent.append((k, table[c[s] - stoich[s][k]], g - offsets[k]) if inside else (k, 0.0, g))
+            shares.append(share)
+        if by_position:
+            ent.sort(key=lambda e: (-offsets[e[0]], e[0]))
+        if shares_reversed:
+            shares = shares[::-1]
+        dsum = shares[0]
+        for share in shares[1:]:
+            dsum += share
+        out.append(([(a, src) for _, a, src in ent], dsum))
+    return out
+
+
+def box_exact(mdl, x, row0=0, nloc=None, diag_first=False, **wrong):
+    """formats 4, 6, 7, 8 and every column of k_spmm_box: acc = +0.0; one fma(a, x[source], acc) per entry of box_rows;
+    then y = fma(-dsum, x[r], acc).  x is the whole vector, the result the local rows [row0, row0 + nloc).
+    Wrong: diag_first - the accumulator starts at -(dsum x[r]) (one rounded multiply) and nothing follows the entries;
+    the flags of box_rows."""
+    x = _lists(x)
+    y = []
+    for r, (ent, dsum) in enumerate(box_rows(mdl, row0, nloc, **wrong)):
+        acc = -(dsum * x[row0 + r]) if diag_first else 0.0
+        for a, src in ent:
+            acc = fma(a, x[src], acc)
+        y.append(acc if diag_first else fma(-dsum, x[row0 + r], acc))
+    return y
+
+
+def box_generic_rows(mdl, row0=0, nloc=None, by_species=False, tie_swapped=False, factors_reversed=False):
+    """any box with 1-3 factors per propensity -> per local row ([(a, source)] by sorted position, dsum).  a_k at
+    coordinates z is ((t_0[z] t_1[z]) t_2[z]), every multiply rounded, the factors in the order model.factors() lists
+    them.  dsum: the sum from 0.0 of a_k(c) in the MODEL's reaction order.  Entries: ascending delta_k = -offsets[k],
+    stable by reaction; the value is a_k at the source coordinates c - nu_k when the source lies in the box (row_box
+    reuses a_k(c) where no factor species moves: the same look-ups, the same bits), else (0.0, the row itself).
+    Wrong: by_species - the entries grouped by the species of their first factor, as the fast path has them;
+    tie_swapped - equal offsets in descending reaction order; factors_reversed - the factors multiplied last first
+    (shows only with three factors: a product of two commutes)."""
+    stoich, offsets, dims, strides, nloc = _box_geometry(mdl, row0, nloc)
+    ndep, dep, tab = mdl.factors()
+    ndep, dep, tab = _lists(ndep), _lists(dep), _lists(tab)
+    at, tables = 0, []
+    for k in range(mdl.R):
+        tables.append([])
+        for i in range(ndep[k]):
+            tables[k].append(tab[at:at + dims[dep[k][i]]])
+            at += dims[dep[k][i]]
+
+    def a_k(k, z):
+        fac = [tables[k][i][z[dep[k][i]]] for i in range(ndep[k])]
+        if factors_reversed:
+            fac = fac[::-1]
+        a = fac[0]
+        for t in fac[1:]:
+            a = a * t
+        return a
+
+    order = sorted(range(mdl.R), key=lambda k: (-offsets[k], -k if tie_swapped else k))
+    if by_species:
+        order = sorted(order, key=lambda k: dep[k][0])
+    out = []
+    for g in range(row0, row0 + nloc):
+        c = [(g // strides[s]) % dims[s] for s in range(mdl.d)]
+        dsum = 0.0
+        for k in range(mdl.R):
+            dsum += a_k(k, c)
+        ent = []
+        for k in order:
+            z = [c[q] - stoich[q][k] for q in range(mdl.d)]
+            inside = all(0 <= z[q] < dims[q] for q in range(mdl.d))
+            ent.append((a_k(k, z), g - offsets[k]) if inside else (0.0, g))
+        out.append((ent, dsum))
+    return out
+
+
+def box_generic_exact(mdl, x, row0=0, nloc=None, diag_last=False, **wrong):
+    """format 3 and the product of the generator box_store writes out: s = -(dsum x[r]) as ONE rounded multiply, then one
+    fma(a, x[source], s) per entry of box_generic_rows.  Where no two reactions share an offset this is spmv_exact over
+    the box's CSR rows; with a shared offset spmv_exact would order the pair by value, the device by reaction.
+    Wrong: diag_last - from +0.0, the diagonal as a closing fma(-dsum, x[r], s); the flags of box_generic_rows."""
+    x = _lists(x)
+    y = []
+    for r, (ent, dsum) in enumerate(box_generic_rows(mdl, row0, nloc, **wrong)):
+        s = 0.0 if diag_last else -(dsum * x[row0 + r])
+        for a, src in ent:
+            s = fma(a, x[src], s)
+        y.append(fma(-dsum, x[row0 + r], s) if diag_last else s)
+    return y
 
 
 def reverse_from(rows, cap):

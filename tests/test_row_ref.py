@@ -1,11 +1,15 @@
 """tests/row_ref.py, the plain restatement of one row of the product, checked without a device: against row sums in
 extended precision, against the oracle's product at the tolerance the device tests use - and that every case of
 tests/test_gpu_build_rows.py can tell a wrong order from the right one (a comparison of bits that no wrong order
-would change proves nothing)."""
+would change proves nothing).  The same for the forward matrix-free rows (box_exact, box_generic_exact) and the
+cases of tests/test_gpu_box_rows.py."""
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
 from tests import adjoint_cases as AC
+from tests import box_cases as BC
 from tests import row_cases as RC
 from tests import row_ref as RR
 from tests.test_block_adjoint_host import banded_form, banded_t, bound, box_t, ell_t
@@ -224,3 +228,186 @@ def test_the_small_boxes_reach_their_edges():
     assert np.abs(AC.model("box_four_slot_6x4").stoich).max() == 2
     slots = {name: RR.box_slots(AC.model(name)) for name in AC.BOXES}
     assert [(len(s), max(map(len, s))) for s in slots.values()] == [(2, 2), (3, 2), (6, 2), (2, 4), (1, 2)]
+
+
+# ---- the forward matrix-free rows (box_exact: formats 4 / 6 / 7 / 8 and k_spmm_box; box_generic_exact: format 3, box_store) -----
+U = 2.0 ** -53
+# which wrong kernel a case can show, and why the others cannot: (function, flag) -> the cases it applies to
+SEVERAL_SPECIES = tuple(n for n in BC.SMALL if n != "box_one_species")        # one species: both entry orders are the same order
+# one or two species (the instantiation's padding species share 0.0): a sum of two shares commutes
+THREE_SHARES = ("box_repressilator_3x2", "box_birth_death_6x2", "decode_49x4x3", "decode_8x49x2", "decode_2x49x2x2x2x2")
+CAN_TELL = {
+    ("box_exact", "diag_first"): BC.SMALL,
+    ("box_exact", "by_position"): SEVERAL_SPECIES,
+    ("box_exact", "tie_swapped"): ("dup_12x9",),                             # no other case has two slots on one offset
+    ("box_exact", "shares_reversed"): THREE_SHARES,
+    ("box_generic_exact", "diag_last"): BC.SMALL + BC.NAMED_GENERIC,
+    ("box_generic_exact", "by_species"): SEVERAL_SPECIES + BC.NAMED_GENERIC,
+    ("box_generic_exact", "tie_swapped"): ("dup_12x9",),
+    ("box_generic_exact", "factors_reversed"): ("three_factor",),            # a product of two factors commutes
+}
+
+
+def test_forward_box_rows_by_hand():
+    """birth at rate 2, death at rate x on {0, 1, 2}: slot order is ascending source offset - the birth (from r - 1)
+    before the death (from r + 1); every number exact, so both definitions give the same"""
+    from krylovfspssa_amd import synth
+    mdl = synth.BoxModel("by hand", (3,), [[1, -1]], lambda r, X: np.full_like(X[0], 2.0) if r == 0 else 1.0 * X[0], deps=[(0,), (0,)])
+    x = [1.0, 10.0, 100.0]
+    assert RR.box_rows(mdl) == [([(0.0, 0), (1.0, 1)], 2.0), ([(2.0, 0), (2.0, 2)], 3.0), ([(2.0, 1), (0.0, 2)], 4.0)]
+    assert RR.box_generic_rows(mdl) == RR.box_rows(mdl)
+    assert RR.box_exact(mdl, x) == [8.0, 172.0, -380.0] == RR.box_generic_exact(mdl, x)
+    assert RR.box_exact(mdl, x, row0=1, nloc=2) == [172.0, -380.0] == RR.box_generic_exact(mdl, x, row0=1, nloc=2)
+    for wrong in ("diag_first", "by_position", "tie_swapped", "shares_reversed"):
+        assert RR.box_exact(mdl, x, **{wrong: True}) == [8.0, 172.0, -380.0]
+    for wrong in ("diag_last", "by_species", "tie_swapped", "factors_reversed"):
+        assert RR.box_generic_exact(mdl, x, **{wrong: True}) == [8.0, 172.0, -380.0]
+
+
+def _exactly_rounded(rows, x):
+    """per row: the Fraction sum of the listed entries and of -dsum x[r], rounded ONCE; sum |a| |x|; present entries"""
+    y, mag, cnt = [], [], []
+    for r, (ent, dsum) in enumerate(rows):
+        t = -Fraction(dsum) * Fraction(x[r])
+        m = abs(dsum * x[r])
+        for a, src in ent:
+            t += Fraction(a) * Fraction(x[src])
+            m += abs(a * x[src])
+        y.append(float(t))
+        mag.append(m)
+        cnt.append(sum(a != 0.0 for a, _ in ent))
+    return np.array(y), np.array(mag), np.array(cnt)
+
+
+@pytest.mark.parametrize("name", BC.all_names())
+def test_box_restatements_against_the_exactly_rounded_row(name):
+    """Both restatements round once per present entry (an fma of 0.0 adds nothing) and once for the diagonal term, each
+    time by at most 2^-53 of a partial sum that sum |a| |x| bounds; the exactly rounded row adds half a rounding: within
+    (entries + 2) 2^-53 sum |a| |x| of it.  The LISTS the arithmetic runs over are checked against the model itself: the
+    off-diagonal entries are synth's gather rows (the same bits with one factor per propensity - a table IS the
+    propensity - and to a few roundings of the factor product otherwise) and dsum is DIAG; the two definitions list the
+    same entries, in two orders, and their dsum differ by the roundings of R - 1 additions each."""
+    c = BC.case(name)
+    mdl, x = c["mdl"], c["x"].tolist()
+    single = name in BC.FAST
+    assert np.abs(c["x"]).min() >= 0.5 and np.abs(c["x"]).max() <= 1.5 and (c["x"] < 0).any() and (c["x"] > 0).any()
+    rows_g = RR.box_generic_rows(mdl)
+    y, mag, cnt = _exactly_rounded(rows_g, x)
+    assert np.all(np.abs(c["yg"] - y) <= (cnt + 2) * U * mag)
+    cols, vals = mdl.rows_at(np.arange(mdl.n, dtype=np.int64))
+    big = np.iinfo(np.int64).max
+    for r, (ent, dsum) in enumerate(rows_g):
+        want = sorted((int(cc), float(v)) for cc, v in zip(cols[r], vals[r]) if cc != big and cc != r)
+        got = sorted((src, a) for a, src in ent if src != r)
+        diag = -float(vals[r][list(cols[r]).index(r)])
+        if single:
+            assert got == want and dsum == diag, (name, r)
+        else:
+            assert [s for s, _ in got] == [s for s, _ in want]
+            assert np.allclose([a for _, a in got], [a for _, a in want], rtol=3e-15, atol=0.0)
+            assert abs(dsum - diag) <= 3e-15 * diag
+    if not single:
+        return
+    rows_f = RR.box_rows(mdl)
+    y, mag, cnt = _exactly_rounded(rows_f, x)
+    assert np.all(np.abs(c["y"] - y) <= (cnt + 2) * U * mag)
+    for r, ((ef, df), (eg, dg)) in enumerate(zip(rows_f, rows_g)):
+        assert sorted(e for e in ef if e[1] != r) == sorted(e for e in eg if e[1] != r)
+        assert abs(df - dg) <= 2 * (mdl.R - 1) * U * max(df, dg)
+    # the two definitions against each other: each within its bound of its own exact row, and the two exact rows differ
+    # by (dsum_fast - dsum_generic) x[r]
+    dd = np.array([abs(df - dg) for (_, df), (_, dg) in zip(rows_f, rows_g)])
+    assert np.all(np.abs(c["y"] - c["yg"]) <= 2 * (cnt + 2) * U * mag + dd * np.abs(c["x"]) * (1 + U))
+
+
+@pytest.mark.parametrize("name", [n for n in BC.FAST if n != "dup_12x9"])
+def test_the_generic_box_row_is_the_stored_row_where_no_offsets_tie(name):
+    """single-factor boxes whose reactions have distinct offsets: sorted position IS ascending source, so
+    box_generic_exact must be spmv_exact over the box's CSR rows, on the bits - also for a row block"""
+    c = BC.case(name)
+    mdl = c["mdl"]
+    assert len(set(mdl.offsets.tolist())) == mdl.R
+    rows, diag = RR.rows_from_csr(mdl.n, *mdl.csr_rows())
+    assert RR.spmv_exact(rows, diag, c["x"]) == c["yg"].tolist()
+    if name in BC.SMALL:
+        r0, nl = mdl.n // 3 + 1, mdl.n // 2
+        assert RR.box_generic_exact(mdl, c["x"], row0=r0, nloc=nl) == c["yg"][r0:r0 + nl].tolist()
+        assert RR.box_exact(mdl, c["x"], row0=r0, nloc=nl) == c["y"][r0:r0 + nl].tolist()
+
+
+def test_tied_offsets_need_a_definition_of_their_own():
+    """dup_12x9: two births per species on ONE offset.  spmv_exact's rule - by source, then by VALUE - puts the smaller rate
+    first; the device goes by reaction.  The two disagree on the bits, which is why box_generic_exact is no spmv_exact."""
+    c = BC.case("dup_12x9")
+    mdl = c["mdl"]
+    assert len(set(mdl.offsets.tolist())) == mdl.R - 2
+    rows, diag = RR.rows_from_csr(mdl.n, *mdl.csr_rows())
+    by_value = [sorted(row) for row in rows]
+    assert sum(a != b for a, b in zip(by_value, rows)) >= 20
+    changed = len(BC.mismatches(np.array(RR.spmv_exact(by_value, diag, c["x"])), c["yg"]))
+    print(f"dup_12x9: by source then value changes {changed} of {mdl.n} rows")
+    assert changed >= 10
+    slots = RR.box_slots(mdl)
+    assert [[k for k, _ in sp] for sp in slots] == [[0, 1, 2], [3, 4, 5]]       # the births (from r - stride) by reaction, then the death
+
+
+@pytest.mark.parametrize("fn,flag", list(CAN_TELL))
+def test_every_forward_box_case_can_tell_a_wrong_kernel(fn, flag):
+    """each wrong variant changes the bits of >= 10 rows of every case it applies to - and of NO row of a case it is
+    said not to apply to (one species; two shares; no tied offsets; at most two factors), which is the reason stated
+    in CAN_TELL.  The loop_* boxes repeat four of these models at a larger size and the random models are breadth, not
+    edges: neither is asked to tell."""
+    names = BC.SMALL + (BC.NAMED_GENERIC if fn == "box_generic_exact" else ())
+    ref = "y" if fn == "box_exact" else "yg"
+    for name in names:
+        c = BC.case(name)
+        z = np.array(getattr(RR, fn)(c["mdl"], c["x"], **{flag: True}))
+        changed = len(BC.mismatches(z, c[ref]))
+        print(f"{fn}({flag}) on {name}: {changed} of {c['n']} rows change")
+        if name in CAN_TELL[(fn, flag)]:
+            assert changed >= 10, (name, fn, flag, changed)
+        else:
+            assert changed == 0, (name, fn, flag, changed)
+
+
+def test_the_decode_boxes_take_the_correction_step():
+    """the kernel's formula in numpy: rows whose decode comes out one short and takes r >= d.  The r < 0 step needs a
+    quotient estimate that is one too LARGE, which q * (1 / d) gives only for q near 2^31: it stays untested at these
+    sizes (no box here has a row that takes it)."""
+    counts = {name: BC.decode_corrections(BC.model(name)) for name in BC.FAST}
+    print(counts)
+    assert [counts[n] for n in BC.DECODE] == [(7, 0), (8, 0), (22, 0), (4, 0)]
+    assert all(lo == 0 for _, lo in counts.values())
+    assert all(hi >= 4 for n, (hi, _) in counts.items() if n in BC.DECODE)
+    # ... also inside the row blocks of the partition tests' boxes nothing else turns up
+    assert 49.0 * (1.0 / 49.0) < 1.0
+
+
+def test_the_forward_box_cases_reach_their_edges():
+    from krylovfspssa_amd import host
+    for name in BC.FAST:
+        assert BC.instance_of(BC.model(name)) == BC.INSTANCE[name], name
+    assert {BC.INSTANCE[n] for n in BC.SMALL} == {BC.INSTANCE[n] for n in BC.LOOP} == {(2, 2), (3, 2), (6, 2), (6, 4)}
+    assert all(BC.model(n).n <= 1600 for n in BC.SMALL + BC.generic_names())
+    fmts = {n: (BC.pencil_format(BC.model(n), 1), BC.pencil_format(BC.model(n), 2)) for n in BC.SMALL}
+    assert fmts["decode_49x4x3"] == (7, 7) and fmts["decode_8x49x2"] == (7, 8) and fmts["decode_2x49x2x2x2x2"] == (7, 8)
+    assert fmts["box_birth_death_6x2"] == (7, 8) and fmts["box_repressilator_3x2"] == (4, 4)       # planes of 143 rows
+    assert all(f == (4, 4) for n, f in fmts.items() if BC.model(n).d < 3)
+    # grid_blocks = 8: a workgroup's share of the trips is more than its four wavefronts only on the loop boxes
+    for name in BC.FAST:
+        share = -(-(-(-BC.model(name).n // 128)) // 8)
+        assert (share > 4) == (name in BC.LOOP), (name, share)
+    gm = BC.model("goutsias")
+    assert gm.n == 720 and sorted(map(len, gm.deps)).count(2) == 2 and (np.count_nonzero(gm.stoich, axis=0) == 3).any()
+    assert sorted(map(len, BC.model("three_factor").deps)) == [1, 1, 2, 3, 3]
+    assert len(BC.generic_names()) >= 6
+    # the row partition: blocks of 64-row multiples; one case whose blocks are shorter than its reach (no halo strips:
+    # the all-gather), every case with a ragged last block
+    for name, P, gather in BC.PARTITIONED:
+        mdl = BC.model(name)
+        blocks = [host.partition(mdl.n, P, r) for r in range(P)]
+        L = blocks[0][2]
+        reach = int(np.abs(mdl.offsets).max())
+        assert all(nr > 0 for _, nr, _ in blocks) and blocks[-1][1] % 64 != 0 and blocks[-1][1] < L
+        assert (-(-reach // 8) * 8 > L) == gather, (name, P, reach, L)
+    assert any(g for _, _, g in BC.PARTITIONED) and not all(g for _, _, g in BC.PARTITIONED)
