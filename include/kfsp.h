@@ -511,12 +511,50 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
  *   scalar; the step loop of kfsp_expv_block runs once, on the head's thread; kfsp_block_info answers for rank 0.
  * w is never touched and a generator change discards the block, as on one context.  A device allocation that fails on
  * one rank only is not agreed on: that rank returns its error and the others are released by the transport's deadline
- * (or a head's watchdog). */
+ * (or a head's watchdog).
+ * TIME INTEGRALS.  Option "block_integral" (default 0: nothing below exists - no byte of any result, no launch and no
+ * allocation differs) keeps beside the block W a second resident block J of the same shape, the time integral of the
+ * solution.  1: kfsp_set_block allocates J and fills it with +0.0; after every ACCEPTED step of kfsp_expv_block
+ *   J <- J + int_0^tau exp(sA) W_step ds      (tau the accepted step, W_step the block the step started from),
+ * so that after solves over t_1, t_2, ... J = int_0^T exp(sA) W_0 ds with T = t_1 + t_2 + ... (J accumulates across calls
+ * until the next kfsp_set_block zeroes it).  It is the integral of the trajectory the solver actually takes, clamps between
+ * steps included, and J itself is never clamped.  W, wsum, kfsp_block_stats and the step sizes are the same bits with the
+ * option on and off: the option does not enter the step control.  2: everything 1 means, and kfsp_get_block answers with J
+ * instead of W (same k, n, ldw, state order and row-block conventions; set 2 round the call and 1 again after it).
+ * Two meanings.  Forward, J_c = int_0^T p(s) ds is the OCCUPATION MEASURE of column c: the expected time spent in each
+ * state up to T (time-averaged distributions; "how long was the switch on").  Backward ("adjoint" = 1, usually with
+ * "block_clamp" = 0), for a column g (a function of the state)
+ *   J(x) = int_0^T exp(s A^T) g ds = E[ int_0^min(T, exit) g(X_s) ds | X_0 = x ]    for every start state x at once:
+ * the ACCUMULATED OBSERVABLE - with g = 1 the mean exit / first-passage time truncated at T (the number that belongs
+ * beside the exit probability 1 - exp(T A^T) 1), with g = a propensity the expected number of firings of that reaction,
+ * with g = a count an accumulated reward.
+ * How.  A step holds per column beta, the basis V and the augmented Hessenberg matrix Hbar of order MBRKDWN + K1, and
+ * exp(tau A) w ~ beta V exp(tau Hbar) e_1.  The same basis gives int_0^tau exp(sA) w ds = tau phi_1(tau A) w ~
+ * beta V [tau phi_1(tau Hbar) e_1], and tau phi_1(tau Hbar) e_1 is the top of the last column of exp(tau [[Hbar, e_1],
+ * [0, 0]]): one more host Pade (kfsp_padm, order <= 103, timed under KFSP_T_HOST_PADE) per column and accepted step,
+ * none for rejected trial steps, no generator product, no extra launch - the combine kernel applies both linear
+ * combinations in its one pass over the basis.  Rows MBRKDWN + MAX(0, K1 - 1) are used, as for W; a column with A v_1 = 0
+ * gets exactly tau e_1, a column with beta = 0 stays exactly +0.0, a column that broke down is integrated on its exact H.
+ * kfsp_block_combine reads, with the option on, a SECOND table behind the first: rows [mx, 2 mx) of coef (16 doubles each),
+ * and J_c <- J_c + sum_{i < mx} coef[(mx + i) * 16 + c] u_{i+1,c} (one fused multiply-add per i, ascending, starting from
+ * the old J element); wsum stays 16 entries and is W's.  kfsp_block_info reports the same launch counts as without.
+ * Lifetime: J lives and dies with the block (a generator change discards both; w is never touched).  With the option on
+ * but no J resident - it was 0 when kfsp_set_block ran - kfsp_expv_block, kfsp_block_combine and kfsp_get_block (value 2)
+ * return -1 and the message names block_integral and kfsp_set_block.  Every other block option combines with it
+ * ("adjoint", "block_clamp", "block_box", "block_small", "block_partition": J is per-rank rows like W, no new collective,
+ * a group head forwards the option), because the combine does not know which operator filled the basis.
+ * ACCURACY.  J has no step control of its own.  A step's error in J is the integral over [0, tau] of the Krylov error of
+ * exp(sA) w, at most tau times the error the accepted step is allowed; so J inherits about T times the bound of W.  This
+ * is an argument, not a guarantee.  Measured on the CPU restatement against dense integrals (three small generators,
+ * forward and transposed, m = 30 and 10): l1(J - J_dense) / (T l1(w_0)) <= 1.1e-12 at tol = 1e-8 and <= 7.3e-10 at tol =
+ * 1e-5 ("Time integrals").  Not provided: a Fortran binding, a J-driven step control, an error estimate
+ * for J through this ABI. */
 /* k start vectors (1 <= k <= 16), W column-major host memory W[j*ldw + i], i in the caller's order (the internal state
  * order is applied as in kfsp_set_vector); n = the number of states of the generator (a rank of a row partition: its
  * nlocal rows, see ROW PARTITIONS) */
 int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W);
-/* the resident block back; k must be the k of kfsp_set_block.  -1 when no block is resident */
+/* the resident block back; k must be the k of kfsp_set_block.  -1 when no block is resident.  Option "block_integral" = 2:
+ * J, the time integral kept beside the block, instead of W (-1 when none is resident) */
 int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W);
 /* Y = A X for k host columns X[j*ld + i] (ld >= n), Y alike; column j is BIT-IDENTICAL to kfsp_spmv of column j (every
  * column of a row is summed in FMATVEC's order, KrylovSolver.f90:598-604).  Leaves the resident block alone. */
@@ -544,7 +582,8 @@ int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total);
  *   hb[(j * 3 + t) * 16 + c], j = 1..m, t = 0, 1, 2: H(j-1,j), H(j,j), H(j+1,j) of column c (102 * 3 * 16 doubles);
  *   nrm[j * 16 + c] = ||u_j||, j = 1..m+1 (103 * 16 doubles); brk[c] = 0, or j when H(j+1,j) <= break_tol ended column
  *   c after its column j (its later entries are 0), or -1 for a column with beta = 0; avnorm[c] = ||A v_{m+1}||.
- * kfsp_block_combine: W_c = max(sum_{i < mx} coef[i * 16 + c] u_{i+1,c}, 0) and wsum[c] = ||W_c||_1; mx <= m + 2.
+ * kfsp_block_combine: W_c = max(sum_{i < mx} coef[i * 16 + c] u_{i+1,c}, 0) and wsum[c] = ||W_c||_1; mx <= m + 2.  With
+ *   option "block_integral" on, coef holds 2 mx rows and rows [mx, 2 mx) update J in the same pass (TIME INTEGRALS above).
  * Option "block_small" = 1 (default 0): where kfsp_arnoldi would take its one-launch pass - at most 4096 rows, a banded
  * or plain (not coded) SELL image, no box, communicator or group, options small_kernel and fused_ortho on - each of the
  * three is ONE launch of one 1024-lane workgroup per block column, and H, the norms and AVNORM of a column are the
@@ -693,7 +732,9 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
- * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
+ * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_integral" (1: kfsp_set_block keeps J, the time integral of the block,
+ * beside it and every accepted step of kfsp_expv_block adds to it; 2: the same and kfsp_get_block answers with J; 0, default: nothing changes;
+ * see TIME INTEGRALS under "several vectors at once"), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
  * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other

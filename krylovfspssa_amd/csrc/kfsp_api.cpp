@@ -2224,6 +2224,10 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "block_partition") ctx->opt_block_partition = value != 0;
     else if (k == "adjoint") ctx->opt_adjoint = value != 0;
     else if (k == "block_clamp") ctx->opt_block_clamp = value != 0;
+    else if (k == "block_integral") {
+        if (value < 0 || value > 2) return fail(ctx, -3, "block_integral is 0, 1 or 2");
+        ctx->opt_block_integral = value;
+    }
     else if (k == "box_pencil") ctx->opt_box_pencil = value;
     else if (k == "box_slab_waves") ctx->opt_box_slab_waves = value;
     else if (k == "sell_code") ctx->opt_sell_code = value;

@@ -40,6 +40,11 @@
 // collectives of a call depends on k, m, the options and the agreed exchange mode only - never on a column's beta, its
 // breakdown or the rows a rank owns.  Still refused (-12): option adjoint (the transposed banded product reads the
 // neighbour's generator rows) and matrix-free boxes; block_small is not taken (small_path excludes partitions).
+//
+// Time integrals (option block_integral; DESIGN.md 12, "Time integrals").  While the option is on kfsp_set_block keeps a
+// second block J of the block's shape (d_bint, +0.0) and block_combine takes kernels of its own, k_bcombine_int /
+// k_bcombine_small_int: the pass over the basis that makes W also adds a second linear combination (the table behind coef,
+// kfsp_block_integral.h) to J.  With the option off neither the kernels above nor any allocation or launch changes.
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
@@ -443,6 +448,38 @@ __global__ __launch_bounds__(kBlock) void k_bcombine(int64_t npairs, int half, c
     flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
 }
 
+// k_bcombine, and beside it J <- J + sum_i cj_i u_i (option block_integral: the time integral of the step from the same
+// basis).  Per element one pass over j: u is loaded once and feeds two fma chains - s from +0.0 (then W's clamp), r from the
+// old J element, j ascending, never clamped.  The partials are those of W alone, summed as k_bcombine sums them.
+__global__ __launch_bounds__(kBlock) void k_bcombine_int(int64_t npairs, int half, const double *__restrict__ U, int64_t ldc, int mx,
+                                                         const double *__restrict__ coef, const double *__restrict__ cj,
+                                                         d2 *__restrict__ w, d2 *__restrict__ jint, double *__restrict__ part, int clamp)
+{
+    __shared__ double red[8 * K];
+    const int q = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) % half);
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
+        d2 s = {0.0, 0.0};
+        d2 r = jint[i];
+        for (int j = 0; j < mx; ++j) {
+            const d2 u = reinterpret_cast<const d2 *>(U + (size_t)j * ldc)[i];
+            s.x = __builtin_fma(coef[j * K + 2 * q], u.x, s.x);
+            s.y = __builtin_fma(coef[j * K + 2 * q + 1], u.y, s.y);
+            r.x = __builtin_fma(cj[j * K + 2 * q], u.x, r.x);
+            r.y = __builtin_fma(cj[j * K + 2 * q + 1], u.y, r.y);
+        }
+        if (clamp) {
+            s.x = s.x > 0.0 ? s.x : 0.0;
+            s.y = s.y > 0.0 ? s.y : 0.0;
+        }
+        w[i] = s;
+        jint[i] = r;
+        a0 += clamp ? s.x : __builtin_fabs(s.x);
+        a1 += clamp ? s.y : __builtin_fabs(s.y);
+    }
+    flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
+}
+
 // caller's column-major block (stage[c * n + i]) -> row-interleaved rows of the internal order, and back
 // (lds: doubles between the columns of stage, >= n)
 __global__ __launch_bounds__(kBlock) void k_bpack(int64_t n, int k, int kp, const double *__restrict__ stage, int64_t lds,
@@ -591,6 +628,32 @@ __global__ __launch_bounds__(kSmallBlock) void k_bcombine_small(int nact, int kp
         for (int j = 0; j < mx; ++j) s = __builtin_fma(coef[j * K + c], U[(size_t)j * ldc + r * kp + c], s);
         if (clamp) s = s > 0.0 ? s : 0.0;
         w[r * kp + c] = s;
+        a += clamp ? s : __builtin_fabs(s);
+    }
+    const double s0 = small_sum(a, red);
+    if (threadIdx.x == 0) sc[kWS + c] = s0;
+}
+
+// k_bcombine_small and the J update of k_bcombine_int: per element the same operations in the same order
+__global__ __launch_bounds__(kSmallBlock) void k_bcombine_small_int(int nact, int kp, const double *__restrict__ U, int64_t ldc, int mx,
+                                                                    const double *__restrict__ coef, const double *__restrict__ cj,
+                                                                    double *__restrict__ w, double *__restrict__ jint,
+                                                                    double *__restrict__ sc, int clamp)
+{
+    __shared__ double red[kSmallBlock / 64];
+    const int c = blockIdx.x;
+    double a = 0.0;
+    for (int r = threadIdx.x; r < nact; r += kSmallBlock) {
+        double s = 0.0;
+        double v = jint[r * kp + c];
+        for (int j = 0; j < mx; ++j) {
+            const double u = U[(size_t)j * ldc + r * kp + c];
+            s = __builtin_fma(coef[j * K + c], u, s);
+            v = __builtin_fma(cj[j * K + c], u, v);
+        }
+        if (clamp) s = s > 0.0 ? s : 0.0;
+        w[r * kp + c] = s;
+        jint[r * kp + c] = v;
         a += clamp ? s : __builtin_fabs(s);
     }
     const double s0 = small_sum(a, red);
@@ -972,6 +1035,9 @@ void block_release(kfsp_ctx *ctx)
     ctx->d_bscal.release();
     ctx->d_bpart.release();
     ctx->d_bxg.release();
+    ctx->d_bint.release();
+    ctx->d_bcj.release();
+    ctx->blk_int = false;
     ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->bxg_kp = ctx->blk_begin_m = 0;
     std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
     std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
@@ -1033,6 +1099,16 @@ int block_mmax(kfsp_ctx *ctx)
 {
     ctx = lead(ctx);
     return (int)(ctx->v_mmax ? std::min(ctx->v_mmax, ctx->opt_mmax) : ctx->opt_mmax);
+}
+
+int block_integral(kfsp_ctx *ctx, int *on)
+{
+    const kfsp_ctx *l = lead(ctx);
+    *on = l->opt_block_integral != 0;
+    if (*on && !l->blk_int)
+        return fail(ctx, -1, "option block_integral is on but the resident block has no integral beside it: set the option "
+                             "before kfsp_set_block");
+    return 0;
 }
 
 int block_begin(kfsp_ctx *ctx, int m, double *beta)
@@ -1132,7 +1208,26 @@ int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
     const int kp = ctx->blk_kp;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(ctx->d_bscal.p + kCMB, coef, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
-    if (small_path(ctx)) {
+    if (ctx->opt_block_integral) {
+        // the same launches with the kernels that carry J along: rows [mx, 2 mx) of coef are J's table
+        if (!ctx->blk_int) return fail(ctx, -1, "option block_integral: no integral resident (set the option before kfsp_set_block)");
+        HIP_TRY(hipMemcpyAsync(ctx->d_bcj.p, coef + (size_t)mx * K, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
+        if (small_path(ctx)) {
+            hipLaunchKernelGGL(k_bcombine_small_int, dim3(kp), dim3(kSmallBlock), 0, st, (int)(ctx->nchunks * kChunk), kp,
+                               bcol(ctx->d_bv.p, ctx, kp, 0), (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, ctx->d_bcj.p,
+                               bcol(ctx->d_blk.p, ctx, kp, 0), bcol(ctx->d_bint.p, ctx, kp, 0), ctx->d_bscal.p,
+                               ctx->opt_block_clamp ? 1 : 0);
+            ctx->blk_info[4] = 1;
+        } else {
+            const int g = flat_grid(ctx, kp);
+            hipLaunchKernelGGL(k_bcombine_int, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
+                               (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, ctx->d_bcj.p,
+                               reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bint.p, ctx, kp, 0)),
+                               ctx->d_bpart.p, ctx->opt_block_clamp ? 1 : 0);
+            if (int rc = finalize(ctx, kFinWsum, 0, kp, g)) return rc;
+            ctx->blk_info[4] = 2;
+        }
+    } else if (small_path(ctx)) {
         hipLaunchKernelGGL(k_bcombine_small, dim3(kp), dim3(kSmallBlock), 0, st, (int)(ctx->nchunks * kChunk), kp,
                            bcol(ctx->d_bv.p, ctx, kp, 0), (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB,
                            bcol(ctx->d_blk.p, ctx, kp, 0), ctx->d_bscal.p, ctx->opt_block_clamp ? 1 : 0);
@@ -1178,14 +1273,26 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
         const int kp = kp_of(k);
         if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         ctx->blk_k = ctx->blk_begin_m = 0;
+        ctx->blk_int = false;
         if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
             ctx->d_blk.release();
+            ctx->d_bint.release();
             HIP_TRY(ctx->d_blk.reserve(col_len(ctx, kp), false));
+        }
+        // J (option block_integral) lives and dies with the block: the same shape, +0.0 everywhere
+        if (ctx->opt_block_integral) {
+            HIP_TRY(ctx->d_bint.reserve(col_len(ctx, kp), false));
+            HIP_TRY(hipMemsetAsync(ctx->d_bint.p, 0, col_len(ctx, kp) * sizeof(double), ctx->stream));
+            HIP_TRY(ctx->d_bcj.reserve((size_t)(kMMax + 3) * K, true));
+        } else {
+            ctx->d_bint.release();
+            ctx->d_bcj.release();
         }
         ctx->blk_kp = kp;
         if (int rc = upload_block(ctx, k, kp, ldw, W, bcol(ctx->d_blk.p, ctx, kp, 0))) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->blk_k = k;
+        ctx->blk_int = ctx->opt_block_integral != 0;
         return 0;
     });
 }
@@ -1197,6 +1304,10 @@ int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W)
         if (int rc = block_supported(ctx)) return rc;
         if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
         if (k != lead(ctx)->blk_k) return fail(ctx, -2, "k is not the number of columns of the resident block");
+        // option block_integral = 2: the answer is J, by the route W takes
+        const bool want_j = lead(ctx)->opt_block_integral == 2;
+        if (want_j)
+            if (int on = 0; int rc = block_integral(ctx, &on)) return rc;
         if (ctx->group) return group_get_block(ctx, k, n, ldw, W);
         if (ctx->use_comm) {
             if (n != ctx->nloc) return fail(ctx, -3, "n is not this rank's block size");
@@ -1208,7 +1319,7 @@ int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W)
             if (!W) return fail(ctx, -5, "null W");
         }
         HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = download_block(ctx, k, ctx->blk_kp, bcol(ctx->d_blk.p, ctx, ctx->blk_kp, 0), ldw, W)) return rc;
+        if (int rc = download_block(ctx, k, ctx->blk_kp, bcol(want_j ? ctx->d_bint.p : ctx->d_blk.p, ctx, ctx->blk_kp, 0), ldw, W)) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return 0;
     });
@@ -1285,6 +1396,7 @@ int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *ws
         if (mx < 1 || mx > lead(ctx)->blk_begin_m + 2) return fail(ctx, -2, "bad mx (need 1 <= mx <= m + 2 of kfsp_block_begin)");
         if (!coef) return fail(ctx, -4, "null coef");
         if (!wsum) return fail(ctx, -5, "null wsum");
+        if (int on = 0; int rc = block_integral(ctx, &on)) return rc;
         return block_combine(ctx, mx, coef, wsum);
     });
 }

@@ -330,6 +330,9 @@ struct kfsp_ctx {
     int64_t blk_info[8] = {};    // kfsp_block_info: how the last block_begin / block_arnoldi / block_combine ran
     int blk_box_occ[4][2] = {};  // workgroups of k_spmm_box resident per CU, by [log2 kp - 1][dots] (0: not asked yet)
     int blk_box_t_occ[4][2] = {};   // the same for k_spmm_box_t (kfsp_block_adj.hip)
+    DevBuf<double> d_bint, d_bcj;   // option block_integral: J, the time integral of the resident block (laid out like d_blk), and
+                                    // its coefficient table; allocated by kfsp_set_block while the option is on, never otherwise
+    bool blk_int = false;           // J is resident beside the block
 
     // scalars
     DevBuf<double> d_part;   // kNumPartial * kMaxGrid
@@ -383,6 +386,8 @@ struct kfsp_ctx {
     int64_t opt_adjoint = 0;              // 1: the block calls multiply with A^T (kfsp_block_adj.hip): backward solves exp(tA^T) F
     int64_t opt_block_partition = 0;      // 1: the block calls run under a row partition (communicator, loop-back rank, group head); 0: -12
     int64_t opt_block_clamp = 1;          // 0: the block combine does not clamp at 0 and wsum is the l1 norm (signed observables)
+    int64_t opt_block_integral = 0;       // 1: kfsp_set_block keeps J = the time integral of the block beside it and the combine updates both;
+                                          // 2: the same, and kfsp_get_block answers with J
     int64_t opt_state_order = 1;          // 1: use kfsp_set_state_coords for large, long-lived generators (0: never)
     int64_t opt_ssa_general = 0;          // 1: the SSA walk always runs its general kernel (A/B of the register-resident one)
     int64_t opt_keep_coords = 0;          // 1: coordinates handed over stay resident even when no order is derived from them

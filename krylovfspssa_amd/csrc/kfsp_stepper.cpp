@@ -17,6 +17,7 @@
 // choice is the one carried out; differences are reported as kfsp_fork entries.
 #include "../../include/kfsp.h"
 #include "kfsp_block.h"
+#include "kfsp_block_integral.h"
 
 #include <algorithm>
 #include <chrono>
@@ -615,10 +616,30 @@ int expv_block_impl(kfsp_ctx *ctx, double t, double tol, int32_t m_in, double *w
     const double krytol = tol <= eps ? std::sqrt(eps) : tol;
     const double rndoff = eps;
 
+    // option block_integral: J <- J + int_0^tau exp(sA) W ds beside every accepted step, from the step's own bases.  It
+    // enters nothing below but the second coefficient table of the combine.
+    int integral = 0;
+    if (int rc = kfsp::block_integral(ctx, &integral)) return rc;
+
     const int mh = m + 2;
     std::vector<double> hb((size_t)(kMMax + 2) * 3 * kBK), nrm((size_t)(kMMax + 3) * kBK), avn(kBK), beta(kBK), ws(kBK, 0.0);
     std::vector<double> H((size_t)mh * mh), E((size_t)k * mh * mh), coef((size_t)(m + 2) * kBK);
     std::vector<int> brk(kBK), mbrk(k), k1(k);
+    std::vector<double> gint, gwork;
+    if (integral) {
+        coef.resize((size_t)2 * (m + 2) * kBK);
+        gint.resize((size_t)mh);
+    }
+    // column c's augmented Hessenberg matrix of this pass, order mbrk + k1, into H (column-major, leading dimension mh)
+    auto build_h = [&](int c) {
+        std::fill(H.begin(), H.end(), 0.0);
+        for (int j = 1; j <= mbrk[c]; ++j) {
+            if (j >= 2) H[(size_t)(j - 1) * mh + (j - 2)] = hb[(size_t)(j * 3 + 0) * kBK + c];
+            H[(size_t)(j - 1) * mh + (j - 1)] = hb[(size_t)(j * 3 + 1) * kBK + c];
+            if (j < mbrk[c] || k1[c] != 0) H[(size_t)(j - 1) * mh + j] = hb[(size_t)(j * 3 + 2) * kBK + c];
+        }
+        H[(size_t)m * mh + (m + 1)] = 1.0;                    // :266
+    };
     int rc = 0;
     unsigned broke = 0;
 
@@ -660,13 +681,7 @@ int expv_block_impl(kfsp_ctx *ctx, double t, double tol, int32_t m_in, double *w
             for (int c = 0; c < k; ++c) {
                 if (brk[c] < 0) continue;                     // beta = 0
                 const int mx = mbrk[c] + k1[c];
-                std::fill(H.begin(), H.end(), 0.0);
-                for (int j = 1; j <= mbrk[c]; ++j) {
-                    if (j >= 2) H[(size_t)(j - 1) * mh + (j - 2)] = hb[(size_t)(j * 3 + 0) * kBK + c];
-                    H[(size_t)(j - 1) * mh + (j - 1)] = hb[(size_t)(j * 3 + 1) * kBK + c];
-                    if (j < mbrk[c] || k1[c] != 0) H[(size_t)(j - 1) * mh + j] = hb[(size_t)(j * 3 + 2) * kBK + c];
-                }
-                H[(size_t)m * mh + (m + 1)] = 1.0;            // :266
+                build_h(c);
                 double *Ec = E.data() + (size_t)c * mh * mh;
                 bool null_h = true;                           // A v_1 = 0 (an absorbing state): exp(t H) = I, which
                 for (int j = 0; j < mx && null_h; ++j)        // DGPADM refuses as 'null H' (dgpadm.f:84)
@@ -722,6 +737,20 @@ int expv_block_impl(kfsp_ctx *ctx, double t, double tol, int32_t m_in, double *w
             mxc = std::max(mxc, mx);
             const double *Ec = E.data() + (size_t)c * mh * mh;
             for (int i = 0; i < mx; ++i) coef[(size_t)i * kBK + c] = beta[c] * Ec[i] / nrm[(size_t)(i + 1) * kBK + c];
+        }
+        if (integral) {
+            // J's table behind W's: g_c = tau phi_1(tau Hbar_c) e_1 for the accepted tau, scaled like coef
+            std::fill(coef.begin() + (size_t)mxc * kBK, coef.begin() + (size_t)2 * mxc * kBK, 0.0);
+            for (int c = 0; c < k; ++c) {
+                if (brk[c] < 0) continue;
+                const int mx = mbrk[c] + std::max(0, k1[c] - 1);
+                build_h(c);
+                const auto t0 = std::chrono::steady_clock::now();
+                rc = kfsp::block_integral_column(kIdeg, mbrk[c] + k1[c], mx, t_step, H.data(), mh, gint.data(), gwork);
+                kfsp_add_timer(ctx, KFSP_T_HOST_PADE, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+                if (rc) return 3000 - rc;
+                for (int i = 0; i < mx; ++i) coef[(size_t)(mxc + i) * kBK + c] = beta[c] * gint[i] / nrm[(size_t)(i + 1) * kBK + c];
+            }
         }
         if ((rc = kfsp::block_combine(ctx, mxc, coef.data(), ws.data()))) return rc;
         t_now += t_step;

@@ -683,19 +683,36 @@ class KfspContext:
     def set_block(self, W):
         """k start vectors as the columns of W (shape n x k, 1 <= k <= 16), caller's state order.
         Stored generators; a matrix-free box (set_matrix_box(..., store=False)) only after set_option("block_box", 1).
-        On a rank of a row partition (set_option("block_partition", 1) first): this rank's nloc rows, as in set_vector."""
+        On a rank of a row partition (set_option("block_partition", 1) first): this rank's nloc rows, as in set_vector.
+        With set_option("block_integral", 1) in force, a second block J of the same shape is kept beside W, zeroed here:
+        every accepted step of expv_block adds int_0^tau exp(sA) W_step ds to it (get_block(integral=True))."""
         nloc = self._block_rows()
         Wf, k = _block_columns(W, nloc)
         self._chk(self._lib.kfsp_set_block(self._h, k, nloc, max(nloc, 1), _p(Wf)), "kfsp_set_block")
         self.block_k = k
 
-    def get_block(self):
+    def get_block(self, integral=False):
+        """The resident block W, n x k in the caller's state order.  integral=True: J instead, the time integral
+        int_0^T exp(sA) W_0 ds accumulated over every expv_block since set_block (T = the sum of their t) - forward the
+        occupation measure (expected time spent in each state), backward (adjoint=True) the accumulated observable
+        E[int_0^min(T, exit) g(X_s) ds | X_0 = x], for g = 1 the truncated mean exit time.  Needs
+        set_option("block_integral", 1) before set_block; the option is set to 2 round the call and put back.  J has no
+        step control of its own: about T times the error bound of W (include/kfsp.h, TIME INTEGRALS)."""
         k = getattr(self, "block_k", 0)
         if not 1 <= k <= BLOCK_K_MAX:
             raise KfspError("no block was set on this context")
         nloc = self._block_rows()
         W = np.empty((nloc, k), dtype=np.float64, order="F")
-        self._chk(self._lib.kfsp_get_block(self._h, k, nloc, max(nloc, 1), _p(W)), "kfsp_get_block")
+        call = lambda: self._chk(self._lib.kfsp_get_block(self._h, k, nloc, max(nloc, 1), _p(W)), "kfsp_get_block")
+        if not integral:
+            call()
+            return W
+        old = getattr(self, "_options", {}).get("block_integral", 0)
+        self.set_option("block_integral", 2)
+        try:
+            call()
+        finally:
+            self.set_option("block_integral", old)
         return W
 
     def _with_block_options(self, call, adjoint, clamp):
@@ -730,7 +747,9 @@ class KfspContext:
         """W <- exp(t A) W for the resident block -> (wsum[k], BlockStats).  adjoint=True: the backward solve
         W <- exp(t A^T) W, E[f(X_t); still inside the FSP | X_0 = x] for every state x and observable column f;
         clamp=False: columns are not clamped at 0 after a step (signed observables) and wsum is their l1 norm.  Both are
-        the options "adjoint" / "block_clamp", set round the call and put back to forward / clamped."""
+        the options "adjoint" / "block_clamp", set round the call and put back to forward / clamped.
+        Under set_option("block_integral", 1) (in force since before set_block) every accepted step also adds its time
+        integral to J (get_block(integral=True)); W, wsum and the statistics are the same bits with and without."""
         k = getattr(self, "block_k", 0)
         if not 1 <= k <= BLOCK_K_MAX:
             raise KfspError("no block was set on this context")
@@ -766,14 +785,22 @@ class KfspContext:
                   "kfsp_block_arnoldi")
         return hb[:m + 1, :, :k].copy(), nrm[:m + 2, :k].copy(), brk[:k].copy(), avn[:k].copy()
 
-    def block_combine(self, mx, coef):
-        """W_c = max(sum_{i < mx} coef[i, c] u_{i+1,c}, 0) for the resident block -> wsum[k]"""
+    def block_combine(self, mx, coef, coef_integral=None):
+        """W_c = max(sum_{i < mx} coef[i, c] u_{i+1,c}, 0) for the resident block -> wsum[k] (of W).
+        Under option "block_integral" the library reads a second table behind the first, and in the same pass
+        J_c += sum_{i < mx} coef_integral[i, c] u_{i+1,c} (never clamped); coef_integral=None leaves J as it is (a table of
+        zeros).  With the option off the second table is not read."""
         k = self._block_k()
         coef = np.asarray(coef, dtype=np.float64)
         if coef.ndim != 2 or coef.shape[0] < mx or coef.shape[1] != k:
             raise ValueError(f"coef must have shape (>= {mx}, {k}), got {coef.shape}")
-        cf = np.zeros((int(mx), BLOCK_K_MAX), dtype=np.float64)
-        cf[:, :k] = coef[:mx]
+        cf = np.zeros((2 * int(mx), BLOCK_K_MAX), dtype=np.float64)
+        cf[:mx, :k] = coef[:mx]
+        if coef_integral is not None:
+            cj = np.asarray(coef_integral, dtype=np.float64)
+            if cj.ndim != 2 or cj.shape[0] < mx or cj.shape[1] != k:
+                raise ValueError(f"coef_integral must have shape (>= {mx}, {k}), got {cj.shape}")
+            cf[mx:, :k] = cj[:mx]
         ws = np.zeros(BLOCK_K_MAX, dtype=np.float64)
         self._chk(self._lib.kfsp_block_combine(self._h, int(mx), _p(cf), _p(ws)), "kfsp_block_combine")
         return ws[:k].copy()
