@@ -468,6 +468,18 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
  * single-factor form (a propensity of several factors, a step of more than 2, more than 4 propensities on a species),
  * option box_generic = 1, a block so wide that an entry reaches more than 2^32 bytes (8 kp bytes per row of reach),
  * communicator and group contexts.  The options box_lds / box_pencil choose among single-vector kernels only.
+ * Option "block_box" = 2 takes EVERY matrix-free box kfsp_set_matrix_box takes.  0 and 1 mean what they always meant - in
+ * particular 1 still refuses a multi-factor box and option box_generic = 1 with -12.  With 2 a box that has the single-factor
+ * form takes the kernels of 1 (the same bits) unless box_generic = 1; every other box - a propensity of two or three
+ * factors (any bimolecular reaction), a step of more than 2, more than 4 propensities on a species, more than 6 species -
+ * and any box under box_generic = 1 takes the interpreted row of kernel format 3: coordinates, propensities and in-box
+ * tests once per row, applied to all columns; column j of kfsp_spmm is bit-identical to kfsp_spmv of column j (format
+ * 3).  Per column: s = -(DIAG x) with DIAG summed in the model's reaction order, then one fused multiply-add per
+ * reaction by ascending source offset - forward a_k(x - nu_k) against X at the source state, under "adjoint" a_k(x)
+ * against X at the target state x + nu_k; an entry outside the box is 0.0 against the row's own X.  X is addressed by
+ * 64-bit row index: there is no reach limit.  Every block call works on it (kfsp_set_block, kfsp_spmm, kfsp_block_*,
+ * kfsp_expv_block with "adjoint", "block_clamp" and "block_integral").  Still -12 with 2: communicator and group
+ * contexts, with or without "block_partition"; "block_small" is not taken, as for every box.
  * A block lives beside w (w is never touched) until the
  * generator changes: the next kfsp_set_matrix_* / kfsp_update_matrix_ell / kfsp_drop_compact / kfsp_expand_resident
  * discards it, and kfsp_get_block then fails.  On the device a block holds kp = k rounded up to 2, 4, 8 or 16 doubles
@@ -732,7 +744,7 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
- * take a matrix-free single-factor box, see "several vectors at once"; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_integral" (1: kfsp_set_block keeps J, the time integral of the block,
+ * take a matrix-free single-factor box, see "several vectors at once"; 2: every matrix-free box - multi-factor propensities, any jump, and any box under box_generic = 1 - through the interpreted row of format 3; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_integral" (1: kfsp_set_block keeps J, the time integral of the block,
  * beside it and every accepted step of kfsp_expv_block adds to it; 2: the same and kfsp_get_block answers with J; 0, default: nothing changes;
  * see TIME INTEGRALS under "several vectors at once"), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
  * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is

@@ -22,6 +22,10 @@
 // Matrix-free boxes (option block_box, k_spmm_box below; DESIGN.md 12, "Matrix-free boxes"): the row of a single-factor box is rebuilt
 // once - coordinates, {sum, valid} look-ups, one LDS read per entry - and applied to all kp columns, in the operation
 // order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_kernels.hip).
+// Multi-factor boxes (option block_box = 2; DESIGN.md 12, "Multi-factor boxes"): every other matrix-free box, and any box
+// under box_generic = 1, takes the interpreted row of kernel format 3 - k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t
+// (kfsp_block_adj.hip), the row code in kfsp_boxg_dev.h; box_generic_path() and spmm_boxg() below.  Values 0 and 1 of the
+// option mean what they always meant.
 //
 // Small generators (option block_small; DESIGN.md 12, "Small generators"): where the single-vector path takes its
 // one-launch pass (<= kSmallRows rows, a banded or plain SELL image, no partition), a block step is three launches of
@@ -765,8 +769,33 @@ int box_block_geometry(const kfsp_ctx *ctx, int kp, bool dots, int (&cache)[4][2
     return product_grid(a.trips, ctx->opt_grid, std::min<int64_t>(1024, (int64_t)256 * occ));
 }
 
+// Option block_box = 2: the generic kernels (k_spmm_boxg, kfsp_block_boxg.hip; k_spmm_boxg_t, kfsp_block_adj.hip) answer
+// for a box without the single-factor form and for any box under box_generic = 1.  Read at every block call.
+bool box_generic_path(const kfsp_ctx *c) { return c->use_box && c->opt_block_box == 2 && (!c->box_fast || c->opt_box_generic != 0); }
+
+// Their launch: box_block_geometry's rule with an occupancy cache of their own, less of the image staged (the head and
+// the factor tables only) and the descriptor by value behind SpmmArgs in the kernel's argument (BoxgArgs).  -1: the
+// descriptor is not one they can walk (block_supported refuses that first).
+int spmm_boxg(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
+{
+    const int32_t ntab = box_generic_image(ctx->box);
+    if (ntab == 0) return -1;
+    size_t lds = 0;
+    const int g = box_block_geometry(ctx, kp, dots, transposed ? ctx->blk_boxg_t_occ : ctx->blk_boxg_occ, [&](size_t) {
+        const size_t bytes = std::max<size_t>((size_t)ntab * sizeof(double), (size_t)4 * kp * sizeof(double));
+        return transposed ? spmm_boxg_t_resident(kp, dots, bytes) : spmm_boxg_resident(kp, dots, bytes);
+    }, a, &lds);
+    lds = std::max<size_t>((size_t)ntab * sizeof(double), (size_t)4 * kp * sizeof(double));
+    a.box_ntab = ntab;
+    a.box_fast = nullptr;
+    if (transposed) launch_spmm_boxg_t(kp, dots, g, lds, a, ctx->box, ctx->stream);
+    else launch_spmm_boxg(kp, dots, g, lds, a, ctx->box, ctx->stream);
+    return g;
+}
+
 int spmm_box(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
 {
+    if (box_generic_path(ctx)) return spmm_boxg(ctx, kp, dots, false, a);
     const SpmmBoxFn fn = spmm_box_fn(kp, ctx->box.pad, dots);
     size_t lds = 0;
     const int g = box_block_geometry(ctx, kp, dots, ctx->blk_box_occ, [&](size_t bytes) {
@@ -793,6 +822,7 @@ bool ell_adj_args(const kfsp_ctx *ctx, EllAdjDev &e)
 // generator is in no form the transposed product reads (block_supported refuses those first).
 int spmm_adjoint(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
 {
+    if (box_generic_path(ctx)) return spmm_boxg(ctx, kp, dots, true, a);
     if (ctx->use_box) {
         BoxAdjDev b;
         if (!box_adj_build(ctx->box, b)) return -1;
@@ -839,6 +869,8 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
     a.trip_jump = 0;
     ctx->blk_info[7] = 0;
     if (ctx->opt_adjoint || ctx->use_box) {
+        // (box_generic is read at every call: a block set under the generic kernels may meet the single-factor ones here)
+        if (ctx->use_box && !box_generic_path(ctx) && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         const int g = ctx->opt_adjoint ? spmm_adjoint(ctx, kp, dots, a) : spmm_box(ctx, kp, dots, a);
         if (g < 0) return fail(ctx, -12, kAdjFormMsg);
         *G = g;
@@ -1042,6 +1074,8 @@ void block_release(kfsp_ctx *ctx)
     std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
     std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
     std::memset(ctx->blk_box_t_occ, 0, sizeof(ctx->blk_box_t_occ));
+    std::memset(ctx->blk_boxg_occ, 0, sizeof(ctx->blk_boxg_occ));
+    std::memset(ctx->blk_boxg_t_occ, 0, sizeof(ctx->blk_boxg_t_occ));
 }
 
 // Every refusal below is made from what all ranks of a partition share (options, the kind of generator), before the
@@ -1073,6 +1107,12 @@ int block_supported(kfsp_ctx *ctx)
         if (!ctx->opt_block_box)
             return fail(ctx, -12, "several vectors at once: not for a matrix-free generator (option box_store = 1 stores it, "
                                   "option block_box = 1 takes it matrix-free)");
+        if (box_generic_path(ctx)) {
+            if (box_generic_image(ctx->box) == 0)
+                return fail(ctx, -12, "several vectors at once: the descriptor of this matrix-free box is not one the generic block "
+                                      "kernels can walk (option box_store = 1 stores it)");
+            return 0;
+        }
         if (ctx->opt_box_generic)
             return fail(ctx, -12, "several vectors at once: not for the interpreted matrix-free product (option box_generic = 1)");
         if (!ctx->box_fast)
@@ -1271,7 +1311,7 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
         }
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
-        if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
+        if (ctx->use_box && !box_generic_path(ctx) && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         ctx->blk_k = ctx->blk_begin_m = 0;
         ctx->blk_int = false;
         if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
@@ -1337,7 +1377,7 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         if (!Y && !(ctx->use_comm && ctx->nloc == 0)) return fail(ctx, -5, "null Y");
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
-        if (ctx->use_box && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
+        if (ctx->use_box && !box_generic_path(ctx) && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
         if (int rc = ensure_basis(ctx, kp, 2)) return rc;
         // under a row partition X is the whole block on every rank (the kfsp_spmv convention): it goes to the gathered
         // block buffer, global row 0 first, and no exchange follows

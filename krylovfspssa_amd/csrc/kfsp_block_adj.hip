@@ -13,12 +13,16 @@
 //   ELL      slots k ascending: OFFDIAG(k, r) X[ADJ(k, r)]; a missing target as 0.0 against the row's own X row;
 //   box      the accumulator starts at +0.0, one fma per slot in species-then-slot order with a_k(x) of the row's own
 //            coordinates and X row r + delta_k when x + nu_k lies in the box (else 0.0 against the row's own X row), then
-//            fma(-dsum, x_r, acc) - the shape of row_box_blk.
+//            fma(-dsum, x_r, acc) - the shape of row_box_blk;
+//   generic box (option block_box = 2, k_spmm_boxg_t; the row code is kfsp_boxg_dev.h's): s = -(dsum x_r) with dsum summed
+//            in the model's reaction order, then one fma per sorted position p ascending of a_p(x) of the row's own
+//            coordinates against X row r - delta_p when x + nu_p lies in the box (else 0.0 against the row's own X row).
 // The file is compiled with contraction off: column c of A^T X does not depend on k, kp or the slot it sits in.
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
 #include "kfsp_box_dev.h"
+#include "kfsp_boxg_dev.h"
 
 namespace kfsp {
 
@@ -274,6 +278,25 @@ SpmmBoxTFn spmm_box_t_fn(int kp, int inst, bool dots)
     }
 }
 
+// Any matrix-free box (option block_box = 2): the interpreted row, transposed.  The descriptor is the forward product's.
+template <int KP, bool DOTS>
+__global__ __launch_bounds__(kBlock) void k_spmm_boxg_t(BoxgArgs)
+{
+    spmm_boxg_body<KP, DOTS, true>();
+}
+
+typedef void (*SpmmBoxgFn)(BoxgArgs);
+
+SpmmBoxgFn spmm_boxg_t_fn(int kp, bool dots)
+{
+    switch (kp) {
+    case 2: return dots ? k_spmm_boxg_t<2, true> : k_spmm_boxg_t<2, false>;
+    case 4: return dots ? k_spmm_boxg_t<4, true> : k_spmm_boxg_t<4, false>;
+    case 8: return dots ? k_spmm_boxg_t<8, true> : k_spmm_boxg_t<8, false>;
+    default: return dots ? k_spmm_boxg_t<16, true> : k_spmm_boxg_t<16, false>;
+    }
+}
+
 }  // namespace
 
 void launch_spmm_t(int kp, bool dots, int grid, const SpmmArgs &a, hipStream_t st)
@@ -314,6 +337,18 @@ int spmm_box_t_resident(int kp, int inst, bool dots, size_t lds)
 void launch_spmm_box_t(int kp, int inst, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxAdjDev &b, hipStream_t st)
 {
     hipLaunchKernelGGL(spmm_box_t_fn(kp, inst, dots), dim3((unsigned)grid), dim3(kBlock), lds, st, a, b);
+}
+
+int spmm_boxg_t_resident(int kp, bool dots, size_t lds)
+{
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, spmm_boxg_t_fn(kp, dots), kBlock, lds) != hipSuccess) nb = 1;
+    return nb > 1 ? nb : 1;
+}
+
+void launch_spmm_boxg_t(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st)
+{
+    hipLaunchKernelGGL(spmm_boxg_t_fn(kp, dots), dim3((unsigned)grid), dim3(kBlock), lds, st, BoxgArgs{a, b});
 }
 
 }  // namespace kfsp

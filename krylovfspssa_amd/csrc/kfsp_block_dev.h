@@ -1,6 +1,7 @@
-// Private: what the two translation units of the block product share - kfsp_block.hip (Y = A X and everything behind
-// the product) and kfsp_block_adj.hip (Y = A^T X, option adjoint).  The row helpers, SpmmArgs and block_sum_cols are the
-// ones kfsp_block.hip always had; the descriptors at the end belong to the transposed product.
+// Private: what the translation units of the block product share - kfsp_block.hip (Y = A X and everything behind
+// the product), kfsp_block_adj.hip (Y = A^T X, option adjoint) and kfsp_block_boxg.hip (Y = A X on any matrix-free box,
+// option block_box = 2).  The row helpers, SpmmArgs and block_sum_cols are the ones kfsp_block.hip always had; the
+// descriptors at the end belong to the transposed product and to the generic matrix-free kernels.
 #pragma once
 
 #include "kfsp_block.h"
@@ -156,6 +157,42 @@ static inline bool box_adj_build(const BoxDev &B, BoxAdjDev &out)
     return true;
 }
 
+// The generic matrix-free block kernels (k_spmm_boxg / k_spmm_boxg_t, option block_box = 2) interpret BoxDev as
+// kfsp_set_matrix_box stored it and index the LDS image with it: the doubles of the image they read - the head and the
+// factor tables, not the single-factor form's species tables behind them - or 0 when the descriptor is not one they can
+// walk without leaving the image or their registers (sizes out of range, a species or a table outside the box or the
+// image, dorder no permutation of the sorted positions, a stoichiometry that does not match between the factor and the
+// move lists).
+static inline int32_t box_generic_image(const BoxDev &B)
+{
+    if (B.ns < 1 || B.ns > kBoxMaxS || B.nr < 1 || B.nr > kBoxMaxR || B.ntab < kBoxImageHead) return 0;
+    for (int s = 0; s < B.ns; ++s)
+        if (B.dims[s] < 1) return 0;
+    int32_t end = kBoxImageHead;
+    uint32_t seen = 0;
+    for (int p = 0; p < B.nr; ++p) {
+        if (B.ndep[p] < 1 || B.ndep[p] > kBoxMaxDep || B.nmov[p] < 0 || B.nmov[p] > kBoxMaxDep) return 0;
+        if (B.dorder[p] < 0 || B.dorder[p] >= B.nr || (seen >> B.dorder[p] & 1u)) return 0;
+        seen |= 1u << B.dorder[p];
+        for (int i = 0; i < B.nmov[p]; ++i) {
+            const int s = B.mov_s[p][i];
+            if (s < 0 || s >= B.ns || B.mov_dim[p][i] != B.dims[s] || B.mov_nu[p][i] == 0) return 0;
+        }
+        for (int i = 0; i < B.ndep[p]; ++i) {
+            const int s = B.dep_s[p][i];
+            if (s < 0 || s >= B.ns) return 0;
+            const int64_t last = (int64_t)B.dep_off[p][i] + B.dims[s];
+            if (B.dep_off[p][i] < kBoxImageHead || last > B.ntab) return 0;
+            end = last > end ? (int32_t)last : end;
+            int nu = 0;                                  // what the move list says of this species
+            for (int j = 0; j < B.nmov[p]; ++j)
+                if (B.mov_s[p][j] == s) nu = B.mov_nu[p][j];
+            if (B.dep_nu[p][i] != nu) return 0;
+        }
+    }
+    return end;
+}
+
 // The transposed SELL product reads the reference arrays: they must be the current generator's (n columns resident,
 // a leading dimension that holds the bw slots) and the buffers as long as that says.
 static inline bool ell_adj_resident(int64_t n, int64_t ell_cols, int32_t ell_ld, int32_t ell_bw, size_t cap_adj, size_t cap_off,
@@ -174,6 +211,12 @@ KFSP_LOCAL void launch_spmm_ell_t(int kp, bool dots, int grid, const SpmmArgs &a
 KFSP_LOCAL int spmm_box_t_resident(int kp, int inst, bool dots, size_t lds);
 KFSP_LOCAL void launch_spmm_box_t(int kp, int inst, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxAdjDev &b,
                                   hipStream_t st);
+// the generic matrix-free kernels (option block_box = 2): k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t
+// (kfsp_block_adj.hip); a.box_ntab doubles of the image are staged into `lds` bytes of dynamic LDS
+KFSP_LOCAL int spmm_boxg_resident(int kp, bool dots, size_t lds);
+KFSP_LOCAL void launch_spmm_boxg(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st);
+KFSP_LOCAL int spmm_boxg_t_resident(int kp, bool dots, size_t lds);
+KFSP_LOCAL void launch_spmm_boxg_t(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st);
 #undef KFSP_LOCAL
 
 }  // namespace kfsp

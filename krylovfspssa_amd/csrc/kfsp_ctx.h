@@ -330,6 +330,7 @@ struct kfsp_ctx {
     int64_t blk_info[8] = {};    // kfsp_block_info: how the last block_begin / block_arnoldi / block_combine ran
     int blk_box_occ[4][2] = {};  // workgroups of k_spmm_box resident per CU, by [log2 kp - 1][dots] (0: not asked yet)
     int blk_box_t_occ[4][2] = {};   // the same for k_spmm_box_t (kfsp_block_adj.hip)
+    int blk_boxg_occ[4][2] = {}, blk_boxg_t_occ[4][2] = {};   // ... for k_spmm_boxg (kfsp_block_boxg.hip) and k_spmm_boxg_t
     DevBuf<double> d_bint, d_bcj;   // option block_integral: J, the time integral of the resident block (laid out like d_blk), and
                                     // its coefficient table; allocated by kfsp_set_block while the option is on, never otherwise
     bool blk_int = false;           // J is resident beside the block
@@ -381,7 +382,8 @@ struct kfsp_ctx {
     int64_t opt_sell_code = -1;            // dictionary-coded SELL columns: -1 auto (under the internal state order), 0 never, 1 always try
     int64_t opt_dia_code = -1;             // dictionary-coded banded values: -1 auto (generators beyond the Infinity Cache), 0 never, 1 always try
     int64_t opt_box_store = 0;            // 1: kfsp_set_matrix_box writes the generator out as stored diagonals on the device (banded form)
-    int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12)
+    int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12);
+                                          // 2: as 1, and every other box (or any under box_generic) through k_spmm_boxg
     int64_t opt_block_small = 0;          // 1: the block path takes its one-launch kernels where the single-vector path takes k_arnoldi_small
     int64_t opt_adjoint = 0;              // 1: the block calls multiply with A^T (kfsp_block_adj.hip): backward solves exp(tA^T) F
     int64_t opt_block_partition = 0;      // 1: the block calls run under a row partition (communicator, loop-back rank, group head); 0: -12

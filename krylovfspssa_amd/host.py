@@ -682,7 +682,9 @@ class KfspContext:
 
     def set_block(self, W):
         """k start vectors as the columns of W (shape n x k, 1 <= k <= 16), caller's state order.
-        Stored generators; a matrix-free box (set_matrix_box(..., store=False)) only after set_option("block_box", 1).
+        Stored generators; a matrix-free box (set_matrix_box(..., store=False)) only after set_option("block_box", 1) -
+        single-factor boxes - or set_option("block_box", 2) - any box: propensities of two or three factors (bimolecular
+        reactions), jumps beyond 2, more than four propensities on a species, more than six species.
         On a rank of a row partition (set_option("block_partition", 1) first): this rank's nloc rows, as in set_vector.
         With set_option("block_integral", 1) in force, a second block J of the same shape is kept beside W, zeroed here:
         every accepted step of expv_block adds int_0^tau exp(sA) W_step ds to it (get_block(integral=True))."""
@@ -734,7 +736,8 @@ class KfspContext:
 
     def spmm(self, X, adjoint=False):
         """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j]) - also on a
-        matrix-free box under set_option("block_box", 1).  adjoint=True: A^T X (option "adjoint" round the call).
+        matrix-free box under set_option("block_box", 1), and on a multi-factor one (or any box under "box_generic" = 1)
+        under set_option("block_box", 2).  adjoint=True: A^T X (option "adjoint" round the call).
         On a rank of a row partition X is the whole block (n rows) and the rank's nloc rows of A X come back, as in spmv."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
@@ -819,7 +822,8 @@ class KfspContext:
         return ms.value
 
     def set_option(self, name, value):
-        """kfsp_set_option (include/kfsp.h lists the names), e.g. "block_box" = 1: the block calls take a matrix-free box."""
+        """kfsp_set_option (include/kfsp.h lists the names), e.g. "block_box" = 1: the block calls take a matrix-free single-factor box;
+        2: every matrix-free box (0 and 1 keep their meaning: a multi-factor box is still refused under 1)."""
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
         if not hasattr(self, "_options"):
             self._options = {}
