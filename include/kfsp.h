@@ -337,7 +337,8 @@ int kfsp_set_propensity_program(kfsp_ctx *ctx, int32_t ns, int32_t nr, int32_t n
  * kfsp_ssa_streams, kfsp_expand_resident - returns -16 and has changed nothing the caller can see (host outputs are to be
  * discarded; the resident lists still describe the FSP as it was); kfsp_propensity_overflow says which species went how
  * far; the caller sets larger tables (kfsp_set_propensity_program + this call) and repeats the operation - deterministic,
- * so the repeat is what a larger table would have given at once. */
+ * so the repeat is what a larger table would have given at once.  A later call replaces an earlier one; one in which no
+ * reaction has a table takes them all away. */
 int kfsp_set_propensity_tables2(kfsp_ctx *ctx, int32_t nr, const int32_t *s1, const int32_t *s2, const int32_t *n1, const int32_t *n2,
                                 const int64_t *off, int64_t len, const double *tab2);
 /* after a -16: max_missed[s] = the largest population of species s that lay beyond a table (0: none) */

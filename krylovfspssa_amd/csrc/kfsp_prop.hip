@@ -221,7 +221,10 @@ int prop_set_tables2(kfsp_ctx *ctx, int32_t nr, const int32_t *s1, const int32_t
         to[(size_t)k] = off[k];
         any = true;
     }
-    if (!any) return 0;
+    if (!any) {                           // (the call replaces what an earlier one set: no table now)
+        ctx->prop_has_tab2 = false;
+        return 0;
+    }
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx->d_prop_t2i.reserve(ti.size(), false));
     HIP_TRY(ctx->d_prop_t2o.reserve(to.size(), false));
@@ -271,10 +274,12 @@ int prop_eval_host(kfsp_ctx *ctx, int32_t n, const int32_t *state, int32_t lds, 
     int32_t *d_state = reinterpret_cast<int32_t *>(base + no_b + nd_b);
     HIP_TRY(hipMemcpyAsync(d_state, state, ns_b, hipMemcpyHostToDevice, st));
     if (int rc = prop_eval_device(ctx, n, d_state, lds, d_off, ldo, d_diag)) return rc;
+    // (a state beyond a two-species table ends the call BEFORE anything is written to the caller's arrays)
+    if (int rc = prop_check_overflow(ctx)) return rc;
     HIP_TRY(hipMemcpyAsync(offdiag, d_off, no_b, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(diag, d_diag, nd_b, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return prop_check_overflow(ctx);
+    return 0;
 }
 
 }  // namespace kfsp

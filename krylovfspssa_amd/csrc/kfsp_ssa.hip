@@ -927,10 +927,11 @@ int ssa_streams_device(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns,
     }
     int32_t nnew = 0, *d_sn = nullptr;
     double *d_on = nullptr, *d_dn = nullptr;
-    *n_found = 0;
+    // (a refused walk - -11, -16 - leaves every output of the caller as it was, the count included)
     if (int rc = ssa_streams_core(ctx, tstep, seedmix, ns, nr, stoich, n, d_state, lds, d_adj, d_off, lda, d_diag, max_count, cap_new,
                                   ldo, &nnew, &d_sn, &d_on, &d_dn))
         return rc;
+    *n_found = 0;
     if (nnew == 0) return 0;
     HIP_TRY(hipMemcpyAsync(state_new, d_sn, (size_t)nnew * lds * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(off_new, d_on, (size_t)nnew * ldo * 8, hipMemcpyDeviceToHost, st));

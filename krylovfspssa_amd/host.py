@@ -70,6 +70,8 @@ def load_library():
         "kfsp_onestep": [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(i32), vp, vp],
         "kfsp_onestep_columns": [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(i32), vp, vp, vp, i32, vp],
         "kfsp_set_propensity_program": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
+        "kfsp_set_propensity_tables2": [vp, i32, vp, vp, vp, vp, vp, i64, vp],
+        "kfsp_propensity_overflow": [vp, i32, vp],
         "kfsp_propensities": [vp, i32, vp, i32, vp, i32, vp],
         "kfsp_ssa_streams": [vp, dbl, i64, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, C.POINTER(i32), vp, vp, i32, vp],
         "kfsp_drop_plan": [vp, dbl, C.POINTER(dbl), C.POINTER(i64), C.POINTER(i64)],
@@ -475,6 +477,25 @@ class KfspContext:
                                                         _p(code_off), _p(code), _p(imm_off), _p(imm), _p(ts), int(tl), _p(tab)),
                   "kfsp_set_propensity_program")
         self._prop_nr = nr
+
+    def set_propensity_tables2(self, s1, s2, n1, n2, off, tab2):
+        """two-species tables of the program just set: reaction k with s1[k] >= 0 reads tab2[off[k] + x[s2[k]] * n1[k] + x[s1[k]]]
+        (s1, s2, n1, n2 int32 [nr], off int64 [nr], tab2 float64); a population beyond a table makes the operation that met it
+        raise KfspError with status -16 (propensity_overflow says which species went how far)"""
+        s1, s2, n1, n2 = (np.ascontiguousarray(a, dtype=np.int32) for a in (s1, s2, n1, n2))
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        tab2 = np.ascontiguousarray(tab2, dtype=np.float64).reshape(-1)
+        nr = len(s1)
+        if not (len(s2) == len(n1) == len(n2) == len(off) == nr):
+            raise ValueError("s1, s2, n1, n2 and off must have one entry per reaction")
+        self._chk(self._lib.kfsp_set_propensity_tables2(self._h, nr, _p(s1), _p(s2), _p(n1), _p(n2), _p(off), len(tab2),
+                                                        _p(tab2) if len(tab2) else None), "kfsp_set_propensity_tables2")
+
+    def propensity_overflow(self, ns):
+        """after a -16: per species the largest population that lay beyond a two-species table (0: none), int32 [ns]"""
+        missed = np.zeros(int(ns), dtype=np.int32)
+        self._chk(self._lib.kfsp_propensity_overflow(self._h, int(ns), _p(missed)), "kfsp_propensity_overflow")
+        return missed
 
     def propensities(self, state):
         state = np.ascontiguousarray(state, dtype=np.int32)

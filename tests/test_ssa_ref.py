@@ -186,6 +186,171 @@ def test_random_family_conditions():
     assert any(c.ref.virtual_jumps > 4 * len(c.state) for c in fam)              # most rim paths leave the FSP
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# two-species tables: the restatement of kfsp_set_propensity_tables2 and the conditions tests/test_gpu_prop_tables2.py
+# relies on
+
+def test_two_species_table_by_hand():
+    """tab2[off + x[s2] n1 + x[s1]] on a 3 x 2 table written out by hand; a miss gives 0.0 and leaves flag and maxima"""
+    I, A, D = R.IMM, R.ADD, R.DIV
+    progs = [([101, 102, I, A, D], [1.0]), ([103], [])]            # x / (y + 1), and a constant
+    nan = math.nan
+    tab2 = [nan, nan, 10.0, 11.0, 12.0, 20.0, 21.0, 22.0, nan]    # rows y = 0, 1 of x = 0, 1, 2 (NOT the code's values: the table is read)
+    p = R.Program(2, [0.5], progs, tables2=([0, -1], [1, -1], [3, 0], [2, 0], [2, 0], tab2))
+    assert [p.eval(0, (x, y)) for y in (0, 1) for x in (0, 1, 2)] == [10.0, 11.0, 12.0, 20.0, 21.0, 22.0]
+    assert not p.missed and p.reads2 == 6 and p.eval(1, (9, 9)) == 0.5 and p.reads2 == 6
+    assert p.eval(0, (3, 1)) == 0.0 and p.missed and p.miss_max == [3, 0]
+    assert p.eval(0, (7, 2)) == 0.0 and p.eval(0, (1, 5)) == 0.0 and p.miss_max == [7, 5] and p.reads2 == 9
+    p.reset_misses()
+    assert not p.missed and p.miss_max == [0, 0] and p.reads2 == 0
+    # the variants read other entries
+    # at (1, 1) - transposed: 2 + 1 * 2 + 1 = 5; n2 as the row length: 2 + 1 * 2 + 1 = 5; the offset of reaction k - 1 (none: 0): 0 + 3 + 1 = 4
+    for variant, want in (("transposed", 20.0), ("row_n2", 20.0), ("offset_prev", 12.0)):
+        q = R.Program(2, [0.5], progs, tables2=([0, -1], [1, -1], [3, 0], [2, 0], [2, 0], tab2), variant=variant)
+        assert p.eval(0, (1, 1)) == 21.0 and q.eval(0, (1, 1)) == want, variant
+    # make_tables2: descending offsets, gaps of NaN, the interpreter's values
+    plain = R.Program(2, [0.5], progs)
+    s1, s2, n1, n2, off, t = R.make_tables2(plain, {0: (1, 0, 4, 3)})
+    assert (s1[0], s2[0], n1[0], n2[0]) == (1, 0, 4, 3) and s1[1] == -1 and off[0] == 5
+    assert np.isnan(t[:5]).all() and np.isnan(t[5 + 12:]).all() and not np.isnan(t[5:17]).any()
+    assert t[5 + 2 * 4 + 3] == 2.0 / (3.0 + 1.0)                   # x = x[s2] = 2, y = x[s1] = 3
+
+
+def _changed(a, b):
+    return int((~(np.asarray(a) == np.asarray(b))).sum())         # (a NaN counts as changed)
+
+
+def test_columns_models_tell_the_variants_apart():
+    """(a): on every model and every list of 255 states or more each wrong restatement changes at least 10 entries of
+    columns(); the list of ONE state has 12 entries in all, of which a variant can reach at most the three tabulated ones and
+    their sum - there every variant must change at least one.  The definition never reads a gap (Program asserts it), the
+    tables have n1 != n2, s1 > s2 on two reactions, offsets descending in k with gaps."""
+    counts = {}
+    for ns in (3, 6, 9):
+        prog, code, states = R.columns_model(ns)
+        s1, s2, n1, n2, off, tab2 = prog.tables2
+        tabd = [k for k in range(prog.nr) if s1[k] >= 0]
+        assert len(tabd) == 4 and sum(s1[k] > s2[k] for k in tabd) >= 2 and all(n1[k] != n2[k] for k in tabd)
+        assert (np.diff(off[tabd]) < 0).all() and np.isnan(tab2).sum() >= 12
+        used = np.zeros(len(tab2), dtype=bool)
+        for k in tabd:
+            used[off[k]:off[k] + n1[k] * n2[k]] = True
+        assert np.array_equal(used, ~np.isnan(tab2))                                # exactly the gaps hold NaN
+        want = prog.columns(states)
+        assert not prog.missed and prog.miss_max == [0] * ns and not np.isnan(want[0]).any()
+        # the same bits from the code (the contract of a table), except where the planted one-species row would be read
+        assert np.array_equal(code.columns(states)[0], want[0]) and np.array_equal(code.columns(states)[1], want[1])
+        assert (states[:, 0] >= 12).any() and (states[:, 0] < 12).any() and (states[:, 1] == 3).any()
+        for variant in R.Program.VARIANTS2:
+            bad = R.columns_model(ns, variant=variant)[0]
+            for n in R.COLUMN_SIZES:
+                o, d = bad.columns(states[:n])
+                c = _changed(o, want[0][:n]) + _changed(d, want[1][:n])
+                assert c >= (10 if n >= 255 else 1), (ns, variant, n, c)
+                counts[ns, variant, n] = c
+    print({k: v for k, v in counts.items() if k[2] in (1, 255)})
+
+
+def test_columns_models_with_small_tables_miss():
+    """extent 4: every state is evaluated, so the maxima are the largest populations of the tabulated species beyond 4; the
+    species of the chain's never-read table and the species without a table report 0"""
+    for ns in (3, 6, 9):
+        prog, _, states = R.columns_model(ns, extent=4)
+        prog.reset_misses()
+        prog.columns(states)
+        want = [0] * ns
+        for s in {0, 1, 2, ns - 1}:                                                # the species of tables 5, 6, 7
+            want[s] = int(states[:, s].max())
+        assert prog.missed and prog.miss_max == want and min(want[s] for s in (0, 1, 2, ns - 1)) >= 4, (ns, prog.miss_max)
+        # the caller's rule serves every state in one round
+        prog2 = R.with_tables2(R.columns_model(ns, extent=4)[0], R.grow_spec(R.spec_of(prog), prog.miss_max))
+        prog2.columns(states)
+        assert not prog2.missed
+
+
+def test_walk_models_with_tables():
+    """(b): tight tables (extent max_count + 1) serve every state the walk evaluates - no miss -, tables of extent 4 do not;
+    at least 100 table reads at unlisted states; the transposed index changes state_new; the kernel each model reaches is
+    read off its construction"""
+    reads = {}
+    for i, (tight, small) in enumerate(R.walk2_cases()):
+        assert R.walk_kernel(tight) == R.walk_kernel(small) == R.WALK2_KERNELS[i] and tight.name.startswith(R.WALK2_KERNELS[i])
+        spec = R.spec_of(tight.program)
+        assert len(spec) == 2 and sorted(a > b for a, b, _, _ in spec.values()) == [False, True]
+        assert all(e1 == e2 == tight.max_count + 1 for _, _, e1, e2 in spec.values())
+        assert all(e1 == e2 == 4 for _, _, e1, e2 in R.spec_of(small.program).values())
+        assert not any(tight.program._chain[k] for k in spec)
+        ref = tight.ref
+        assert ref.first_miss is None and ref.reads2 >= 100 and ref.nnew > 0 and ref.virtual_jumps > 0, (tight.name, ref.reads2)
+        assert small.ref.first_miss is not None and max(small.ref.miss_max) >= 4, small.name
+        bad = R.tabulated(R.variant_cases()[4 + i] if i < 5 else R.table_case(11), tight.max_count + 1, t_scale=tight.t_scale,
+                          variant="transposed", max_count=tight.max_count)
+        assert not np.array_equal(bad.ref.state_new, ref.state_new), tight.name
+        reads[tight.name] = ref.reads2
+    print(reads)
+
+
+def test_stage_of_the_first_miss():
+    """(d): the restatement shows every stage first somewhere.  The walk: the models of (b) with tables of extent 4.  The
+    sweep: the models of (c) without a walk.  The columns of the walk's new states: the models of (c) under a horizon that
+    ends every path at its first jump - the state it recorded last is evaluated by no path, only for its column."""
+    stages = [small.ref.first_miss for _, small in R.walk2_cases()]
+    assert "walk" in stages, stages
+    for tight, small in R.sweep2_cases():
+        assert R.expansion(tight, t_ssa=0.0).first_miss is None and R.expansion(tight).first_miss is None
+        e = R.expansion(small, t_ssa=0.0)
+        assert e.first_miss == "sweep" and max(e.miss_max) == 4, small.name
+        e = R.expansion(small)
+        assert e.first_miss == "columns" and e.walk.reads2 == 0 and e.walk.virtual_jumps == 0, small.name
+        # every listed state lies inside the small tables
+        assert int(small.state.max()) == 3
+
+
+def test_callers_loop_stays_within_the_round_cap():
+    """after a miss the caller grows the tables by grow_spec and repeats: within ns + ceil(log2(max_count + 1)) rounds (callers_loop
+    asserts it) the answer is the tight tables' - for the walk alone, for the sweep alone and for the whole expansion"""
+    def attempt_walk(case):
+        def f(prog):
+            w = R.walk(case.tstep, case.seedmix, case.nu, case.state, case.adj, case.off, case.diag, case.max_count, prog)
+            return (None, w.miss_max) if w.first_miss else (w, None)
+        return f
+
+    def attempt_expand(case, t_ssa):
+        def f(prog):
+            e = R.expansion(case, prog, t_ssa)
+            return (None, e.miss_max) if e.first_miss else (e, None)
+        return f
+
+    assert R.round_cap(2, 6) == 5 and R.round_cap(3, 7) == 6 and R.round_cap(2, 11) == 6
+    rounds = {}
+    for tight, small in R.walk2_cases():
+        w, r, _ = R.callers_loop(small, attempt_walk(small))
+        assert r >= 1 and np.array_equal(w.state_new, tight.ref.state_new) and np.array_equal(w.off_new, tight.ref.off_new)
+        assert np.array_equal(w.diag_new, tight.ref.diag_new)
+        rounds[small.name] = r
+    for tight, small in R.sweep2_cases() + R.walk2_cases()[:1] + R.walk2_cases()[5:]:
+        for t_ssa in (0.0, None):
+            want = R.expansion(tight, t_ssa=t_ssa)
+            e, r, _ = R.callers_loop(small, attempt_expand(small, t_ssa))
+            assert want.first_miss is None and r >= 1, (small.name, t_ssa)
+            assert np.array_equal(e.state, want.state) and np.array_equal(e.adj, want.adj)
+            assert np.array_equal(e.off, want.off) and np.array_equal(e.diag, want.diag)
+    print(rounds)
+
+
+def test_share_case_misses_in_one_share_only():
+    """300 seeds under three ranks: rank 0 walks no wavefront, rank 1 wavefront 0, rank 2 wavefront 1 - and only the seeds
+    of wavefront 1 meet a population beyond the small table"""
+    small, tight = R.share_case(True), R.share_case(False)
+    args = (small.tstep, small.seedmix, small.nu, small.state, small.adj, small.off, small.diag, small.max_count, small.program)
+    assert len(small.state) == 300 and len(R.SHARE_WAVE0) == 172 and len(R.SHARE_WAVE1) == 128
+    assert R.walk(*args, seeds=R.SHARE_WAVE0).first_miss != "walk"
+    w1 = R.walk(*args, seeds=R.SHARE_WAVE1)
+    assert w1.first_miss == "walk" and w1.miss_max[0] >= 4 and w1.miss_max[1] == 0
+    assert small.ref.first_miss == "walk" and small.ref.miss_max == w1.miss_max
+    assert tight.ref.first_miss is None and tight.ref.nnew > 0 and R.expansion(tight).first_miss is None
+
+
 def test_regrow_case_counts_more_records_than_the_first_list_holds():
     w = R.regrow_ref()
     assert 2 ** 18 < w.records < 2 ** 19 and w.ends["horizon"] == 4500
