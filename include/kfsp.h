@@ -561,7 +561,57 @@ int kfsp_dgexpv(kfsp_ctx *ctx, double t, double fsptol, double krytol, int n_rea
  * is an argument, not a guarantee.  Measured on the CPU restatement against dense integrals (three small generators,
  * forward and transposed, m = 30 and 10): l1(J - J_dense) / (T l1(w_0)) <= 1.1e-12 at tol = 1e-8 and <= 7.3e-10 at tol =
  * 1e-5 ("Time integrals").  Not provided: a Fortran binding, a J-driven step control, an error estimate
- * for J through this ABI. */
+ * for J through this ABI.
+ * TARGET SETS.  A target set (THE CALLS below; none resident by default: nothing here exists then - no byte of any result,
+ * no launch and no allocation differs) makes a set T of states of the FSP ABSORBING for the block path: first-passage
+ * problems - when does the switch flip, when does a count first reach a threshold, with which probability from each
+ * start state.  With D = diag(1 - 1_T), every block call works on the KILLED generator
+ *   Q = D A D      (D A^T D under "adjoint"):   rows and columns of T are zero,
+ * without the generator being touched: a matrix-free box (block_box = 1 / 2) and a device-built generator take a set as a
+ * stored one does.  kfsp_set_block stores D W (+0.0 on T; J starts at 0); kfsp_block_begin / _arnoldi / _combine and
+ * kfsp_expv_block run on Q; kfsp_spmm returns D A D X.  W, J and every basis column are exactly +0.0 on T at all times.
+ * What the numbers mean (forward, column c started from a distribution w_0 off T):
+ *   wsum_c = 1^T exp(tQ) w_0                   the SURVIVAL probability: neither in T nor out of the FSP by t;
+ *   F_c(t) = 1_T^T A J_c, J_c = int_0^t exp(sQ) w_0 ds      the probability of HAVING REACHED T by t: the flux call, which = 1;
+ *   f_c(t) = 1_T^T A W_c(t)                    the FIRST-PASSAGE DENSITY at t (dF/dt): the flux call, which = 0;
+ *   1 - wsum_c = F_c(t) + leak_c(t)            the mass balance: leak is the probability of having left the FSP first.
+ * Both fluxes are per-column sums over the rows of T of ONE product with the unmasked A.  They are forward quantities:
+ * the flux call returns -12 under "adjoint".  The backward recipes, per START STATE x, need no flux:
+ *   mean first-passage time truncated at T_end:  set the target, "adjoint" = 1, "block_integral" = 1, "block_clamp" = 0,
+ *     column g = 1; after kfsp_expv_block(T_end), J(x) = E[min(tau_T, exit, T_end) | X_0 = x] (0 on T);
+ *   probability of reaching T before T_end:  BEFORE the set is installed, g = D A^T 1_T by kfsp_spmm under "adjoint" (X =
+ *     the indicator of T, then zero g on T on the host); install the set, solve backward with "block_integral" = 1 from
+ *     W = g: J(x) = P[tau_T <= min(T_end, exit) | X_0 = x], and w_0 . J equals F(T_end) of the forward solve from w_0.
+ * How.  No product kernel changes.  An Arnoldi step writes z = A u_j raw with the partials u_{j-1} . z and u_j . z; since
+ * every basis column is 0 on T, u . z = u . (D z) and H(j-1,j), H(j,j) are already those of Q; the update pass then
+ * zeroes z on T before it sums ||z||^2 and z . u_j, which makes u_{j+1} a basis column of Q and zero on T again; the
+ * invariant starts at u_1 = D W.  So a pass is the 4 m + 3 launches it was (kfsp_block_info), with one flag byte per row
+ * added to its three streaming kernels; "block_clamp", "block_integral", "block_box" combine as they are (the combine
+ * only sees columns that are 0 on T).  "block_small" is not taken while a set is resident (the general path runs, with the
+ * same bits as under block_small = 0).  Everything single-vector - kfsp_spmv, kfsp_dgexpv, w - is untouched, and
+ * kfsp_spmm_bench keeps timing the RAW product A X.
+ * Lifetime: a set lives until it is cleared or the generator changes (kfsp_set_matrix_* / kfsp_update_matrix_ell /
+ * kfsp_drop_compact / kfsp_expand_resident discard it with the block).  Setting or clearing it discards the resident
+ * block and its J as a generator change does - W must be D W from the start - so kfsp_get_block then fails until the next
+ * kfsp_set_block.  Not provided: row partitions (communicator, loop-back rank, group head: -12), a Fortran binding.
+ * THE CALLS.  The set of entry points of this library is fixed, so a target set travels through three existing ones,
+ * under option "block_target" as a CALL MODE (default 0: every call is what it always was; set the mode round the one call
+ * and 0 again after it, as "block_integral" = 2 round kfsp_get_block; whether a set is resident is state, not the option):
+ *   "block_target" = 1, kfsp_set_block(ctx, 1, n, ldw, F): INSTALL the set instead of storing a block.  F is one column of
+ *     doubles, F[i] != 0 puts state i (caller's order; the internal state order is applied as in kfsp_set_vector) into T;
+ *     n = the number of states of the generator.  F == NULL or n == 0 CLEARS the set.  On the device the set is one byte
+ *     per row.  Returns -1 null context or no matrix set, -2 n is not the number of states (or k is not 1), -12 a
+ *     communicator, a loop-back rank or a group head (before any collective, with or without "block_partition").
+ *   "block_target" = 2, kfsp_block_info(ctx, v): v[0] = 1 when a set is resident, v[1] = its number of states, v[2] =
+ *     kernel launches enqueued by the last flux call (3: the raw product, the partial sums, their finish), v[3..7] = 0.
+ *   "block_target" = 3, kfsp_block_begin(ctx, which, out): the FLUX into the set, out[c] = sum over i in T of (A X_c)_i
+ *     with the UNMASKED A; entries >= k are 0.  which = 0: X = the resident W (the first-passage density at the solve's
+ *     current time); which = 1: X = the resident J (the probability of having reached T by the accumulated time; J
+ *     accumulates across kfsp_expv_block calls, so repeated calls trace the CDF).  One raw block product into a scratch
+ *     column of its own (W, J and a basis laid out by a plain kfsp_block_begin are not touched), one reduction in a fixed
+ *     order: two calls give the same bits.  Returns -1 no block or no target set resident, or which = 1 without J; -2 bad
+ *     which; -3 null out; -12 option "adjoint" is on, and as kfsp_set_block.
+ * krylovfspssa_amd/host.py wraps the three as set_block_target, block_target_info and block_hit. */
 /* k start vectors (1 <= k <= 16), W column-major host memory W[j*ldw + i], i in the caller's order (the internal state
  * order is applied as in kfsp_set_vector); n = the number of states of the generator (a rank of a row partition: its
  * nlocal rows, see ROW PARTITIONS) */
@@ -570,7 +620,8 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
  * J, the time integral kept beside the block, instead of W (-1 when none is resident) */
 int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W);
 /* Y = A X for k host columns X[j*ld + i] (ld >= n), Y alike; column j is BIT-IDENTICAL to kfsp_spmv of column j (every
- * column of a row is summed in FMATVEC's order, KrylovSolver.f90:598-604).  Leaves the resident block alone. */
+ * column of a row is summed in FMATVEC's order, KrylovSolver.f90:598-604).  Leaves the resident block alone.  While a
+ * target set is resident (TARGET SETS): Y = D A D X - X is masked when packed, Y before it is unpacked. */
 int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y);
 /* W <- exp(t A) W for the resident block: EXPOKIT's step control of DGEXPV_FSP (KrylovSolver.f90:177-187, 280-345,
  * 437, 540-548) with the Krylov dimension fixed at m (<= option m_max, capped at n - 1), ONE step size for all
@@ -583,7 +634,8 @@ typedef struct {
     double t_now, step_min, step_max, x_error, s_error;
 } kfsp_block_stats;
 int kfsp_expv_block(kfsp_ctx *ctx, double t, double tol, int32_t m, double *wsum, kfsp_block_stats *stats);
-/* reps block products Y = A X on the resident block, bracketed by HIP events (like kfsp_spmv_bench) */
+/* reps block products Y = A X on the resident block, bracketed by HIP events (like kfsp_spmv_bench).  The RAW product,
+ * also while a target set is resident: the masks are no part of what it times. */
 int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total);
 /* The three device phases of one step of kfsp_expv_block, as kfsp_begin_step / kfsp_arnoldi / kfsp_combine are those of
  * the single-vector step.  All arrays are host memory with 16 entries per row, one per block column (entries >= k
@@ -747,7 +799,7 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
  * take a matrix-free single-factor box, see "several vectors at once"; 2: every matrix-free box - multi-factor propensities, any jump, and any box under box_generic = 1 - through the interpreted row of format 3; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_integral" (1: kfsp_set_block keeps J, the time integral of the block,
  * beside it and every accepted step of kfsp_expv_block adds to it; 2: the same and kfsp_get_block answers with J; 0, default: nothing changes;
- * see TIME INTEGRALS under "several vectors at once"), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
+ * see TIME INTEGRALS under "several vectors at once"), "block_target" (call mode of the target-set protocol: 1 kfsp_set_block installs or clears a target set, 2 kfsp_block_info reports it, 3 kfsp_block_begin is the flux into it; 0, default: the calls as ever; see TARGET SETS under "several vectors at once"), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
  * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other

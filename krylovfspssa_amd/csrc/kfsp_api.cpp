@@ -234,6 +234,7 @@ int kfsp::resize(kfsp_ctx *ctx, int64_t n)
     ctx->n = n;
     ctx->trip_order_n = 0;             // a trip order belongs to one generator
     kfsp::block_release(ctx);          // ... and so does a block of vectors (kfsp_set_block)
+    kfsp::block_target_release(ctx);   // ... and its target set (kfsp_set_block under block_target = 1)
     ctx->L = round_up((n + ctx->nranks - 1) / ctx->nranks, kChunk);
     if (ctx->L == 0) ctx->L = kChunk;
     ctx->row0 = (int64_t)ctx->rank * ctx->L;
@@ -628,6 +629,7 @@ int kfsp_destroy(kfsp_ctx *ctx)
     ctx->d_sortidx.release(); ctx->d_sorttmp.release(); ctx->d_gmask.release(); ctx->d_zero.release();
     ctx->d_skeys.release(); ctx->d_skeys2.release(); ctx->d_perm2.release(); ctx->d_prop_fast_i.release(); ctx->d_prop_fast_d.release();
     kfsp::block_release(ctx);
+    kfsp::block_target_release(ctx);
     if (ctx->h_loop) (void)hipHostFree(ctx->h_loop);
     if (ctx->h_H) (void)hipHostFree(ctx->h_H);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
@@ -1848,6 +1850,7 @@ int kfsp_drop_compact(kfsp_ctx *ctx, int64_t *n_new)
     if (!n_new) return fail(ctx, -2, "null n_new");
     HIP_TRY(hipSetDevice(ctx->device));
     kfsp::block_release(ctx);          // the FSP changes: a block of vectors belongs to the old one
+    kfsp::block_target_release(ctx);   // ... and so does its target set
     hipStream_t st = ctx->stream;
     const int64_t n = ctx->n;
     const double *src = ctx->d_w.p;
@@ -2227,6 +2230,10 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "block_integral") {
         if (value < 0 || value > 2) return fail(ctx, -3, "block_integral is 0, 1 or 2");
         ctx->opt_block_integral = value;
+    }
+    else if (k == "block_target") {
+        if (value < 0 || value > 3) return fail(ctx, -3, "block_target is 0, 1, 2 or 3");
+        ctx->opt_block_target = value;
     }
     else if (k == "box_pencil") ctx->opt_box_pencil = value;
     else if (k == "box_slab_waves") ctx->opt_box_slab_waves = value;

@@ -49,6 +49,13 @@
 // second block J of the block's shape (d_bint, +0.0) and block_combine takes kernels of its own, k_bcombine_int /
 // k_bcombine_small_int: the pass over the basis that makes W also adds a second linear combination (the table behind coef,
 // kfsp_block_integral.h) to J.  With the option off neither the kernels above nor any allocation or launch changes.
+//
+// Target sets (the target-set mode of kfsp_set_block; DESIGN.md 12, "Target sets").  While a set T is resident (d_btgt: one byte per row of
+// the internal order) every block call works on the killed generator Q = D A D, D = diag(1 - 1_T), and no product kernel
+// knows: the raw product's partials u . z are already those of Q because every basis column is 0 on T, and the TARGET
+// instantiations of k_bcopy_nrm / k_bortho / k_bnorm put +0.0 on T before they sum.  kfsp_set_block stores D W, kfsp_spmm
+// masks X and Y (k_btarget_zero), the flux mode of kfsp_block_begin sums one raw product over T (k_bhit + the sum stage of k_bfinal).  With no
+// set resident the false instantiations run: the code as it was, no launch and no allocation more.
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
@@ -59,6 +66,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 namespace kfsp {
 
@@ -364,14 +372,20 @@ __device__ __forceinline__ void flat_sum(double a0, double a1, int half, double 
     __syncthreads();
 }
 
-// U = W, partial: ||W_c||^2
+// Target sets (the target-set mode of kfsp_set_block; DESIGN.md 12, "Target sets"): TARGET instantiations of the three streaming kernels
+// of a pass read one flag byte per row - pair i lies in row i >> sh, sh = log2(kp / 2) - and put +0.0 where the flag is
+// set, before anything is summed.  The false instantiations are the kernels as they were: tgt and sh are not read.
+//
+// U = W, partial: ||W_c||^2.  TARGET: U = D W
+template <bool TARGET>
 __global__ __launch_bounds__(kBlock) void k_bcopy_nrm(int64_t npairs, int half, const d2 *__restrict__ w, d2 *__restrict__ u,
-                                                      double *__restrict__ part)
+                                                      double *__restrict__ part, const uint8_t *__restrict__ tgt, int sh)
 {
     __shared__ double red[8 * K];
     double a0 = 0.0, a1 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
-        const d2 v = w[i];
+        d2 v = w[i];
+        if (TARGET && tgt[i >> sh]) v.x = v.y = 0.0;
         u[i] = v;
         a0 = __builtin_fma(v.x, v.x, a0);
         a1 = __builtin_fma(v.y, v.y, a1);
@@ -379,10 +393,12 @@ __global__ __launch_bounds__(kBlock) void k_bcopy_nrm(int64_t npairs, int half, 
     flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
 }
 
-// z <- cz z - c1 u1 - c2 u2 per column; partials ||z||^2 and z . u2
+// z <- cz z - c1 u1 - c2 u2 per column; partials ||z||^2 and z . u2.  TARGET: z <- D (...), so the next basis column is
+// one of D A D and zero on the set again
+template <bool TARGET>
 __global__ __launch_bounds__(kBlock) void k_bortho(int64_t npairs, int half, d2 *__restrict__ z, const d2 *__restrict__ u1,
                                                    const d2 *__restrict__ u2, const double *__restrict__ co,
-                                                   double *__restrict__ part)
+                                                   double *__restrict__ part, const uint8_t *__restrict__ tgt, int sh)
 {
     __shared__ double red[8 * K];
     const int q = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) % half);
@@ -402,6 +418,7 @@ __global__ __launch_bounds__(kBlock) void k_bortho(int64_t npairs, int half, d2 
         }
         v.x = __builtin_fma(-c2.x, b.x, v.x);
         v.y = __builtin_fma(-c2.y, b.y, v.y);
+        if (TARGET && tgt[i >> sh]) v.x = v.y = 0.0;
         z[i] = v;
         s0 = __builtin_fma(v.x, v.x, s0);
         s1 = __builtin_fma(v.y, v.y, s1);
@@ -412,17 +429,57 @@ __global__ __launch_bounds__(kBlock) void k_bortho(int64_t npairs, int half, d2 
     flat_sum(g0, g1, half, red, part + ((size_t)kMaxGrid + blockIdx.x) * K);
 }
 
-// partial: ||z_c||^2
-__global__ __launch_bounds__(kBlock) void k_bnorm(int64_t npairs, int half, const d2 *__restrict__ z, double *__restrict__ part)
+// partial: ||z_c||^2.  TARGET: of D z, and z <- D z in place (kfsp_block_combine may read that column: mx = m + 2)
+template <bool TARGET>
+__global__ __launch_bounds__(kBlock) void k_bnorm(int64_t npairs, int half, typename std::conditional<TARGET, d2, const d2>::type *__restrict__ z,
+                                                  double *__restrict__ part, const uint8_t *__restrict__ tgt, int sh)
 {
     __shared__ double red[8 * K];
     double a0 = 0.0, a1 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
-        const d2 v = z[i];
+        d2 v = z[i];
+        if constexpr (TARGET) {
+            if (tgt[i >> sh]) {
+                v.x = v.y = 0.0;
+                z[i] = v;
+            }
+        }
         a0 = __builtin_fma(v.x, v.x, a0);
         a1 = __builtin_fma(v.y, v.y, a1);
     }
     flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
+}
+
+// x <- D x: +0.0 on the rows of the set (kfsp_set_block's W, kfsp_spmm's X and Y)
+__global__ __launch_bounds__(kBlock) void k_btarget_zero(int64_t npairs, int sh, const uint8_t *__restrict__ tgt, d2 *__restrict__ x)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock)
+        if (tgt[i >> sh]) x[i] = d2{0.0, 0.0};
+}
+
+// partial: the sum of y_c over the rows of the set (the flux mode of kfsp_block_begin), in the lane and block order of the kernels above
+__global__ __launch_bounds__(kBlock) void k_bhit(int64_t npairs, int half, int sh, const uint8_t *__restrict__ tgt, const d2 *__restrict__ y,
+                                                 double *__restrict__ part)
+{
+    __shared__ double red[8 * K];
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * kBlock) {
+        if (tgt[i >> sh]) {
+            const d2 v = y[i];
+            a0 += v.x;
+            a1 += v.y;
+        }
+    }
+    flat_sum(a0, a1, half, red, part + (size_t)blockIdx.x * K);
+}
+
+// the caller's flags (stage[state], any non-zero byte) -> one byte 0 / 1 per row of the internal order; rows in [n, rows)
+// read "keep"
+__global__ __launch_bounds__(kBlock) void k_btarget_pack(int64_t n, int64_t rows, const uint8_t *__restrict__ stage,
+                                                         const int32_t *__restrict__ perm, uint8_t *__restrict__ tgt)
+{
+    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kBlock)
+        tgt[r] = r < n && stage[perm ? perm[r] : r] != 0 ? 1 : 0;
 }
 
 // W = max(sum_i coef_i u_i, 0) (DGEMV :444, clamp :447-449), partial: sum W (DASUM :450).  clamp = 0 (option block_clamp,
@@ -696,15 +753,27 @@ int spmm_grid(const kfsp_ctx *c) { return product_grid(spmm_trips(c), c->opt_gri
 
 // The small path is taken where kfsp_arnoldi (qiop = 2) takes k_arnoldi_small on this context (kfsp_api.cpp), short of
 // coded SELL columns: those stay on the multi-launch path.  So does every backward pass (option adjoint): k_barnoldi_small
-// has the forward product compiled in.
+// has the forward product compiled in.  And every pass under a target set (the target-set mode of kfsp_set_block): the masks live in the
+// streaming kernels of the general path.
 bool small_path(const kfsp_ctx *c)
 {
-    return c->opt_block_small != 0 && c->opt_adjoint == 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->use_box &&
+    return c->opt_block_small != 0 && !c->blk_tgt && c->opt_adjoint == 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->use_box &&
            c->nchunks * kChunk <= kSmallRows && (c->use_dia || (c->have_sell && !c->sell_coded)) && c->slots < (1LL << 31);
 }
 
 // grid of the streaming kernels over a block column
 int flat_grid(const kfsp_ctx *c, int kp) { return vec_grid(red_pairs(c, kp), c->opt_vgrid); }
+
+// target sets: the row of pair i is i >> pair_shift(kp)
+int pair_shift(int kp) { return kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3)); }
+
+// col <- D col for a block column of width kp (row 0 at col); nothing without a set
+void target_zero(kfsp_ctx *ctx, int kp, double *col)
+{
+    if (!ctx->blk_tgt) return;
+    hipLaunchKernelGGL(k_btarget_zero, dim3(flat_grid(ctx, kp)), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), pair_shift(kp),
+                       ctx->d_btgt.p, reinterpret_cast<d2 *>(col));
+}
 
 template <int KP, bool PART>
 void launch_spmm_kp(int fmt, bool dots, int g, const SpmmArgs &a, hipStream_t st)
@@ -1069,6 +1138,9 @@ void block_release(kfsp_ctx *ctx)
     ctx->d_bxg.release();
     ctx->d_bint.release();
     ctx->d_bcj.release();
+    ctx->d_bhit.release();
+    ctx->d_bhsum.release();
+    ctx->bhit_launches = 0;
     ctx->blk_int = false;
     ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->bxg_kp = ctx->blk_begin_m = 0;
     std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
@@ -1076,6 +1148,13 @@ void block_release(kfsp_ctx *ctx)
     std::memset(ctx->blk_box_t_occ, 0, sizeof(ctx->blk_box_t_occ));
     std::memset(ctx->blk_boxg_occ, 0, sizeof(ctx->blk_boxg_occ));
     std::memset(ctx->blk_boxg_t_occ, 0, sizeof(ctx->blk_boxg_t_occ));
+}
+
+void block_target_release(kfsp_ctx *ctx)
+{
+    ctx->d_btgt.release();
+    ctx->blk_tgt = false;
+    ctx->btgt_states = 0;
 }
 
 // Every refusal below is made from what all ranks of a partition share (options, the kind of generator), before the
@@ -1165,9 +1244,9 @@ int block_begin(kfsp_ctx *ctx, int m, double *beta)
         ctx->blk_info[2] = 1;
     } else {
         const int g = flat_grid(ctx, kp);
-        hipLaunchKernelGGL(k_bcopy_nrm, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2,
-                           reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)),
-                           ctx->d_bpart.p);
+        hipLaunchKernelGGL((ctx->blk_tgt ? k_bcopy_nrm<true> : k_bcopy_nrm<false>), dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp),
+                           kp / 2, reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
+                           reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)), ctx->d_bpart.p, (const uint8_t *)ctx->d_btgt.p, pair_shift(kp));
         if (int rc = finalize(ctx, kFinBegin, 1, kp, g)) return rc;
         ctx->blk_info[2] = 2;
     }
@@ -1189,6 +1268,9 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     double *V = ctx->d_bv.p;
     auto u = [&](int j) { return bcol(V, ctx, kp, j - 1); };   // u_j, 1-based
     const bool small = small_path(ctx);
+    // target set: the update pass and the AVNORM norm mask what the raw product wrote (null: the kernels as they were)
+    const uint8_t *tgt = ctx->blk_tgt ? ctx->d_btgt.p : nullptr;
+    const int sh = pair_shift(kp);
     ctx->blk_info[0] = small ? 1 : 0;
     ctx->blk_info[1] = ctx->blk_info[5] = 0;
     ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
@@ -1218,16 +1300,17 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
         int g = 0;
         if (int rc = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true, &g)) return rc;
         if (int rc = finalize(ctx, kFinDots, j, kp, g)) return rc;
-        hipLaunchKernelGGL(k_bortho, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
+        hipLaunchKernelGGL((tgt ? k_bortho<true> : k_bortho<false>), dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
                            reinterpret_cast<const d2 *>(j >= 2 ? u(j - 1) : nullptr), reinterpret_cast<const d2 *>(u(j)),
-                           ctx->d_bscal.p + kCO, ctx->d_bpart.p);
+                           ctx->d_bscal.p + kCO, ctx->d_bpart.p, tgt, sh);
         if (int rc = finalize(ctx, kFinNorm, j, kp, gv, break_tol)) return rc;
     }
     if (!small) {
         // the extra product for AVNORM (:261-263) into the scratch column
         int g = 0;
         if (int rc = spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false, &g)) return rc;
-        hipLaunchKernelGGL(k_bnorm, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p);
+        if (tgt) hipLaunchKernelGGL(k_bnorm<true>, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(m + 2)), ctx->d_bpart.p, tgt, sh);
+        else hipLaunchKernelGGL(k_bnorm<false>, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p, tgt, sh);
         if (int rc = finalize(ctx, kFinAvn, m + 1, kp, gv)) return rc;
     }
     std::vector<double> h((size_t)kScal);
@@ -1291,9 +1374,22 @@ using namespace kfsp;
 
 extern "C" {
 
+// Target sets travel through three existing entry points (the exported surface of the library is pinned): option
+// "block_target" is the call mode - 1: kfsp_set_block takes flags, 2: kfsp_block_info reports the set, 3: kfsp_block_begin
+// is the flux into it (include/kfsp.h, TARGET SETS).  A group head answers with the mode of its rank 0.
+static int set_block_target(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldf, const double *F);
+static int block_target_info(kfsp_ctx *ctx, int64_t *v);
+static int block_hit(kfsp_ctx *ctx, int32_t which, double *out);
+static int64_t target_mode(kfsp_ctx *ctx)
+{
+    const kfsp_ctx *l = lead(ctx);
+    return l ? l->opt_block_target : 0;
+}
+
 int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W)
 {
     if (!ctx) return -1;
+    if (target_mode(ctx) == 1) return set_block_target(ctx, k, n, ldw, W);
     return guarded(ctx, [&]() -> int {
         if (int rc = block_supported(ctx)) return rc;
         if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
@@ -1330,6 +1426,7 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
         }
         ctx->blk_kp = kp;
         if (int rc = upload_block(ctx, k, kp, ldw, W, bcol(ctx->d_blk.p, ctx, kp, 0))) return rc;
+        target_zero(ctx, kp, bcol(ctx->d_blk.p, ctx, kp, 0));       // a target set: the block is D W from the start
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->blk_k = k;
         ctx->blk_int = ctx->opt_block_integral != 0;
@@ -1384,8 +1481,10 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         const bool whole = ctx->use_comm;
         double *x = whole ? xg_row0(ctx, kp) : bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
         if (int rc = upload_block(ctx, k, kp, ld, X, x, whole)) return rc;
+        target_zero(ctx, kp, x);                                    // a target set: Y = D A D X
         int g = 0;
         if (int rc = spmm(ctx, kp, x, y, nullptr, nullptr, false, &g, whole)) return rc;
+        target_zero(ctx, kp, y);
         ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
         if (int rc = download_block(ctx, k, kp, y, ld, Y)) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1404,6 +1503,7 @@ static int block_call_ok(kfsp_ctx *ctx)
 int kfsp_block_begin(kfsp_ctx *ctx, int32_t m, double *beta)
 {
     if (!ctx) return -1;
+    if (target_mode(ctx) == 3) return block_hit(ctx, m, beta);
     return guarded(ctx, [&]() -> int {
         if (int rc = block_call_ok(ctx)) return rc;
         if (m < 1 || m > kMMax) return fail(ctx, -2, "bad m (need 1 <= m <= 100)");
@@ -1445,9 +1545,101 @@ int kfsp_block_info(kfsp_ctx *ctx, int64_t *v)
 {
     if (!ctx) return -1;
     if (!v) return fail(ctx, -2, "null v");
+    if (target_mode(ctx) == 2) return block_target_info(ctx, v);
     if (ctx->group) return group_block_info(ctx, v);
     for (int i = 0; i < 8; ++i) v[i] = ctx->blk_info[i];
     return 0;
+}
+
+static int set_block_target(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldf, const double *F)
+{
+    (void)ldf;                                   // one column: the leading dimension is never used
+    return guarded(ctx, [&]() -> int {
+        // refused from what every rank shares, before anything else (block_supported's rule)
+        if (ctx->group || ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm)
+            return fail(ctx, -12, "kfsp_set_block under block_target = 1 (a target set): not with a row partition (communicator, loop-back rank or group context), "
+                                  "with or without option block_partition");
+        if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
+        const bool clear = !F || n == 0;
+        if (!clear && k != 1) return fail(ctx, -2, "block_target = 1: the flags are ONE column (k = 1)");
+        if (!clear && n != ctx->n) return fail(ctx, -2, "block_target = 1: n is not the number of states of the generator");
+        HIP_TRY(hipSetDevice(ctx->device));
+        // the resident block is W, not D W (or D' W): it goes, and its J, as when the generator changes
+        block_release(ctx);
+        block_target_release(ctx);
+        if (clear) return 0;
+        const int64_t rows = ctx->nchunks * kChunk;
+        std::vector<uint8_t> flags((size_t)n);
+        int64_t cnt = 0;
+        for (int64_t i = 0; i < n; ++i) cnt += flags[(size_t)i] = F[i] != 0.0;
+        DevBuf<uint8_t> stage;
+        HIP_TRY(ctx->d_btgt.reserve((size_t)rows, true));
+        hipError_t e = stage.reserve((size_t)n, false);
+        if (e == hipSuccess) e = hipMemcpyAsync(stage.p, flags.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (rows + kBlock - 1) / kBlock));
+            hipLaunchKernelGGL(k_btarget_pack, dim3(g), dim3(kBlock), 0, ctx->stream, n, rows, (const uint8_t *)stage.p,
+                               ctx->perm_on ? (const int32_t *)ctx->d_perm.p : nullptr, ctx->d_btgt.p);
+            e = hipStreamSynchronize(ctx->stream);
+        }
+        stage.release();
+        if (e != hipSuccess) {
+            block_target_release(ctx);
+            HIP_TRY(e);
+        }
+        ctx->blk_tgt = true;
+        ctx->btgt_states = cnt;
+        return 0;
+    });
+}
+
+static int block_target_info(kfsp_ctx *ctx, int64_t *v)
+{
+    v[0] = ctx->blk_tgt ? 1 : 0;
+    v[1] = ctx->btgt_states;
+    v[2] = ctx->bhit_launches;
+    for (int i = 3; i < 8; ++i) v[i] = 0;
+    return 0;
+}
+
+static int block_hit(kfsp_ctx *ctx, int32_t which, double *out)
+{
+    return guarded(ctx, [&]() -> int {
+        if (int rc = block_call_ok(ctx)) return rc;
+        if (!ctx->blk_tgt) return fail(ctx, -1, "block_target = 3: no target set resident (kfsp_set_block under block_target = 1)");
+        if (which != 0 && which != 1) return fail(ctx, -2, "block_target = 3: m is 0 (the flux of the block W) or 1 (of its time integral J)");
+        if (!out) return fail(ctx, -3, "null out");
+        if (ctx->opt_adjoint)
+            return fail(ctx, -12, "block_target = 3: the flux into the set is a forward quantity, not with option adjoint "
+                                  "(include/kfsp.h, TARGET SETS, has the backward recipe)");
+        if (which == 1 && !ctx->blk_int)
+            return fail(ctx, -1, "block_target = 3: no integral resident beside the block (option block_integral before kfsp_set_block)");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const int kp = ctx->blk_kp;
+        hipStream_t st = ctx->stream;
+        if (int rc = ensure_scalars(ctx)) return rc;
+        // the raw product goes to a column of its own: W, J and a basis laid out by kfsp_block_begin stay as they are
+        if (ctx->d_bhit.cap < col_len(ctx, kp)) {
+            ctx->d_bhit.release();
+            HIP_TRY(ctx->d_bhit.reserve(col_len(ctx, kp), true));
+        }
+        HIP_TRY(ctx->d_bhsum.reserve((size_t)2 * K, true));
+        double *y = bcol(ctx->d_bhit.p, ctx, kp, 0);
+        int g = 0;
+        if (int rc = spmm(ctx, kp, bcol(which ? ctx->d_bint.p : ctx->d_blk.p, ctx, kp, 0), y, nullptr, nullptr, false, &g)) return rc;
+        const int gv = flat_grid(ctx, kp);
+        hipLaunchKernelGGL(k_bhit, dim3(gv), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, pair_shift(kp), (const uint8_t *)ctx->d_btgt.p,
+                           reinterpret_cast<const d2 *>(y), ctx->d_bpart.p);
+        // the sum stage of k_bfinal alone: the block partials in its fixed order (both of its sums read the same ones)
+        hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, st, (int)kFinWsum, 0, kp, gv, ctx->d_bpart.p, (int64_t)0, ctx->d_bscal.p, 0.0,
+                           ctx->d_bhsum.p);
+        ctx->bhit_launches = 3;
+        double h[K];
+        HIP_TRY(hipMemcpyAsync(h, ctx->d_bhsum.p, K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int c = 0; c < K; ++c) out[c] = c < ctx->blk_k ? h[c] : 0.0;
+        return 0;
+    });
 }
 
 int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)

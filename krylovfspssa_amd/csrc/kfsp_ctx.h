@@ -334,6 +334,14 @@ struct kfsp_ctx {
     DevBuf<double> d_bint, d_bcj;   // option block_integral: J, the time integral of the resident block (laid out like d_blk), and
                                     // its coefficient table; allocated by kfsp_set_block while the option is on, never otherwise
     bool blk_int = false;           // J is resident beside the block
+    // target set of the block path (kfsp_set_block under block_target = 1): one byte per row of the internal order, nchunks * kChunk of
+    // them (1: the row's state is in the set; the padding rows read 0).  Lives until cleared or the generator changes
+    // (block_target_release beside every block_release of a generator change); nothing of it exists while none is set.
+    DevBuf<uint8_t> d_btgt;
+    bool blk_tgt = false;           // a set is resident
+    int64_t btgt_states = 0;        // its number of states
+    int64_t bhit_launches = 0;      // launches enqueued by the last flux call (kfsp_block_begin under block_target = 3)
+    DevBuf<double> d_bhit, d_bhsum; // the flux call: its scratch block column and the 2 K finished sums; released with the block
 
     // scalars
     DevBuf<double> d_part;   // kNumPartial * kMaxGrid
@@ -388,6 +396,8 @@ struct kfsp_ctx {
     int64_t opt_adjoint = 0;              // 1: the block calls multiply with A^T (kfsp_block_adj.hip): backward solves exp(tA^T) F
     int64_t opt_block_partition = 0;      // 1: the block calls run under a row partition (communicator, loop-back rank, group head); 0: -12
     int64_t opt_block_clamp = 1;          // 0: the block combine does not clamp at 0 and wsum is the l1 norm (signed observables)
+    int64_t opt_block_target = 0;         // call mode of the target-set protocol (include/kfsp.h, TARGET SETS): 1 kfsp_set_block takes flags,
+                                          // 2 kfsp_block_info reports the set, 3 kfsp_block_begin is the flux into it; 0: the calls as they were
     int64_t opt_block_integral = 0;       // 1: kfsp_set_block keeps J = the time integral of the block beside it and the combine updates both;
                                           // 2: the same, and kfsp_get_block answers with J
     int64_t opt_state_order = 1;          // 1: use kfsp_set_state_coords for large, long-lived generators (0: never)
@@ -533,4 +543,6 @@ int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t 
 void launch_zero_pad(int64_t n0, int64_t n1, double *w, hipStream_t st);
 // several vectors at once (kfsp_block.hip): drop the resident block and its buffers
 void block_release(kfsp_ctx *ctx);
+// ... and the target set of kfsp_set_block under block_target = 1 (a generator change calls both, kfsp_set_block under block_target = 1 the first alone)
+void block_target_release(kfsp_ctx *ctx);
 }  // namespace kfsp

@@ -708,7 +708,8 @@ class KfspContext:
         reactions), jumps beyond 2, more than four propensities on a species, more than six species.
         On a rank of a row partition (set_option("block_partition", 1) first): this rank's nloc rows, as in set_vector.
         With set_option("block_integral", 1) in force, a second block J of the same shape is kept beside W, zeroed here:
-        every accepted step of expv_block adds int_0^tau exp(sA) W_step ds to it (get_block(integral=True))."""
+        every accepted step of expv_block adds int_0^tau exp(sA) W_step ds to it (get_block(integral=True)).
+        While a target set is resident (set_block_target) the block stored is D W: +0.0 on the states of the set."""
         nloc = self._block_rows()
         Wf, k = _block_columns(W, nloc)
         self._chk(self._lib.kfsp_set_block(self._h, k, nloc, max(nloc, 1), _p(Wf)), "kfsp_set_block")
@@ -720,7 +721,9 @@ class KfspContext:
         occupation measure (expected time spent in each state), backward (adjoint=True) the accumulated observable
         E[int_0^min(T, exit) g(X_s) ds | X_0 = x], for g = 1 the truncated mean exit time.  Needs
         set_option("block_integral", 1) before set_block; the option is set to 2 round the call and put back.  J has no
-        step control of its own: about T times the error bound of W (include/kfsp.h, TIME INTEGRALS)."""
+        step control of its own: about T times the error bound of W (include/kfsp.h, TIME INTEGRALS).
+        Under a target set W and J are exactly +0.0 on the set; set_block_target discards the block, so this raises
+        until the next set_block."""
         k = getattr(self, "block_k", 0)
         if not 1 <= k <= BLOCK_K_MAX:
             raise KfspError("no block was set on this context")
@@ -759,7 +762,8 @@ class KfspContext:
         """A X for the columns of X (shape n x k, 1 <= k <= 16); column j is bit-identical to spmv(X[:, j]) - also on a
         matrix-free box under set_option("block_box", 1), and on a multi-factor one (or any box under "box_generic" = 1)
         under set_option("block_box", 2).  adjoint=True: A^T X (option "adjoint" round the call).
-        On a rank of a row partition X is the whole block (n rows) and the rank's nloc rows of A X come back, as in spmv."""
+        On a rank of a row partition X is the whole block (n rows) and the rank's nloc rows of A X come back, as in spmv.
+        While a target set is resident: D A D X (D A^T D X), the product with the killed generator - +0.0 on the set."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
         self._with_block_options(lambda: self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm"),
@@ -773,7 +777,10 @@ class KfspContext:
         clamp=False: columns are not clamped at 0 after a step (signed observables) and wsum is their l1 norm.  Both are
         the options "adjoint" / "block_clamp", set round the call and put back to forward / clamped.
         Under set_option("block_integral", 1) (in force since before set_block) every accepted step also adds its time
-        integral to J (get_block(integral=True)); W, wsum and the statistics are the same bits with and without."""
+        integral to J (get_block(integral=True)); W, wsum and the statistics are the same bits with and without.
+        While a target set is resident the solve is the one of the killed generator Q = D A D: wsum is the survival
+        probability, block_hit() the first-passage density and block_hit(integral=True) the probability of having
+        reached the set (include/kfsp.h, TARGET SETS)."""
         k = getattr(self, "block_k", 0)
         if not 1 <= k <= BLOCK_K_MAX:
             raise KfspError("no block was set on this context")
@@ -835,6 +842,45 @@ class KfspContext:
         self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info")
         return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes", "adjoint", "exchange"),
                         (int(x) for x in v[:8])))
+
+    def _target_mode(self, mode, call):
+        """call() under option "block_target" = mode (the call modes of include/kfsp.h, TARGET SETS), then 0 again"""
+        self.set_option("block_target", mode)
+        try:
+            return call()
+        finally:
+            self.set_option("block_target", 0)
+
+    def set_block_target(self, flags):
+        """Make the states with flags[i] != 0 (n entries, caller's state order) absorbing for the block path: every block
+        call then works on Q = D A D, D = diag(1 - flags) - first-passage problems without touching the generator, also
+        on matrix-free boxes.  None (or an empty array) clears the set.  Setting or clearing discards the resident block
+        and its J; the set lives until it is cleared or the generator changes.  Not under a row partition.
+        (kfsp_set_block under option "block_target" = 1: the flags travel as one column of doubles.)"""
+        if flags is None or np.size(flags) == 0:
+            self._target_mode(1, lambda: self._chk(self._lib.kfsp_set_block(self._h, 1, 0, 1, None), "kfsp_set_block (block_target = 1)"))
+        else:
+            f = np.ascontiguousarray(np.asarray(flags).reshape(-1) != 0, dtype=np.float64)
+            self._target_mode(1, lambda: self._chk(self._lib.kfsp_set_block(self._h, 1, f.size, max(f.size, 1), _p(f)),
+                                                   "kfsp_set_block (block_target = 1)"))
+
+    def block_target_info(self):
+        """whether a target set is resident, its number of states, launches of the last block_hit (kfsp_block_info under
+        option "block_target" = 2)"""
+        v = np.zeros(8, dtype=np.int64)
+        self._target_mode(2, lambda: self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info (block_target = 2)"))
+        return {"resident": int(v[0]), "states": int(v[1]), "hit_launches": int(v[2])}
+
+    def block_hit(self, integral=False):
+        """The flux into the target set, per column -> hit[k]: sum over the set of (A X)_i with the unmasked A.  X = W
+        (default): the first-passage density at the solve's current time.  integral=True: X = J (set_option("block_integral",
+        1) before set_block): the probability of having reached the set by the accumulated time; 1 - wsum = hit + leak
+        out of the FSP.  Forward only (-12 under option "adjoint").  (kfsp_block_begin under option "block_target" = 3.)"""
+        k = self._block_k()
+        out = np.zeros(BLOCK_K_MAX, dtype=np.float64)
+        self._target_mode(3, lambda: self._chk(self._lib.kfsp_block_begin(self._h, 1 if integral else 0, _p(out)),
+                                               "kfsp_block_begin (block_target = 3)"))
+        return out[:k].copy()
 
     def spmm_bench(self, reps):
         """ms for reps block products on the resident block"""
