@@ -111,16 +111,10 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
                                                  : (ctx->sell_coded && !force_plain_sell ? 5 : 0));
     const int64_t H = ctx->halo, L = ctx->L;
     const int64_t trip_rows = dia ? 128 : 64;
-    int64_t lo = 0, hi = 0;
+    // interior trips [lo, hi) read no halo row; whether launching them on their own pays: product_split (kfsp_host.h)
     // (a SELL generator takes part when its reach is bounded - the internal state order - and the halo mode was agreed)
-    bool split = !src_is_global && !force_sell && ctx->use_halo && ctx->opt_overlap != 0 && ctx->comm_stream != nullptr;
-    if (split) {
-        // interior trips [lo, hi) read no halo row; whether launching them on their own pays: product_split (kfsp_host.h)
-        const ProductSplit ps = product_split(H, L, trips, trip_rows, ctx->opt_overlap);
-        lo = ps.lo;
-        hi = ps.hi;
-        split = ps.split;
-    }
+    const ProductSplit ps = product_split(H, L, trips, trip_rows, ctx->opt_overlap);
+    const bool split = !src_is_global && !force_sell && ctx->use_halo && ctx->opt_overlap != 0 && ctx->comm_stream != nullptr && ps.split;
     if (!split) {
         const double *xg = src;
         if (!src_is_global)
@@ -170,30 +164,21 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         if (p2) *p2 = Pending{P2, g};
         return 0;
     }
-    // exchange on the communication stream, behind everything that produced src
-    HIP_TRY(hipEventRecord(ctx->ev_src, st));
-    HIP_TRY(hipStreamWaitEvent(ctx->comm_stream, ctx->ev_src, 0));
-    if (int rc = exchange_strips(ctx, src, ctx->comm_stream)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev_halo, ctx->comm_stream));
+    // the exchange beside the interior trips, then the boundary trips: overlapped_product (kfsp_host.h)
     a.xg = src - ctx->row0;
     int used = 0;
-    auto launch_range = [&](int64_t b, int64_t e, int64_t split, int64_t jump, int g) {
-        if (e <= b) return;
-        a.partial = P1 ? P1 + used : nullptr;
-        a.partial2 = P2 ? P2 + used : nullptr;
+    auto launch_range = [&](int64_t b, int64_t e, int64_t split_at, int64_t jump, int g, int at) {
+        if (e <= b) return 0;
+        a.partial = P1 ? P1 + at : nullptr;
+        a.partial2 = P2 ? P2 + at : nullptr;
         a.trip_begin = b;
         a.trip_end = e;
-        a.trip_split = split;
+        a.trip_split = split_at;
         a.trip_jump = jump;
         launch_spmv(mode, g, a, nt, fmt, st, ctx->box_lds_bytes);
-        used += g;
+        return g;
     };
-    // interior: no halo row is read (the boundary launch keeps 512 of the slot's kMaxGrid partials)
-    launch_range(lo, hi, INT64_MAX, 0, std::min(product_grid(hi - lo, ctx->opt_grid, dflt_cap), kMaxGrid - 512));
-    HIP_TRY(hipStreamWaitEvent(st, ctx->ev_halo, 0));
-    // one launch for both boundary ranges: linear trips [0, lo) are themselves,
-    // [lo, lo + trips - hi) stand for [hi, trips)
-    launch_range(0, lo + (trips - hi), lo, hi - lo, product_grid(lo + (trips - hi), 0, 512));
+    if (int rc = overlapped_product(ctx, ps, trips, src, 1, dflt_cap, launch_range, &used)) return rc;
     if (p1) *p1 = Pending{P1, used};
     if (p2) *p2 = Pending{P2, used};
     return 0;

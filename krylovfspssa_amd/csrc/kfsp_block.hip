@@ -24,7 +24,7 @@
 // order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_kernels.hip).
 // Multi-factor boxes (option block_box = 2; DESIGN.md 12, "Multi-factor boxes"): every other matrix-free box, and any box
 // under box_generic = 1, takes the interpreted row of kernel format 3 - k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t
-// (kfsp_block_adj.hip), the row code in kfsp_boxg_dev.h; box_generic_path() and spmm_boxg() below.  Values 0 and 1 of the
+// (kfsp_block_adj.hip), the row code in kfsp_boxg_dev.h; box_generic_path() and spmm_staged() below.  Values 0 and 1 of the
 // option mean what they always meant.
 //
 // Small generators (option block_small; DESIGN.md 12, "Small generators"): where the single-vector path takes its
@@ -38,7 +38,7 @@
 // rank's rows: k_spmm takes local rows and addresses X by global row (SpmmArgs::row0), the source column is made visible
 // before every product the way the single-vector path does it - the neighbours' strips of halo * kp doubles into the
 // column's own margins (exchange_strips with a width), or an all-gather of L * kp doubles into d_bxg - and in halo mode
-// the product is split into an interior launch beside the exchange and one boundary launch (product_split, kfsp_host.h).
+// the product is split into an interior launch beside the exchange and one boundary launch (overlapped_product, kfsp_host.h).
 // Every block-partial sum is all-reduced before the bookkeeping reads it: k_bfinal sums the rank's partials in its fixed
 // order into 2 K staging doubles, one comm_allreduce, k_bfinal again with G = 1 on the reduced sums.  The sequence of
 // collectives of a call depends on k, m, the options and the agreed exchange mode only - never on a column's beta, its
@@ -60,6 +60,7 @@
 
 #include "kfsp_block_dev.h"
 #include "kfsp_box_dev.h"
+#include "kfsp_boxg_dev.h"
 #include "kfsp_host.h"
 
 #include <algorithm>
@@ -724,9 +725,6 @@ __global__ __launch_bounds__(kSmallBlock) void k_bcombine_small_int(int nact, in
 // ---- host side
 const char *const kAdjFormMsg = "several vectors at once, option adjoint: the generator is resident in no form the transposed product reads";
 
-const char *const kBoxReachMsg = "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
-                                 "at this block width (fewer columns, or option box_store = 1)";
-
 int kp_of(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)); }
 
 int spmm_fmt(const kfsp_ctx *c) { return c->use_dia ? (c->dia_masked ? 2 : 1) : (c->sell_coded ? 5 : 0); }
@@ -764,115 +762,113 @@ bool small_path(const kfsp_ctx *c)
 // grid of the streaming kernels over a block column
 int flat_grid(const kfsp_ctx *c, int kp) { return vec_grid(red_pairs(c, kp), c->opt_vgrid); }
 
-// target sets: the row of pair i is i >> pair_shift(kp)
-int pair_shift(int kp) { return kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3)); }
+// A streaming kernel over a block column of width kp: flat_grid workgroups on the context's stream, the pairs and kp / 2
+// in front of the kernel's own arguments.  Returns the grid: that many block partials.
+template <class Kern, class... Args>
+int launch_flat(kfsp_ctx *ctx, int kp, Kern kern, Args... args)
+{
+    const int g = flat_grid(ctx, kp);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2, args...);
+    return g;
+}
 
-// col <- D col for a block column of width kp (row 0 at col); nothing without a set
+d2 *pairs(double *p) { return reinterpret_cast<d2 *>(p); }
+const d2 *pairs(const double *p) { return reinterpret_cast<const d2 *>(p); }
+
+// grid of the pack / unpack kernels over `items` elements
+int pack_grid(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (items + kBlock - 1) / kBlock)); }
+
+// col <- D col for a block column of width kp (row 0 at col; target sets: the row of pair i is i >> kp_index(kp));
+// nothing without a set
 void target_zero(kfsp_ctx *ctx, int kp, double *col)
 {
     if (!ctx->blk_tgt) return;
-    hipLaunchKernelGGL(k_btarget_zero, dim3(flat_grid(ctx, kp)), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), pair_shift(kp),
-                       ctx->d_btgt.p, reinterpret_cast<d2 *>(col));
+    hipLaunchKernelGGL(k_btarget_zero, dim3(flat_grid(ctx, kp)), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp_index(kp),
+                       ctx->d_btgt.p, pairs(col));
 }
 
-template <int KP, bool PART>
-void launch_spmm_kp(int fmt, bool dots, int g, const SpmmArgs &a, hipStream_t st)
+// k_spmm of the stored forms (fmt: spmm_fmt; part: the launch of a rank of a row partition)
+SpmmFn spmm_kernel(int kp, int fmt, bool dots, bool part)
 {
-#define KFSP_SPMM(F)                                                                                   \
-    if (dots) hipLaunchKernelGGL((k_spmm<KP, F, true, PART>), dim3(g), dim3(kBlock), 0, st, a);        \
-    else hipLaunchKernelGGL((k_spmm<KP, F, false, PART>), dim3(g), dim3(kBlock), 0, st, a);
-    switch (fmt) {
-    case 1: KFSP_SPMM(1) break;
-    case 2: KFSP_SPMM(2) break;
-    case 5: KFSP_SPMM(5) break;
-    default: KFSP_SPMM(0) break;
-    }
-#undef KFSP_SPMM
+    return dispatch_kp_dots(kp, dots, [&](auto KP, auto DOTS) {
+        return dispatch_bool(part, [&](auto PART) -> SpmmFn {
+            switch (fmt) {
+            case 1: return k_spmm<decltype(KP)::value, 1, decltype(DOTS)::value, decltype(PART)::value>;
+            case 2: return k_spmm<decltype(KP)::value, 2, decltype(DOTS)::value, decltype(PART)::value>;
+            case 5: return k_spmm<decltype(KP)::value, 5, decltype(DOTS)::value, decltype(PART)::value>;
+            default: return k_spmm<decltype(KP)::value, 0, decltype(DOTS)::value, decltype(PART)::value>;
+            }
+        });
+    });
 }
 
-typedef void (*SpmmBoxFn)(SpmmArgs);
-
-template <int KP, bool DOTS>
-SpmmBoxFn spmm_box_fn_kp(int inst)
+SpmmFn spmm_box_kernel(int kp, int inst, bool dots)
 {
-    // inst = species of the instantiation * 16 + slots per species (BoxDev::pad, kfsp_set_matrix_box)
-    switch (inst) {
-    case 2 * 16 + 2: return k_spmm_box<KP, 2, 2, DOTS>;
-    case 3 * 16 + 2: return k_spmm_box<KP, 3, 2, DOTS>;
-    case 6 * 16 + 2: return k_spmm_box<KP, 6, 2, DOTS>;
-    default: return k_spmm_box<KP, 6, 4, DOTS>;
-    }
-}
-
-SpmmBoxFn spmm_box_fn(int kp, int inst, bool dots)
-{
-    switch (kp) {
-    case 2: return dots ? spmm_box_fn_kp<2, true>(inst) : spmm_box_fn_kp<2, false>(inst);
-    case 4: return dots ? spmm_box_fn_kp<4, true>(inst) : spmm_box_fn_kp<4, false>(inst);
-    case 8: return dots ? spmm_box_fn_kp<8, true>(inst) : spmm_box_fn_kp<8, false>(inst);
-    default: return dots ? spmm_box_fn_kp<16, true>(inst) : spmm_box_fn_kp<16, false>(inst);
-    }
-}
-
-// In the block layout a reach of delta rows is 8 kp delta bytes, and k_spmm_box addresses X as scalar base + unsigned
-// 32-bit lane offset: the backward plus the forward reach plus one 128-row group must stay below 2^32 bytes.
-bool box_block_reach_ok(const kfsp_ctx *c, int kp)
-{
-    const int64_t back = std::max<int64_t>(0, -(int64_t)c->delta[0]), fwd = std::max<int64_t>(0, (int64_t)c->delta[c->nd - 1]);
-    return (back + fwd + 128) * 8 * (int64_t)kp < (1LL << 32);
-}
-
-// Launch geometry of the matrix-free block product, forward and transposed: the dynamic LDS (*lds), the table pointers
-// of `a`, and the grid (returned).  Every workgroup copies the table image first, so no more workgroups are launched than
-// are resident at once (the rule of the single-vector product, run_product): the runtime says how many fit - resident(lds),
-// asked once per width and variant and kept in `cache` (blk_box_occ or blk_box_t_occ).
-template <class Resident>
-int box_block_geometry(const kfsp_ctx *ctx, int kp, bool dots, int (&cache)[4][2], Resident resident, SpmmArgs &a, size_t *lds)
-{
-    *lds = std::max<size_t>(ctx->box_lds_bytes, (size_t)4 * kp * sizeof(double));
-    int &occ = cache[kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3))][dots ? 1 : 0];
-    if (occ == 0) occ = std::max(resident(*lds), 1);
-    a.box_tab = ctx->d_box.p;
-    a.box_ntab = ctx->box.ntab;
-    a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
-    return product_grid(a.trips, ctx->opt_grid, std::min<int64_t>(1024, (int64_t)256 * occ));
+    return dispatch_kp_dots(kp, dots, [&](auto KP, auto DOTS) {
+        return dispatch_box_inst(inst, [](auto NS, auto PER) -> SpmmFn {
+            return k_spmm_box<decltype(KP)::value, decltype(NS)::value, decltype(PER)::value, decltype(DOTS)::value>;
+        });
+    });
 }
 
 // Option block_box = 2: the generic kernels (k_spmm_boxg, kfsp_block_boxg.hip; k_spmm_boxg_t, kfsp_block_adj.hip) answer
 // for a box without the single-factor form and for any box under box_generic = 1.  Read at every block call.
 bool box_generic_path(const kfsp_ctx *c) { return c->use_box && c->opt_block_box == 2 && (!c->box_fast || c->opt_box_generic != 0); }
 
-// Their launch: box_block_geometry's rule with an occupancy cache of their own, less of the image staged (the head and
-// the factor tables only) and the descriptor by value behind SpmmArgs in the kernel's argument (BoxgArgs).  -1: the
-// descriptor is not one they can walk (block_supported refuses that first).
-int spmm_boxg(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
+// In the block layout a reach of delta rows is 8 kp delta bytes, and the single-factor kernels (k_spmm_box, k_spmm_box_t)
+// address X as scalar base + unsigned 32-bit lane offset: the backward plus the forward reach plus one 128-row group must
+// stay below 2^32 bytes.
+bool box_block_reach_ok(const kfsp_ctx *c, int kp)
 {
-    const int32_t ntab = box_generic_image(ctx->box);
-    if (ntab == 0) return -1;
-    size_t lds = 0;
-    const int g = box_block_geometry(ctx, kp, dots, transposed ? ctx->blk_boxg_t_occ : ctx->blk_boxg_occ, [&](size_t) {
-        const size_t bytes = std::max<size_t>((size_t)ntab * sizeof(double), (size_t)4 * kp * sizeof(double));
-        return transposed ? spmm_boxg_t_resident(kp, dots, bytes) : spmm_boxg_resident(kp, dots, bytes);
-    }, a, &lds);
-    lds = std::max<size_t>((size_t)ntab * sizeof(double), (size_t)4 * kp * sizeof(double));
-    a.box_ntab = ntab;
-    a.box_fast = nullptr;
-    if (transposed) launch_spmm_boxg_t(kp, dots, g, lds, a, ctx->box, ctx->stream);
-    else launch_spmm_boxg(kp, dots, g, lds, a, ctx->box, ctx->stream);
+    const int64_t back = std::max<int64_t>(0, -(int64_t)c->delta[0]), fwd = std::max<int64_t>(0, (int64_t)c->delta[c->nd - 1]);
+    return (back + fwd + 128) * 8 * (int64_t)kp < (1LL << 32);
+}
+
+// ... refused where a block of this width meets those kernels (box_generic is read at every call: a block set under the
+// generic kernels, which address X by 64-bit row index, may meet the single-factor ones later)
+int box_reach_check(kfsp_ctx *c, int kp)
+{
+    if (!c->use_box || box_generic_path(c) || box_block_reach_ok(c, kp)) return 0;
+    return fail(c, -12, "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
+                        "at this block width (fewer columns, or option box_store = 1)");
+}
+
+// One launch of a kernel that stages a table image of `image_bytes` into dynamic LDS.  Every workgroup copies the image
+// first, so no more workgroups are launched than are resident at once (the rule of the single-vector product,
+// run_product): the runtime says how many fit, asked once per family, width and variant (blk_staged_occ).  The
+// reductions reuse the image's LDS: never less than 4 kp doubles of it.  Returns the grid.
+template <class... Args>
+int launch_staged(kfsp_ctx *ctx, StagedFamily fam, int kp, bool dots, int64_t trips, size_t image_bytes, void (*kern)(Args...),
+                  const Args &...args)
+{
+    const size_t lds = std::max<size_t>(image_bytes, (size_t)4 * kp * sizeof(double));
+    int &occ = ctx->blk_staged_occ[fam][kp_index(kp)][dots ? 1 : 0];
+    if (occ == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kBlock, lds) != hipSuccess || occ < 1)) occ = 1;
+    const int g = product_grid(trips, ctx->opt_grid, std::min<int64_t>(1024, (int64_t)256 * occ));
+    hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(kBlock), lds, ctx->stream, args...);
     return g;
 }
 
-int spmm_box(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
+// The block product of a matrix-free box, forward or transposed: the table pointers of `a`, then the kernel of the
+// family.  The single-factor kernels stage the whole image and read the descriptor behind it; the generic ones stage
+// the head and the factor tables only and take the box descriptor by value behind SpmmArgs (BoxgArgs).  -1: the
+// descriptor is not one the family can walk (block_supported refuses that first).
+int spmm_staged(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
 {
-    if (box_generic_path(ctx)) return spmm_boxg(ctx, kp, dots, false, a);
-    const SpmmBoxFn fn = spmm_box_fn(kp, ctx->box.pad, dots);
-    size_t lds = 0;
-    const int g = box_block_geometry(ctx, kp, dots, ctx->blk_box_occ, [&](size_t bytes) {
-        int nb = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kBlock, bytes) == hipSuccess ? nb : 1;
-    }, a, &lds);
-    hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kBlock), lds, ctx->stream, a);
-    return g;
+    a.box_tab = ctx->d_box.p;
+    if (box_generic_path(ctx)) {
+        a.box_ntab = box_generic_image(ctx->box);
+        a.box_fast = nullptr;
+        if (a.box_ntab == 0) return -1;
+        return launch_staged(ctx, transposed ? kStagedBoxgT : kStagedBoxg, kp, dots, a.trips, (size_t)a.box_ntab * sizeof(double),
+                             transposed ? spmm_boxg_t_kernel(kp, dots) : spmm_boxg_kernel(kp, dots), BoxgArgs{a, ctx->box});
+    }
+    a.box_ntab = ctx->box.ntab;
+    a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
+    if (!transposed) return launch_staged(ctx, kStagedBox, kp, dots, a.trips, ctx->box_lds_bytes, spmm_box_kernel(kp, ctx->box.pad, dots), a);
+    BoxAdjDev b;
+    if (!box_adj_build(ctx->box, b)) return -1;
+    return launch_staged(ctx, kStagedBoxT, kp, dots, a.trips, ctx->box_lds_bytes, spmm_box_t_kernel(kp, ctx->box.pad, dots), a, b);
 }
 
 // The reference arrays in the order the device keeps its vectors: the relabelled copies under the internal state order.
@@ -887,35 +883,11 @@ bool ell_adj_args(const kfsp_ctx *ctx, EllAdjDev &e)
     return true;
 }
 
-// Y = A^T X (option adjoint, kfsp_block_adj.hip): the grid rules of the forward product of the same form.  -1: the
-// generator is in no form the transposed product reads (block_supported refuses those first).
-int spmm_adjoint(kfsp_ctx *ctx, int kp, bool dots, SpmmArgs &a)
-{
-    if (box_generic_path(ctx)) return spmm_boxg(ctx, kp, dots, true, a);
-    if (ctx->use_box) {
-        BoxAdjDev b;
-        if (!box_adj_build(ctx->box, b)) return -1;
-        size_t lds = 0;
-        const int g = box_block_geometry(ctx, kp, dots, ctx->blk_box_t_occ,
-                                         [&](size_t bytes) { return spmm_box_t_resident(kp, ctx->box.pad, dots, bytes); }, a, &lds);
-        launch_spmm_box_t(kp, ctx->box.pad, dots, g, lds, a, b, ctx->stream);
-        return g;
-    }
-    const int g = spmm_grid(ctx);
-    if (ctx->use_dia) {
-        launch_spmm_t(kp, dots, g, a, ctx->stream);
-        return g;
-    }
-    EllAdjDev e;
-    if (!ell_adj_args(ctx, e)) return -1;
-    launch_spmm_ell_t(kp, dots, g, a, e, ctx->stream);
-    return g;
-}
-
 // Y = A X, or A^T X under option adjoint (block columns of width kp); dots: partials of ua . Y and ub . Y in *G slots.
-// x: row 0 of the source column.  Under a row partition (forward stored forms only, block_supported) the source is made
-// visible first - the strips into x's own margins, or all blocks gathered into d_bxg - unless x_global says that x is
-// row 0 of a whole block every rank already holds (kfsp_spmm).  blk_info[7] records how.
+// x: row 0 of the source column.  The transposed product (kfsp_block_adj.hip) takes the grid of the forward product of
+// the same form.  Under a row partition (forward stored forms only, block_supported) the source is made visible first -
+// the strips into x's own margins, or all blocks gathered into d_bxg - unless x_global says that x is row 0 of a whole
+// block every rank already holds (kfsp_spmm).  blk_info[7] records how.
 int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, const double *ub, bool dots, int *G, bool x_global = false)
 {
     SpmmArgs a;
@@ -937,27 +909,28 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
     a.trip_split = INT64_MAX;
     a.trip_jump = 0;
     ctx->blk_info[7] = 0;
-    if (ctx->opt_adjoint || ctx->use_box) {
-        // (box_generic is read at every call: a block set under the generic kernels may meet the single-factor ones here)
-        if (ctx->use_box && !box_generic_path(ctx) && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
-        const int g = ctx->opt_adjoint ? spmm_adjoint(ctx, kp, dots, a) : spmm_box(ctx, kp, dots, a);
-        if (g < 0) return fail(ctx, -12, kAdjFormMsg);
-        *G = g;
-        return 0;
-    }
     hipStream_t st = ctx->stream;
-    const int fmt = spmm_fmt(ctx);
-    const bool part = ctx->use_comm;
-    auto launch = [&](int g) {
-        switch (kp) {
-        case 2: part ? launch_spmm_kp<2, true>(fmt, dots, g, a, st) : launch_spmm_kp<2, false>(fmt, dots, g, a, st); break;
-        case 4: part ? launch_spmm_kp<4, true>(fmt, dots, g, a, st) : launch_spmm_kp<4, false>(fmt, dots, g, a, st); break;
-        case 8: part ? launch_spmm_kp<8, true>(fmt, dots, g, a, st) : launch_spmm_kp<8, false>(fmt, dots, g, a, st); break;
-        default: part ? launch_spmm_kp<16, true>(fmt, dots, g, a, st) : launch_spmm_kp<16, false>(fmt, dots, g, a, st); break;
-        }
-    };
     const int g = spmm_grid(ctx);
     *G = g;
+    if (ctx->use_box) {
+        if (int rc = box_reach_check(ctx, kp)) return rc;
+        const int gs = spmm_staged(ctx, kp, dots, ctx->opt_adjoint != 0, a);
+        if (gs < 0) return fail(ctx, -12, kAdjFormMsg);      // (block_supported refuses those first)
+        *G = gs;
+        return 0;
+    }
+    if (ctx->opt_adjoint) {
+        if (ctx->use_dia) {
+            hipLaunchKernelGGL(spmm_t_kernel(kp, dots), dim3(g), dim3(kBlock), 0, st, a);
+            return 0;
+        }
+        EllAdjDev e;
+        if (!ell_adj_args(ctx, e)) return fail(ctx, -12, kAdjFormMsg);
+        hipLaunchKernelGGL(spmm_ell_t_kernel(kp, dots), dim3(g), dim3(kBlock), 0, st, a, e);
+        return 0;
+    }
+    const SpmmFn kern = spmm_kernel(kp, spmm_fmt(ctx), dots, ctx->use_comm);
+    auto launch = [&](int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, a); };
     if (!ctx->use_comm) {
         launch(g);
         return 0;
@@ -982,28 +955,18 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
         launch(g);
         return 0;
     }
-    // the strips travel on the communication stream, behind everything that produced x, while the interior trips run
-    HIP_TRY(hipEventRecord(ctx->ev_src, st));
-    HIP_TRY(hipStreamWaitEvent(ctx->comm_stream, ctx->ev_src, 0));
-    if (int rc = exchange_strips(ctx, x, ctx->comm_stream, kp)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev_halo, ctx->comm_stream));
+    // the strips travel on the communication stream while the interior trips run (overlapped_product, kfsp_host.h)
     a.trip_order = nullptr;
-    // interior: no halo row is read (the boundary launch keeps 512 of a slot's kMaxGrid partials, as run_product does)
-    const int g1 = std::min(product_grid(ps.hi - ps.lo, ctx->opt_grid, 1024), kMaxGrid - 512);
-    a.trip_begin = ps.lo;
-    a.trip_end = ps.hi;
-    launch(g1);
-    HIP_TRY(hipStreamWaitEvent(st, ctx->ev_halo, 0));
-    // one launch for both boundary ranges: linear trips [0, lo) are themselves, [lo, lo + trips - hi) stand for [hi, trips)
-    const int64_t nb = ps.lo + (a.trips - ps.hi);
-    const int g2 = product_grid(nb, 0, 512);
-    a.part = ctx->d_bpart.p + (size_t)g1 * K;
-    a.trip_begin = 0;
-    a.trip_end = nb;
-    a.trip_split = ps.lo;
-    a.trip_jump = ps.hi - ps.lo;
-    launch(g2);
-    *G = g1 + g2;
+    auto launch_range = [&](int64_t begin, int64_t end, int64_t split, int64_t jump, int grid, int used) {
+        a.part = ctx->d_bpart.p + (size_t)used * K;
+        a.trip_begin = begin;
+        a.trip_end = end;
+        a.trip_split = split;
+        a.trip_jump = jump;
+        launch(grid);
+        return grid;
+    };
+    if (int rc = overlapped_product(ctx, ps, a.trips, x, kp, 1024, launch_range, G)) return rc;
     ctx->blk_info[7] = 5;
     return 0;
 }
@@ -1035,39 +998,31 @@ int ensure_scalars(kfsp_ctx *ctx)
     return 0;
 }
 
-// what a row partition exchanges block columns through: the strip buffer at block width, the gathered block (zeroed
-// when allocated and whenever the width changes: its margins and the rows behind n must read 0)
-int ensure_exchange(kfsp_ctx *ctx, int kp)
+// `need` doubles in a buffer of block columns laid out for width kp (*laid): zeroed when allocated and whenever the
+// width changes - margins, and the rows behind n, must read 0
+int reserve_for_width(kfsp_ctx *ctx, DevBuf<double> &buf, int *laid, size_t need, int kp)
 {
-    if (!ctx->use_comm) return 0;
-    if (ctx->use_halo) HIP_TRY(ctx->d_strip.reserve((size_t)(2 * ctx->halo) * (size_t)(ctx->nranks + 1) * (size_t)kp, true));
-    const size_t need = xg_len(ctx, kp);
-    if (need > ctx->d_bxg.cap) {
-        ctx->d_bxg.release();
-        HIP_TRY(ctx->d_bxg.reserve(need, true));
-        ctx->bxg_kp = kp;
+    if (need > buf.cap) {
+        buf.release();
+        HIP_TRY(buf.reserve(need, true));
+        *laid = kp;
     }
-    if (ctx->bxg_kp != kp) {
-        HIP_TRY(hipMemsetAsync(ctx->d_bxg.p, 0, ctx->d_bxg.cap * sizeof(double), ctx->stream));
-        ctx->bxg_kp = kp;
+    if (*laid != kp) {
+        HIP_TRY(hipMemsetAsync(buf.p, 0, buf.cap * sizeof(double), ctx->stream));
+        *laid = kp;
     }
     return 0;
 }
 
-// ncols block columns of width kp in d_bv (zeroed whenever the width changes: margins must read 0)
+// ncols block columns of width kp in d_bv; under a row partition also what it exchanges block columns through - the strip
+// buffer at block width and the gathered block; and the scalars
 int ensure_basis(kfsp_ctx *ctx, int kp, int ncols)
 {
-    const size_t need = (size_t)ncols * col_len(ctx, kp);
-    if (need > ctx->d_bv.cap) {
-        ctx->d_bv.release();
-        HIP_TRY(ctx->d_bv.reserve(need, true));
-        ctx->bv_kp = kp;
+    if (int rc = reserve_for_width(ctx, ctx->d_bv, &ctx->bv_kp, (size_t)ncols * col_len(ctx, kp), kp)) return rc;
+    if (ctx->use_comm) {
+        if (ctx->use_halo) HIP_TRY(ctx->d_strip.reserve((size_t)(2 * ctx->halo) * (size_t)(ctx->nranks + 1) * (size_t)kp, true));
+        if (int rc = reserve_for_width(ctx, ctx->d_bxg, &ctx->bxg_kp, xg_len(ctx, kp), kp)) return rc;
     }
-    if (ctx->bv_kp != kp) {
-        HIP_TRY(hipMemsetAsync(ctx->d_bv.p, 0, ctx->d_bv.cap * sizeof(double), ctx->stream));
-        ctx->bv_kp = kp;
-    }
-    if (int rc = ensure_exchange(ctx, kp)) return rc;
     return ensure_scalars(ctx);
 }
 
@@ -1084,8 +1039,7 @@ int upload_block(kfsp_ctx *ctx, int k, int kp, int64_t ld, const double *W, doub
         HIP_TRY(hipMemsetAsync(col0 - (size_t)margin_rows(ctx) * kp, 0, col_len(ctx, kp) * sizeof(double), st));
         for (int c = 0; c < k; ++c)
             if (int rc = upload_states(ctx, W ? W + (size_t)c * ld : W, ctx->d_bstage.p + (size_t)c * L, nl)) return rc;
-        const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (nl * kp + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL(k_bpack, dim3(g), dim3(kBlock), 0, st, nl, k, kp, ctx->d_bstage.p, L, (const int32_t *)nullptr, col0);
+        hipLaunchKernelGGL(k_bpack, dim3(pack_grid(nl * kp)), dim3(kBlock), 0, st, nl, k, kp, ctx->d_bstage.p, L, (const int32_t *)nullptr, col0);
         return 0;
     }
     const int64_t n = ctx->n;
@@ -1094,8 +1048,7 @@ int upload_block(kfsp_ctx *ctx, int k, int kp, int64_t ld, const double *W, doub
     else HIP_TRY(hipMemsetAsync(col0 - (size_t)margin_rows(ctx) * kp, 0, col_len(ctx, kp) * sizeof(double), st));
     HIP_TRY(hipMemcpy2DAsync(ctx->d_bstage.p, (size_t)n * sizeof(double), W, (size_t)ld * sizeof(double), (size_t)n * sizeof(double),
                              (size_t)k, hipMemcpyHostToDevice, st));
-    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n * kp + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_bpack, dim3(g), dim3(kBlock), 0, st, n, k, kp, ctx->d_bstage.p, n, ctx->perm_on ? ctx->d_perm.p : nullptr, col0);
+    hipLaunchKernelGGL(k_bpack, dim3(pack_grid(n * kp)), dim3(kBlock), 0, st, n, k, kp, ctx->d_bstage.p, n, ctx->perm_on ? ctx->d_perm.p : nullptr, col0);
     return 0;
 }
 
@@ -1107,16 +1060,14 @@ int download_block(kfsp_ctx *ctx, int k, int kp, const double *col0, int64_t ld,
     if (ctx->use_comm) {
         const int64_t L = ctx->L;
         HIP_TRY(ctx->d_bstage.reserve((size_t)L * k, false));
-        const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (L * k + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL(k_bunpack, dim3(g), dim3(kBlock), 0, st, L, k, kp, col0, (const int32_t *)nullptr, ctx->d_bstage.p, L);
+        hipLaunchKernelGGL(k_bunpack, dim3(pack_grid(L * k)), dim3(kBlock), 0, st, L, k, kp, col0, (const int32_t *)nullptr, ctx->d_bstage.p, L);
         for (int c = 0; c < k; ++c)
             if (int rc = download_states(ctx, ctx->d_bstage.p + (size_t)c * L, W ? W + (size_t)c * ld : W, ctx->nloc)) return rc;
         return 0;
     }
     const int64_t n = ctx->n;
     HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
-    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n * k + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_bunpack, dim3(g), dim3(kBlock), 0, st, n, k, kp, col0, ctx->perm_on ? ctx->d_iperm.p : nullptr, ctx->d_bstage.p, n);
+    hipLaunchKernelGGL(k_bunpack, dim3(pack_grid(n * k)), dim3(kBlock), 0, st, n, k, kp, col0, ctx->perm_on ? ctx->d_iperm.p : nullptr, ctx->d_bstage.p, n);
     HIP_TRY(hipMemcpy2DAsync(W, (size_t)ld * sizeof(double), ctx->d_bstage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
                              (size_t)k, hipMemcpyDeviceToHost, st));
     return 0;
@@ -1144,10 +1095,7 @@ void block_release(kfsp_ctx *ctx)
     ctx->blk_int = false;
     ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->bxg_kp = ctx->blk_begin_m = 0;
     std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
-    std::memset(ctx->blk_box_occ, 0, sizeof(ctx->blk_box_occ));
-    std::memset(ctx->blk_box_t_occ, 0, sizeof(ctx->blk_box_t_occ));
-    std::memset(ctx->blk_boxg_occ, 0, sizeof(ctx->blk_boxg_occ));
-    std::memset(ctx->blk_boxg_t_occ, 0, sizeof(ctx->blk_boxg_t_occ));
+    std::memset(ctx->blk_staged_occ, 0, sizeof(ctx->blk_staged_occ));
 }
 
 void block_target_release(kfsp_ctx *ctx)
@@ -1243,10 +1191,8 @@ int block_begin(kfsp_ctx *ctx, int m, double *beta)
                            bcol(ctx->d_blk.p, ctx, kp, 0), bcol(ctx->d_bv.p, ctx, kp, 0), ctx->d_bscal.p);
         ctx->blk_info[2] = 1;
     } else {
-        const int g = flat_grid(ctx, kp);
-        hipLaunchKernelGGL((ctx->blk_tgt ? k_bcopy_nrm<true> : k_bcopy_nrm<false>), dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp),
-                           kp / 2, reinterpret_cast<const d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
-                           reinterpret_cast<d2 *>(bcol(ctx->d_bv.p, ctx, kp, 0)), ctx->d_bpart.p, (const uint8_t *)ctx->d_btgt.p, pair_shift(kp));
+        const int g = launch_flat(ctx, kp, ctx->blk_tgt ? k_bcopy_nrm<true> : k_bcopy_nrm<false>, pairs(bcol(ctx->d_blk.p, ctx, kp, 0)),
+                                  pairs(bcol(ctx->d_bv.p, ctx, kp, 0)), ctx->d_bpart.p, ctx->d_btgt.p, kp_index(kp));
         if (int rc = finalize(ctx, kFinBegin, 1, kp, g)) return rc;
         ctx->blk_info[2] = 2;
     }
@@ -1263,14 +1209,12 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
     const int kp = ctx->blk_kp;
     if (int rc = ensure_basis(ctx, kp, m + 2)) return rc;
     hipStream_t st = ctx->stream;
-    const int gv = flat_grid(ctx, kp);
-    const int64_t np = red_pairs(ctx, kp);
     double *V = ctx->d_bv.p;
     auto u = [&](int j) { return bcol(V, ctx, kp, j - 1); };   // u_j, 1-based
     const bool small = small_path(ctx);
     // target set: the update pass and the AVNORM norm mask what the raw product wrote (null: the kernels as they were)
     const uint8_t *tgt = ctx->blk_tgt ? ctx->d_btgt.p : nullptr;
-    const int sh = pair_shift(kp);
+    const int sh = kp_index(kp);
     ctx->blk_info[0] = small ? 1 : 0;
     ctx->blk_info[1] = ctx->blk_info[5] = 0;
     ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
@@ -1300,17 +1244,17 @@ int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nr
         int g = 0;
         if (int rc = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true, &g)) return rc;
         if (int rc = finalize(ctx, kFinDots, j, kp, g)) return rc;
-        hipLaunchKernelGGL((tgt ? k_bortho<true> : k_bortho<false>), dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(j + 1)),
-                           reinterpret_cast<const d2 *>(j >= 2 ? u(j - 1) : nullptr), reinterpret_cast<const d2 *>(u(j)),
-                           ctx->d_bscal.p + kCO, ctx->d_bpart.p, tgt, sh);
+        const int gv = launch_flat(ctx, kp, tgt ? k_bortho<true> : k_bortho<false>, pairs(u(j + 1)), pairs(j >= 2 ? u(j - 1) : nullptr),
+                                   pairs(u(j)), ctx->d_bscal.p + kCO, ctx->d_bpart.p, tgt, sh);
         if (int rc = finalize(ctx, kFinNorm, j, kp, gv, break_tol)) return rc;
     }
     if (!small) {
         // the extra product for AVNORM (:261-263) into the scratch column
         int g = 0;
         if (int rc = spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false, &g)) return rc;
-        if (tgt) hipLaunchKernelGGL(k_bnorm<true>, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<d2 *>(u(m + 2)), ctx->d_bpart.p, tgt, sh);
-        else hipLaunchKernelGGL(k_bnorm<false>, dim3(gv), dim3(kBlock), 0, st, np, kp / 2, reinterpret_cast<const d2 *>(u(m + 2)), ctx->d_bpart.p, tgt, sh);
+        // (two launches for a const: the set's instantiation writes D z back)
+        const int gv = tgt ? launch_flat(ctx, kp, k_bnorm<true>, pairs(u(m + 2)), ctx->d_bpart.p, tgt, sh)
+                           : launch_flat(ctx, kp, k_bnorm<false>, pairs(u(m + 2)), ctx->d_bpart.p, tgt, sh);
         if (int rc = finalize(ctx, kFinAvn, m + 1, kp, gv)) return rc;
     }
     std::vector<double> h((size_t)kScal);
@@ -1331,38 +1275,26 @@ int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
     const int kp = ctx->blk_kp;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(ctx->d_bscal.p + kCMB, coef, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
-    if (ctx->opt_block_integral) {
-        // the same launches with the kernels that carry J along: rows [mx, 2 mx) of coef are J's table
+    // option block_integral: the same launches with the kernels that carry J along; rows [mx, 2 mx) of coef are J's table
+    const bool integral = ctx->opt_block_integral != 0, small = small_path(ctx);
+    if (integral) {
         if (!ctx->blk_int) return fail(ctx, -1, "option block_integral: no integral resident (set the option before kfsp_set_block)");
         HIP_TRY(hipMemcpyAsync(ctx->d_bcj.p, coef + (size_t)mx * K, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
-        if (small_path(ctx)) {
-            hipLaunchKernelGGL(k_bcombine_small_int, dim3(kp), dim3(kSmallBlock), 0, st, (int)(ctx->nchunks * kChunk), kp,
-                               bcol(ctx->d_bv.p, ctx, kp, 0), (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, ctx->d_bcj.p,
-                               bcol(ctx->d_blk.p, ctx, kp, 0), bcol(ctx->d_bint.p, ctx, kp, 0), ctx->d_bscal.p,
-                               ctx->opt_block_clamp ? 1 : 0);
-            ctx->blk_info[4] = 1;
-        } else {
-            const int g = flat_grid(ctx, kp);
-            hipLaunchKernelGGL(k_bcombine_int, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
-                               (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, ctx->d_bcj.p,
-                               reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)), reinterpret_cast<d2 *>(bcol(ctx->d_bint.p, ctx, kp, 0)),
-                               ctx->d_bpart.p, ctx->opt_block_clamp ? 1 : 0);
-            if (int rc = finalize(ctx, kFinWsum, 0, kp, g)) return rc;
-            ctx->blk_info[4] = 2;
-        }
-    } else if (small_path(ctx)) {
-        hipLaunchKernelGGL(k_bcombine_small, dim3(kp), dim3(kSmallBlock), 0, st, (int)(ctx->nchunks * kChunk), kp,
-                           bcol(ctx->d_bv.p, ctx, kp, 0), (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB,
-                           bcol(ctx->d_blk.p, ctx, kp, 0), ctx->d_bscal.p, ctx->opt_block_clamp ? 1 : 0);
-        ctx->blk_info[4] = 1;
-    } else {
-        const int g = flat_grid(ctx, kp);
-        hipLaunchKernelGGL(k_bcombine, dim3(g), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, bcol(ctx->d_bv.p, ctx, kp, 0),
-                           (int64_t)col_len(ctx, kp), mx, ctx->d_bscal.p + kCMB, reinterpret_cast<d2 *>(bcol(ctx->d_blk.p, ctx, kp, 0)),
-                           ctx->d_bpart.p, ctx->opt_block_clamp ? 1 : 0);
-        if (int rc = finalize(ctx, kFinWsum, 0, kp, g)) return rc;
-        ctx->blk_info[4] = 2;
     }
+    const double *U = bcol(ctx->d_bv.p, ctx, kp, 0), *cw = ctx->d_bscal.p + kCMB, *cj = ctx->d_bcj.p;
+    double *w = bcol(ctx->d_blk.p, ctx, kp, 0), *J = integral ? bcol(ctx->d_bint.p, ctx, kp, 0) : nullptr;
+    const int64_t ldc = (int64_t)col_len(ctx, kp);
+    const int clamp = ctx->opt_block_clamp ? 1 : 0;
+    if (small) {
+        const int nact = (int)(ctx->nchunks * kChunk);
+        if (integral) hipLaunchKernelGGL(k_bcombine_small_int, dim3(kp), dim3(kSmallBlock), 0, st, nact, kp, U, ldc, mx, cw, cj, w, J, ctx->d_bscal.p, clamp);
+        else hipLaunchKernelGGL(k_bcombine_small, dim3(kp), dim3(kSmallBlock), 0, st, nact, kp, U, ldc, mx, cw, w, ctx->d_bscal.p, clamp);
+    } else {
+        const int g = integral ? launch_flat(ctx, kp, k_bcombine_int, U, ldc, mx, cw, cj, pairs(w), pairs(J), ctx->d_bpart.p, clamp)
+                               : launch_flat(ctx, kp, k_bcombine, U, ldc, mx, cw, pairs(w), ctx->d_bpart.p, clamp);
+        if (int rc = finalize(ctx, kFinWsum, 0, kp, g)) return rc;
+    }
+    ctx->blk_info[4] = small ? 1 : 2;
     HIP_TRY(hipMemcpyAsync(wsum, ctx->d_bscal.p + kWS, K * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -1386,6 +1318,25 @@ static int64_t target_mode(kfsp_ctx *ctx)
     return l ? l->opt_block_target : 0;
 }
 
+// what the calls on a resident block share: a context that takes blocks and holds one
+static int block_call_ok(kfsp_ctx *ctx, const char *none = "no block resident (none was set, or the generator changed since)")
+{
+    if (int rc = block_supported(ctx)) return rc;
+    if (lead(ctx)->blk_k == 0) return fail(ctx, -1, none);
+    return 0;
+}
+
+// n, ldw and W of kfsp_set_block / kfsp_get_block.  A rank's arguments are its own (a caller that gets them wrong on one
+// rank only leaves the others waiting, as in kfsp_set_vector); a rank without rows may pass no W.
+static int block_args_ok(kfsp_ctx *ctx, int64_t n, int64_t ldw, const double *W)
+{
+    if (n != (ctx->use_comm ? ctx->nloc : ctx->n))
+        return fail(ctx, -3, ctx->use_comm ? "n is not this rank's block size" : "n is not the number of states of the generator");
+    if (ldw < n) return fail(ctx, -4, "ldw < n");
+    if (!W && !(ctx->use_comm && n == 0)) return fail(ctx, -5, "null W");
+    return 0;
+}
+
 int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W)
 {
     if (!ctx) return -1;
@@ -1394,20 +1345,10 @@ int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const doubl
         if (int rc = block_supported(ctx)) return rc;
         if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
         if (ctx->group) return group_set_block(ctx, k, n, ldw, W);
-        // (a rank's arguments are its own: a caller that gets them wrong on one rank only leaves the others waiting, as in
-        // kfsp_set_vector)
-        if (ctx->use_comm) {
-            if (n != ctx->nloc) return fail(ctx, -3, "n is not this rank's block size");
-            if (ldw < n) return fail(ctx, -4, "ldw < n");
-            if (!W && n > 0) return fail(ctx, -5, "null W");
-        } else {
-            if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
-            if (ldw < n) return fail(ctx, -4, "ldw < n");
-            if (!W) return fail(ctx, -5, "null W");
-        }
+        if (int rc = block_args_ok(ctx, n, ldw, W)) return rc;
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
-        if (ctx->use_box && !box_generic_path(ctx) && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
+        if (int rc = box_reach_check(ctx, kp)) return rc;
         ctx->blk_k = ctx->blk_begin_m = 0;
         ctx->blk_int = false;
         if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
@@ -1438,23 +1379,14 @@ int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W)
 {
     if (!ctx) return -1;
     return guarded(ctx, [&]() -> int {
-        if (int rc = block_supported(ctx)) return rc;
-        if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
+        if (int rc = block_call_ok(ctx)) return rc;
         if (k != lead(ctx)->blk_k) return fail(ctx, -2, "k is not the number of columns of the resident block");
         // option block_integral = 2: the answer is J, by the route W takes
         const bool want_j = lead(ctx)->opt_block_integral == 2;
         if (want_j)
             if (int on = 0; int rc = block_integral(ctx, &on)) return rc;
         if (ctx->group) return group_get_block(ctx, k, n, ldw, W);
-        if (ctx->use_comm) {
-            if (n != ctx->nloc) return fail(ctx, -3, "n is not this rank's block size");
-            if (ldw < n) return fail(ctx, -4, "ldw < n");
-            if (!W && n > 0) return fail(ctx, -5, "null W");
-        } else {
-            if (n != ctx->n) return fail(ctx, -3, "n is not the number of states of the generator");
-            if (ldw < n) return fail(ctx, -4, "ldw < n");
-            if (!W) return fail(ctx, -5, "null W");
-        }
+        if (int rc = block_args_ok(ctx, n, ldw, W)) return rc;
         HIP_TRY(hipSetDevice(ctx->device));
         if (int rc = download_block(ctx, k, ctx->blk_kp, bcol(want_j ? ctx->d_bint.p : ctx->d_blk.p, ctx, ctx->blk_kp, 0), ldw, W)) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1474,7 +1406,7 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         if (!Y && !(ctx->use_comm && ctx->nloc == 0)) return fail(ctx, -5, "null Y");
         HIP_TRY(hipSetDevice(ctx->device));
         const int kp = kp_of(k);
-        if (ctx->use_box && !box_generic_path(ctx) && !box_block_reach_ok(ctx, kp)) return fail(ctx, -12, kBoxReachMsg);
+        if (int rc = box_reach_check(ctx, kp)) return rc;
         if (int rc = ensure_basis(ctx, kp, 2)) return rc;
         // under a row partition X is the whole block on every rank (the kfsp_spmv convention): it goes to the gathered
         // block buffer, global row 0 first, and no exchange follows
@@ -1490,14 +1422,6 @@ int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return 0;
     });
-}
-
-// what the three pass calls share: a context that takes blocks and holds one
-static int block_call_ok(kfsp_ctx *ctx)
-{
-    if (int rc = block_supported(ctx)) return rc;
-    if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident (none was set, or the generator changed since)");
-    return 0;
 }
 
 int kfsp_block_begin(kfsp_ctx *ctx, int32_t m, double *beta)
@@ -1577,8 +1501,7 @@ static int set_block_target(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldf, co
         hipError_t e = stage.reserve((size_t)n, false);
         if (e == hipSuccess) e = hipMemcpyAsync(stage.p, flags.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
-            const int g = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (rows + kBlock - 1) / kBlock));
-            hipLaunchKernelGGL(k_btarget_pack, dim3(g), dim3(kBlock), 0, ctx->stream, n, rows, (const uint8_t *)stage.p,
+            hipLaunchKernelGGL(k_btarget_pack, dim3(pack_grid(rows)), dim3(kBlock), 0, ctx->stream, n, rows, (const uint8_t *)stage.p,
                                ctx->perm_on ? (const int32_t *)ctx->d_perm.p : nullptr, ctx->d_btgt.p);
             e = hipStreamSynchronize(ctx->stream);
         }
@@ -1627,9 +1550,7 @@ static int block_hit(kfsp_ctx *ctx, int32_t which, double *out)
         double *y = bcol(ctx->d_bhit.p, ctx, kp, 0);
         int g = 0;
         if (int rc = spmm(ctx, kp, bcol(which ? ctx->d_bint.p : ctx->d_blk.p, ctx, kp, 0), y, nullptr, nullptr, false, &g)) return rc;
-        const int gv = flat_grid(ctx, kp);
-        hipLaunchKernelGGL(k_bhit, dim3(gv), dim3(kBlock), 0, st, red_pairs(ctx, kp), kp / 2, pair_shift(kp), (const uint8_t *)ctx->d_btgt.p,
-                           reinterpret_cast<const d2 *>(y), ctx->d_bpart.p);
+        const int gv = launch_flat(ctx, kp, k_bhit, kp_index(kp), ctx->d_btgt.p, pairs(y), ctx->d_bpart.p);
         // the sum stage of k_bfinal alone: the block partials in its fixed order (both of its sums read the same ones)
         hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, st, (int)kFinWsum, 0, kp, gv, ctx->d_bpart.p, (int64_t)0, ctx->d_bscal.p, 0.0,
                            ctx->d_bhsum.p);
@@ -1646,8 +1567,7 @@ int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)
 {
     if (!ctx) return -1;
     return guarded(ctx, [&]() -> int {
-        if (int rc = block_supported(ctx)) return rc;
-        if (lead(ctx)->blk_k == 0) return fail(ctx, -1, "no block resident");
+        if (int rc = block_call_ok(ctx, "no block resident")) return rc;
         if (reps < 1) return fail(ctx, -2, "reps < 1");
         if (!ms_total) return fail(ctx, -3, "null ms_total");
         if (ctx->group) return group_spmm_bench(ctx, reps, ms_total);

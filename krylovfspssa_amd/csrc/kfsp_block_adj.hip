@@ -255,29 +255,6 @@ __global__ __launch_bounds__(kBlock) void k_spmm_box_t(SpmmArgs a, BoxAdjDev b)
     }
 }
 
-typedef void (*SpmmBoxTFn)(SpmmArgs, BoxAdjDev);
-
-template <int KP, bool DOTS>
-SpmmBoxTFn spmm_box_t_fn_kp(int inst)
-{
-    switch (inst) {
-    case 2 * 16 + 2: return k_spmm_box_t<KP, 2, 2, DOTS>;
-    case 3 * 16 + 2: return k_spmm_box_t<KP, 3, 2, DOTS>;
-    case 6 * 16 + 2: return k_spmm_box_t<KP, 6, 2, DOTS>;
-    default: return k_spmm_box_t<KP, 6, 4, DOTS>;
-    }
-}
-
-SpmmBoxTFn spmm_box_t_fn(int kp, int inst, bool dots)
-{
-    switch (kp) {
-    case 2: return dots ? spmm_box_t_fn_kp<2, true>(inst) : spmm_box_t_fn_kp<2, false>(inst);
-    case 4: return dots ? spmm_box_t_fn_kp<4, true>(inst) : spmm_box_t_fn_kp<4, false>(inst);
-    case 8: return dots ? spmm_box_t_fn_kp<8, true>(inst) : spmm_box_t_fn_kp<8, false>(inst);
-    default: return dots ? spmm_box_t_fn_kp<16, true>(inst) : spmm_box_t_fn_kp<16, false>(inst);
-    }
-}
-
 // Any matrix-free box (option block_box = 2): the interpreted row, transposed.  The descriptor is the forward product's.
 template <int KP, bool DOTS>
 __global__ __launch_bounds__(kBlock) void k_spmm_boxg_t(BoxgArgs)
@@ -285,70 +262,31 @@ __global__ __launch_bounds__(kBlock) void k_spmm_boxg_t(BoxgArgs)
     spmm_boxg_body<KP, DOTS, true>();
 }
 
-typedef void (*SpmmBoxgFn)(BoxgArgs);
-
-SpmmBoxgFn spmm_boxg_t_fn(int kp, bool dots)
-{
-    switch (kp) {
-    case 2: return dots ? k_spmm_boxg_t<2, true> : k_spmm_boxg_t<2, false>;
-    case 4: return dots ? k_spmm_boxg_t<4, true> : k_spmm_boxg_t<4, false>;
-    case 8: return dots ? k_spmm_boxg_t<8, true> : k_spmm_boxg_t<8, false>;
-    default: return dots ? k_spmm_boxg_t<16, true> : k_spmm_boxg_t<16, false>;
-    }
-}
-
 }  // namespace
 
-void launch_spmm_t(int kp, bool dots, int grid, const SpmmArgs &a, hipStream_t st)
+// ---- the kernels by function pointer (kfsp_block_dev.h): kfsp_block.hip launches them
+SpmmFn spmm_t_kernel(int kp, bool dots)
 {
-#define KFSP_SPMM_T(KP)                                                                                  \
-    if (dots) hipLaunchKernelGGL((k_spmm_t<KP, true>), dim3(grid), dim3(kBlock), 0, st, a);             \
-    else hipLaunchKernelGGL((k_spmm_t<KP, false>), dim3(grid), dim3(kBlock), 0, st, a);
-    switch (kp) {
-    case 2: KFSP_SPMM_T(2) break;
-    case 4: KFSP_SPMM_T(4) break;
-    case 8: KFSP_SPMM_T(8) break;
-    default: KFSP_SPMM_T(16) break;
-    }
-#undef KFSP_SPMM_T
+    return dispatch_kp_dots(kp, dots, [](auto KP, auto DOTS) -> SpmmFn { return k_spmm_t<decltype(KP)::value, decltype(DOTS)::value>; });
 }
 
-void launch_spmm_ell_t(int kp, bool dots, int grid, const SpmmArgs &a, const EllAdjDev &e, hipStream_t st)
+SpmmEllTFn spmm_ell_t_kernel(int kp, bool dots)
 {
-#define KFSP_SPMM_T(KP)                                                                                  \
-    if (dots) hipLaunchKernelGGL((k_spmm_ell_t<KP, true>), dim3(grid), dim3(kBlock), 0, st, a, e);      \
-    else hipLaunchKernelGGL((k_spmm_ell_t<KP, false>), dim3(grid), dim3(kBlock), 0, st, a, e);
-    switch (kp) {
-    case 2: KFSP_SPMM_T(2) break;
-    case 4: KFSP_SPMM_T(4) break;
-    case 8: KFSP_SPMM_T(8) break;
-    default: KFSP_SPMM_T(16) break;
-    }
-#undef KFSP_SPMM_T
+    return dispatch_kp_dots(kp, dots, [](auto KP, auto DOTS) -> SpmmEllTFn { return k_spmm_ell_t<decltype(KP)::value, decltype(DOTS)::value>; });
 }
 
-int spmm_box_t_resident(int kp, int inst, bool dots, size_t lds)
+SpmmBoxTFn spmm_box_t_kernel(int kp, int inst, bool dots)
 {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, spmm_box_t_fn(kp, inst, dots), kBlock, lds) != hipSuccess) nb = 1;
-    return nb > 1 ? nb : 1;
+    return dispatch_kp_dots(kp, dots, [&](auto KP, auto DOTS) {
+        return dispatch_box_inst(inst, [](auto NS, auto PER) -> SpmmBoxTFn {
+            return k_spmm_box_t<decltype(KP)::value, decltype(NS)::value, decltype(PER)::value, decltype(DOTS)::value>;
+        });
+    });
 }
 
-void launch_spmm_box_t(int kp, int inst, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxAdjDev &b, hipStream_t st)
+SpmmBoxgFn spmm_boxg_t_kernel(int kp, bool dots)
 {
-    hipLaunchKernelGGL(spmm_box_t_fn(kp, inst, dots), dim3((unsigned)grid), dim3(kBlock), lds, st, a, b);
-}
-
-int spmm_boxg_t_resident(int kp, bool dots, size_t lds)
-{
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, spmm_boxg_t_fn(kp, dots), kBlock, lds) != hipSuccess) nb = 1;
-    return nb > 1 ? nb : 1;
-}
-
-void launch_spmm_boxg_t(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st)
-{
-    hipLaunchKernelGGL(spmm_boxg_t_fn(kp, dots), dim3((unsigned)grid), dim3(kBlock), lds, st, BoxgArgs{a, b});
+    return dispatch_kp_dots(kp, dots, [](auto KP, auto DOTS) -> SpmmBoxgFn { return k_spmm_boxg_t<decltype(KP)::value, decltype(DOTS)::value>; });
 }
 
 }  // namespace kfsp

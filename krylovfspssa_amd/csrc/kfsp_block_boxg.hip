@@ -18,30 +18,11 @@ __global__ __launch_bounds__(kBlock) void k_spmm_boxg(BoxgArgs)
     spmm_boxg_body<KP, DOTS, false>();
 }
 
-typedef void (*SpmmBoxgFn)(BoxgArgs);
-
-SpmmBoxgFn spmm_boxg_fn(int kp, bool dots)
-{
-    switch (kp) {
-    case 2: return dots ? k_spmm_boxg<2, true> : k_spmm_boxg<2, false>;
-    case 4: return dots ? k_spmm_boxg<4, true> : k_spmm_boxg<4, false>;
-    case 8: return dots ? k_spmm_boxg<8, true> : k_spmm_boxg<8, false>;
-    default: return dots ? k_spmm_boxg<16, true> : k_spmm_boxg<16, false>;
-    }
-}
-
 }  // namespace
 
-int spmm_boxg_resident(int kp, bool dots, size_t lds)
+SpmmBoxgFn spmm_boxg_kernel(int kp, bool dots)
 {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, spmm_boxg_fn(kp, dots), kBlock, lds) != hipSuccess) nb = 1;
-    return nb > 1 ? nb : 1;
-}
-
-void launch_spmm_boxg(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st)
-{
-    hipLaunchKernelGGL(spmm_boxg_fn(kp, dots), dim3((unsigned)grid), dim3(kBlock), lds, st, BoxgArgs{a, b});
+    return dispatch_kp_dots(kp, dots, [](auto KP, auto DOTS) -> SpmmBoxgFn { return k_spmm_boxg<decltype(KP)::value, decltype(DOTS)::value>; });
 }
 
 }  // namespace kfsp

@@ -7,10 +7,57 @@
 #include "kfsp_block.h"
 #include "kfsp_internal.h"
 
+#include <type_traits>
+
 namespace kfsp {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef int i2 __attribute__((ext_vector_type(2)));
+
+// ---- from run-time widths and variants to kernel instantiations: the one place that spells the cases out (plain host
+// code: tests/block_dispatch_check.cpp)
+// log2(kp) - 1 for a block width kp in {2, 4, 8, 16}: the slot of the width in a table, and the shift from a 16-byte pair
+// of a block column to its row (pair i lies in row i >> kp_index(kp))
+constexpr int kp_index(int kp) { return kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3)); }
+
+// f(std::integral_constant<int, KP>) for the width; anything that is not 2, 4 or 8 takes 16
+template <class F>
+decltype(auto) dispatch_kp(int kp, F &&f)
+{
+    switch (kp) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+    }
+}
+
+template <class F>
+decltype(auto) dispatch_bool(bool on, F &&f)
+{
+    return on ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// f(width, std::bool_constant<dots>): what nearly every product kernel is instantiated by
+template <class F>
+decltype(auto) dispatch_kp_dots(int kp, bool dots, F &&f)
+{
+    return dispatch_kp(kp, [&](auto KP) { return dots ? f(KP, std::true_type{}) : f(KP, std::false_type{}); });
+}
+
+// f(species, slots per species) of the single-factor box instantiation; inst = species * 16 + slots per species
+// (BoxDev::pad, kfsp_set_matrix_box), anything else takes the widest one
+template <class F>
+decltype(auto) dispatch_box_inst(int inst, F &&f)
+{
+    using std::integral_constant;
+    switch (inst) {
+    case 2 * 16 + 2: return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+    case 3 * 16 + 2: return f(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    case 6 * 16 + 2: return f(integral_constant<int, 6>{}, integral_constant<int, 2>{});
+    default: return f(integral_constant<int, 6>{}, integral_constant<int, 4>{});
+    }
+}
 
 #if defined(__HIPCC__)
 template <int KP>
@@ -203,20 +250,23 @@ static inline bool ell_adj_resident(int64_t n, int64_t ell_cols, int32_t ell_ld,
     return cap_adj >= nent && cap_off >= nent && cap_diag >= (size_t)n;
 }
 
-// launches (kfsp_block_adj.hip); the grid is the caller's.  Hidden: the shared object exports nothing new.
+// The kernels of the other translation units, by function pointer: kfsp_block.hip launches them (the grid and the LDS
+// are its business).  Hidden: the shared object exports nothing new.
+struct BoxgArgs;   // kfsp_boxg_dev.h
+typedef void (*SpmmFn)(SpmmArgs);
+typedef void (*SpmmEllTFn)(SpmmArgs, EllAdjDev);
+typedef void (*SpmmBoxTFn)(SpmmArgs, BoxAdjDev);
+typedef void (*SpmmBoxgFn)(BoxgArgs);
 #define KFSP_LOCAL __attribute__((visibility("hidden")))
-KFSP_LOCAL void launch_spmm_t(int kp, bool dots, int grid, const SpmmArgs &a, hipStream_t st);
-KFSP_LOCAL void launch_spmm_ell_t(int kp, bool dots, int grid, const SpmmArgs &a, const EllAdjDev &e, hipStream_t st);
-// workgroups of k_spmm_box_t resident per CU with `lds` bytes of dynamic LDS (>= 1)
-KFSP_LOCAL int spmm_box_t_resident(int kp, int inst, bool dots, size_t lds);
-KFSP_LOCAL void launch_spmm_box_t(int kp, int inst, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxAdjDev &b,
-                                  hipStream_t st);
-// the generic matrix-free kernels (option block_box = 2): k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t
-// (kfsp_block_adj.hip); a.box_ntab doubles of the image are staged into `lds` bytes of dynamic LDS
-KFSP_LOCAL int spmm_boxg_resident(int kp, bool dots, size_t lds);
-KFSP_LOCAL void launch_spmm_boxg(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st);
-KFSP_LOCAL int spmm_boxg_t_resident(int kp, bool dots, size_t lds);
-KFSP_LOCAL void launch_spmm_boxg_t(int kp, bool dots, int grid, size_t lds, const SpmmArgs &a, const BoxDev &b, hipStream_t st);
+KFSP_LOCAL SpmmFn spmm_t_kernel(int kp, bool dots);                    // k_spmm_t (kfsp_block_adj.hip)
+KFSP_LOCAL SpmmEllTFn spmm_ell_t_kernel(int kp, bool dots);            // k_spmm_ell_t
+KFSP_LOCAL SpmmBoxTFn spmm_box_t_kernel(int kp, int inst, bool dots);  // k_spmm_box_t
+KFSP_LOCAL SpmmBoxgFn spmm_boxg_t_kernel(int kp, bool dots);           // k_spmm_boxg_t
+KFSP_LOCAL SpmmBoxgFn spmm_boxg_kernel(int kp, bool dots);             // k_spmm_boxg (kfsp_block_boxg.hip)
 #undef KFSP_LOCAL
+
+// the four kernel families that stage the table image of a matrix-free box into dynamic LDS: first index of the
+// occupancy cache (kfsp_ctx::blk_staged_occ)
+enum StagedFamily { kStagedBox = 0, kStagedBoxT = 1, kStagedBoxg = 2, kStagedBoxgT = 3 };
 
 }  // namespace kfsp

@@ -328,9 +328,8 @@ struct kfsp_ctx {
     int bv_kp = 0;               // width d_bv is laid out for
     int blk_begin_m = 0;         // Krylov dimension the last block_begin laid the basis out for (0: none since kfsp_set_block)
     int64_t blk_info[8] = {};    // kfsp_block_info: how the last block_begin / block_arnoldi / block_combine ran
-    int blk_box_occ[4][2] = {};  // workgroups of k_spmm_box resident per CU, by [log2 kp - 1][dots] (0: not asked yet)
-    int blk_box_t_occ[4][2] = {};   // the same for k_spmm_box_t (kfsp_block_adj.hip)
-    int blk_boxg_occ[4][2] = {}, blk_boxg_t_occ[4][2] = {};   // ... for k_spmm_boxg (kfsp_block_boxg.hip) and k_spmm_boxg_t
+    int blk_staged_occ[4][4][2] = {};   // workgroups resident per CU of the kernels that stage a box's table image, by
+                                        // [StagedFamily][kp_index(kp)][dots] (kfsp_block_dev.h; 0: not asked yet)
     DevBuf<double> d_bint, d_bcj;   // option block_integral: J, the time integral of the resident block (laid out like d_blk), and
                                     // its coefficient table; allocated by kfsp_set_block while the option is on, never otherwise
     bool blk_int = false;           // J is resident beside the block

@@ -91,6 +91,30 @@ inline ProductSplit product_split(int64_t H, int64_t L, int64_t trips, int64_t t
     return s;
 }
 
+// The split product itself.  The strips of `src` (width doubles per row) travel on the communication stream, behind
+// everything that produced src, while the interior trips run on the compute stream; the boundary trips follow once the
+// halo has landed, as ONE launch: linear trips [0, lo) are themselves, [lo, lo + trips - hi) stand for [hi, trips).
+// launch_range(begin, end, split, jump, grid, used) launches the linear trips [begin, end) (SpmvArgs / SpmmArgs:
+// trip_split, trip_jump) on `grid` workgroups with its block partials `used` slots into the caller's buffer, and returns
+// the slots it took.  The interior keeps 512 of a slot's kMaxGrid partials free for the boundary launch.  *used: the
+// slots of both launches.  The caller has set trip_order = nullptr: the ranges are linear.
+template <class LaunchRange>
+int overlapped_product(kfsp_ctx *ctx, const ProductSplit &ps, int64_t trips, const double *src, int width, int64_t dflt_cap,
+                       LaunchRange &&launch_range, int *used)
+{
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipEventRecord(ctx->ev_src, st));
+    HIP_TRY(hipStreamWaitEvent(ctx->comm_stream, ctx->ev_src, 0));
+    if (int rc = exchange_strips(ctx, src, ctx->comm_stream, width)) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev_halo, ctx->comm_stream));
+    const int g1 = std::min(product_grid(ps.hi - ps.lo, ctx->opt_grid, dflt_cap), kMaxGrid - 512);
+    *used = launch_range(ps.lo, ps.hi, INT64_MAX, (int64_t)0, g1, 0);
+    HIP_TRY(hipStreamWaitEvent(st, ctx->ev_halo, 0));
+    const int64_t nb = ps.lo + (trips - ps.hi);
+    *used += launch_range((int64_t)0, nb, ps.lo, ps.hi - ps.lo, product_grid(nb, 0, 512), *used);
+    return 0;
+}
+
 // Rows of margin on either side of every basis column once strips of H rows are exchanged (setup_exchange): the strip,
 // a quarter of head room, and 128 rows because the banded kernel works on 128-row groups whose padded half reads up to
 // one group beyond the block end.  A multiple of 64.
