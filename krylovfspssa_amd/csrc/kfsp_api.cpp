@@ -26,9 +26,6 @@ int64_t act_pairs(const kfsp_ctx *c) { return c->nchunks * (kChunk / 2); }
 
 int vec_grid(const kfsp_ctx *c) { return kfsp::vec_grid(act_pairs(c), c->opt_vgrid); }
 
-// the product reads the dictionary-coded image of the banded values (kernel format 9): unmasked, single rank, stored
-bool dia_code_on(const kfsp_ctx *c) { return c->use_dia && !c->use_box && c->dia_coded && !c->dia_masked && !c->use_comm; }
-
 bool use_nt(const kfsp_ctx *c)
 {
     if (c->opt_nt >= 0) return c->opt_nt != 0;
@@ -50,11 +47,7 @@ double *next_partial(kfsp_ctx *c)
 void set_matrix_args(const kfsp_ctx *c, SpmvArgs &a)
 {
     generator_args(c, a.A, a.D);
-    a.C.rec = c->d_dcode.p;
-    a.C.dict = c->d_ddict.p;
-    for (int d = 0; d <= kMaxDiag; ++d) a.C.doff[d] = c->dia_doff[d];
-    a.C.w = c->dia_code_w;
-    a.C.rec_bytes = c->dia_code_rec;
+    dia_code_args(c, a.C);
     if (c->use_box) a.B = c->box;
     else a.B.ns = a.B.nr = a.B.ntab = 0;
     a.box_tab = c->d_box.p;
@@ -2209,6 +2202,7 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "box_tile") ctx->opt_box_tile = value;
     else if (k == "block_box") ctx->opt_block_box = value;
     else if (k == "block_small") ctx->opt_block_small = value;
+    else if (k == "block_dia_code") ctx->opt_block_dia_code = value != 0;
     else if (k == "block_partition") ctx->opt_block_partition = value != 0;
     else if (k == "adjoint") ctx->opt_adjoint = value != 0;
     else if (k == "block_clamp") ctx->opt_block_clamp = value != 0;

@@ -56,6 +56,12 @@
 // instantiations of k_bcopy_nrm / k_bortho / k_bnorm put +0.0 on T before they sum.  kfsp_set_block stores D W, kfsp_spmm
 // masks X and Y (k_btarget_zero), the flux mode of kfsp_block_begin sums one raw product over T (k_bhit + the sum stage of k_bfinal).  With no
 // set resident the false instantiations run: the code as it was, no launch and no allocation more.
+//
+// Coded banded generators (option block_dia_code; DESIGN.md 12, "Coded banded generators").  OPT-IN: with 1 the forward
+// product of a banded generator whose coded image the single-vector product reads (dia_code_on, kfsp_host.h) takes
+// k_spmm_diac (kfsp_block_diac.hip) - one record per row and the dictionaries in LDS instead of nd value streams, the
+// same bits - unless the call is a transposed one or the one-launch small pass (spmm_diac_for below).  Everything else
+// keeps its kernel; with the option at 0 no launch, byte or report changes.
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
@@ -836,12 +842,19 @@ int box_reach_check(kfsp_ctx *c, int kp)
 // One launch of a kernel that stages a table image of `image_bytes` into dynamic LDS.  Every workgroup copies the image
 // first, so no more workgroups are launched than are resident at once (the rule of the single-vector product,
 // run_product): the runtime says how many fit, asked once per family, width and variant (blk_staged_occ).  The
-// reductions reuse the image's LDS: never less than 4 kp doubles of it.  Returns the grid.
+// reductions of the box kernels reuse the image's LDS: never less than 4 kp doubles of it; the coded banded kernel keeps
+// its reduction scratch apart (static LDS) and asks for the dictionaries alone (staged_lds: the dynamic LDS of the launch).
+// Returns the grid.
+size_t staged_lds(StagedFamily fam, size_t image_bytes, int kp)
+{
+    return fam == kStagedDiac ? image_bytes : std::max<size_t>(image_bytes, (size_t)4 * kp * sizeof(double));
+}
+
 template <class... Args>
 int launch_staged(kfsp_ctx *ctx, StagedFamily fam, int kp, bool dots, int64_t trips, size_t image_bytes, void (*kern)(Args...),
                   const Args &...args)
 {
-    const size_t lds = std::max<size_t>(image_bytes, (size_t)4 * kp * sizeof(double));
+    const size_t lds = staged_lds(fam, image_bytes, kp);
     int &occ = ctx->blk_staged_occ[fam][kp_index(kp)][dots ? 1 : 0];
     if (occ == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kBlock, lds) != hipSuccess || occ < 1)) occ = 1;
     const int g = product_grid(trips, ctx->opt_grid, std::min<int64_t>(1024, (int64_t)256 * occ));
@@ -869,6 +882,19 @@ int spmm_staged(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
     BoxAdjDev b;
     if (!box_adj_build(ctx->box, b)) return -1;
     return launch_staged(ctx, kStagedBoxT, kp, dots, a.trips, ctx->box_lds_bytes, spmm_box_t_kernel(kp, ctx->box.pad, dots), a, b);
+}
+
+// Option block_dia_code: the kernel that reads the coded banded image for this call, or null - the rule of
+// block_dia_code_path (kfsp_host.h), a form dispatch_diac knows, and an image that is what the kernel walks: records for
+// every row a trip touches, all codes of a row inside its record, the dictionaries within the LDS budget.  Null: the
+// plain kernel runs, as it always has.  Read at every block call.
+SpmmDiacFn spmm_diac_for(const kfsp_ctx *c, int kp, bool dots, int64_t trips)
+{
+    if (!block_dia_code_path(dia_code_on(c), c->opt_block_dia_code, c->opt_adjoint != 0, small_path(c))) return nullptr;
+    const int w = c->dia_code_w, rec = c->dia_code_rec, nd = c->nd;
+    if (nd < 1 || nd > kMaxDiag || w < 1 || nd * w > rec * 8 || c->dia_ld < trips * 128) return nullptr;
+    if (c->dia_doff[nd] < 1 || (int64_t)c->dia_doff[nd] * 8 > kDiaCodeLds) return nullptr;
+    return spmm_diac_kernel(kp, w, rec, dots);
 }
 
 // The reference arrays in the order the device keeps its vectors: the relabelled copies under the internal state order.
@@ -909,6 +935,9 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
     a.trip_split = INT64_MAX;
     a.trip_jump = 0;
     ctx->blk_info[7] = 0;
+    // option block_dia_code: slots 1 and 5 say, product by product, whether the coded kernel ran (9, its dynamic LDS) or
+    // not (0, 0); with the option off nothing here writes them
+    if (ctx->opt_block_dia_code) ctx->blk_info[1] = ctx->blk_info[5] = 0;
     hipStream_t st = ctx->stream;
     const int g = spmm_grid(ctx);
     *G = g;
@@ -927,6 +956,15 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
         EllAdjDev e;
         if (!ell_adj_args(ctx, e)) return fail(ctx, -12, kAdjFormMsg);
         hipLaunchKernelGGL(spmm_ell_t_kernel(kp, dots), dim3(g), dim3(kBlock), 0, st, a, e);
+        return 0;
+    }
+    if (const SpmmDiacFn coded = spmm_diac_for(ctx, kp, dots, a.trips)) {
+        DiaCodeDev C;
+        dia_code_args(ctx, C);
+        const size_t image = (size_t)C.doff[ctx->nd] * sizeof(double);
+        *G = launch_staged(ctx, kStagedDiac, kp, dots, a.trips, image, coded, a, C);
+        ctx->blk_info[1] = 9;
+        ctx->blk_info[5] = (int64_t)staged_lds(kStagedDiac, image, kp);
         return 0;
     }
     const SpmmFn kern = spmm_kernel(kp, spmm_fmt(ctx), dots, ctx->use_comm);

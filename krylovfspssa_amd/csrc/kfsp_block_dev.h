@@ -1,6 +1,6 @@
 // Private: what the translation units of the block product share - kfsp_block.hip (Y = A X and everything behind
-// the product), kfsp_block_adj.hip (Y = A^T X, option adjoint) and kfsp_block_boxg.hip (Y = A X on any matrix-free box,
-// option block_box = 2).  The row helpers, SpmmArgs and block_sum_cols are the ones kfsp_block.hip always had; the
+// the product), kfsp_block_adj.hip (Y = A^T X, option adjoint), kfsp_block_boxg.hip (Y = A X on any matrix-free box,
+// option block_box = 2) and kfsp_block_diac.hip (Y = A X from the coded banded image, option block_dia_code).  The row helpers, SpmmArgs and block_sum_cols are the ones kfsp_block.hip always had; the
 // descriptors at the end belong to the transposed product and to the generic matrix-free kernels.
 #pragma once
 
@@ -58,6 +58,29 @@ decltype(auto) dispatch_box_inst(int inst, F &&f)
     default: return f(integral_constant<int, 6>{}, integral_constant<int, 4>{});
     }
 }
+
+// f(bits per code, bytes per record) of the coded banded block product (k_spmm_diac, kfsp_block_diac.hip) for the four
+// forms dia_code_rule can choose.  Anything else reaches NO instantiation: the answer is a value-initialised result (a null
+// kernel pointer), and the caller keeps the plain kernel.
+template <class F>
+auto dispatch_diac(int w, int rec, F &&f) -> decltype(f(std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{}))
+{
+    using std::integral_constant;
+    using R = decltype(f(integral_constant<int, 8>{}, integral_constant<int, 8>{}));
+    if (w == 8 && rec == 8) return f(integral_constant<int, 8>{}, integral_constant<int, 8>{});
+    if (w == 8 && rec == 16) return f(integral_constant<int, 8>{}, integral_constant<int, 16>{});
+    if (w == 16 && rec == 8) return f(integral_constant<int, 16>{}, integral_constant<int, 8>{});
+    if (w == 16 && rec == 16) return f(integral_constant<int, 16>{}, integral_constant<int, 16>{});
+    return R{};
+}
+
+// Where code d of a row lies in its record (DiaCodeDev, kfsp_internal.h; coded_vals, kfsp_kernels.hip): a 64-bit record
+// word holds 64 / w codes of w bits, diagonal d in word d / (64 / w) at bit w (d mod 64 / w).  Plain code: the kernel
+// and tests/block_dia_code_check.cpp read the same lines.
+constexpr int diac_word(int w, int d) { return d / (64 / w); }
+constexpr int diac_shift(int w, int d) { return (d % (64 / w)) * w; }
+constexpr unsigned diac_mask(int w) { return (1u << w) - 1u; }
+constexpr unsigned diac_code(int w, unsigned long long word, int d) { return (unsigned)(word >> diac_shift(w, d)) & diac_mask(w); }
 
 #if defined(__HIPCC__)
 template <int KP>
@@ -257,7 +280,9 @@ typedef void (*SpmmFn)(SpmmArgs);
 typedef void (*SpmmEllTFn)(SpmmArgs, EllAdjDev);
 typedef void (*SpmmBoxTFn)(SpmmArgs, BoxAdjDev);
 typedef void (*SpmmBoxgFn)(BoxgArgs);
+typedef void (*SpmmDiacFn)(SpmmArgs, DiaCodeDev);
 #define KFSP_LOCAL __attribute__((visibility("hidden")))
+KFSP_LOCAL SpmmDiacFn spmm_diac_kernel(int kp, int w, int rec, bool dots);   // k_spmm_diac (kfsp_block_diac.hip); null: no such form
 KFSP_LOCAL SpmmFn spmm_t_kernel(int kp, bool dots);                    // k_spmm_t (kfsp_block_adj.hip)
 KFSP_LOCAL SpmmEllTFn spmm_ell_t_kernel(int kp, bool dots);            // k_spmm_ell_t
 KFSP_LOCAL SpmmBoxTFn spmm_box_t_kernel(int kp, int inst, bool dots);  // k_spmm_box_t
@@ -265,8 +290,8 @@ KFSP_LOCAL SpmmBoxgFn spmm_boxg_t_kernel(int kp, bool dots);           // k_spmm
 KFSP_LOCAL SpmmBoxgFn spmm_boxg_kernel(int kp, bool dots);             // k_spmm_boxg (kfsp_block_boxg.hip)
 #undef KFSP_LOCAL
 
-// the four kernel families that stage the table image of a matrix-free box into dynamic LDS: first index of the
-// occupancy cache (kfsp_ctx::blk_staged_occ)
-enum StagedFamily { kStagedBox = 0, kStagedBoxT = 1, kStagedBoxg = 2, kStagedBoxgT = 3 };
+// the kernel families that stage an image into dynamic LDS - the table image of a matrix-free box, or the dictionaries
+// of the coded banded form (option block_dia_code): first index of the occupancy cache (kfsp_ctx::blk_staged_occ)
+enum StagedFamily { kStagedBox = 0, kStagedBoxT = 1, kStagedBoxg = 2, kStagedBoxgT = 3, kStagedDiac = 4, kStagedFamilies = 5 };
 
 }  // namespace kfsp

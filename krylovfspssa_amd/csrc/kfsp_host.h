@@ -149,4 +149,27 @@ inline void generator_args(const kfsp_ctx *c, SellDev &A, DiaDev &D)
     D.zero = c->d_zero.p;
 }
 
+// ---- the dictionary-coded image of the banded values (kernel format 9), single vector and block alike
+// the product may read it: banded, stored, the image resident for d_dia, unmasked, single rank
+inline bool dia_code_on(const kfsp_ctx *c) { return c->use_dia && !c->use_box && c->dia_coded && !c->dia_masked && !c->use_comm; }
+
+inline void dia_code_args(const kfsp_ctx *c, DiaCodeDev &C)
+{
+    C.rec = c->d_dcode.p;
+    C.dict = c->d_ddict.p;
+    for (int d = 0; d <= kMaxDiag; ++d) C.doff[d] = c->dia_doff[d];
+    C.w = c->dia_code_w;
+    C.rec_bytes = c->dia_code_rec;
+}
+
+// Option block_dia_code: the forward block product takes the coded image (k_spmm_diac, kfsp_block_diac.hip) where the
+// single-vector product takes it (coded_on = dia_code_on), the option is on, the product is not the transposed one
+// (row r of A^T needs code d of row r - delta_d: nd record loads) and the pass is not the one-launch small one (its
+// product is compiled into k_barnoldi_small).  Everything else keeps the kernel it had.  Plain flags, so that a
+// stand-alone program can walk all combinations (tests/block_dia_code_check.cpp).
+inline bool block_dia_code_path(bool coded_on, int64_t opt_block_dia_code, bool adjoint, bool small)
+{
+    return coded_on && opt_block_dia_code != 0 && !adjoint && !small;
+}
+
 }  // namespace kfsp

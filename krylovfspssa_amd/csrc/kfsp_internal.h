@@ -91,8 +91,10 @@ struct DiaDev {
 // codes.  The kernel keeps every dictionary in LDS and computes with dict[d][code]: the very doubles of the plain
 // streams, the same multiply-adds in the same order, bit-identical products.  DIAG stays an 8-byte stream (it has
 // about as many distinct values as rows).  One code width per matrix, chosen by dia_code_rule; a matrix that does not
-// fit keeps the plain kernel.  The plain streams stay resident (block products, masked / halo / partitioned forms,
-// kfsp_get_matrix read them): the coded image costs 8 or 16 B per row on top.
+// fit keeps the plain kernel.  The plain streams stay resident (the transposed and the small-pass block products, every
+// block product without option block_dia_code, masked / halo / partitioned forms and kfsp_get_matrix read them): the
+// coded image costs 8 or 16 B per row on top.  The forward block product reads the coded image under option
+// block_dia_code (k_spmm_diac, kfsp_block_diac.hip).
 constexpr int kDiaCodeLds = 40 * 1024;        // LDS bytes all dictionaries together may take: 4 workgroups per CU stay resident
 struct DiaCodeDev {
     const unsigned long long *rec;   // [ld] records of rec_bytes each

@@ -763,7 +763,10 @@ class KfspContext:
         matrix-free box under set_option("block_box", 1), and on a multi-factor one (or any box under "box_generic" = 1)
         under set_option("block_box", 2).  adjoint=True: A^T X (option "adjoint" round the call).
         On a rank of a row partition X is the whole block (n rows) and the rank's nloc rows of A X come back, as in spmv.
-        While a target set is resident: D A D X (D A^T D X), the product with the killed generator - +0.0 on the set."""
+        While a target set is resident: D A D X (D A^T D X), the product with the killed generator - +0.0 on the set.
+        Under set_option("block_dia_code", 1) the forward product of a banded generator with a coded image
+        (dia_code_info()["active"]) reads one record per row and the dictionaries in LDS instead of the value streams: the
+        same bits; block_info() tells which kernel ran."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
         self._with_block_options(lambda: self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm"),
@@ -837,7 +840,9 @@ class KfspContext:
         return ws[:k].copy()
 
     def block_info(self):
-        """how the last block calls ran (kfsp_block_info)"""
+        """how the last block calls ran (kfsp_block_info).  While option "block_dia_code" is on, every block product writes
+        "fmt" and "lds_bytes": 9 and the dynamic LDS of the launch (the dictionaries) when the coded kernel ran, else 0 and 0.
+        With the option off the two slots are what they always were (the one-launch small pass fills them)."""
         v = np.zeros(8, dtype=np.int64)
         self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info")
         return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes", "adjoint", "exchange"),
@@ -890,7 +895,9 @@ class KfspContext:
 
     def set_option(self, name, value):
         """kfsp_set_option (include/kfsp.h lists the names), e.g. "block_box" = 1: the block calls take a matrix-free single-factor box;
-        2: every matrix-free box (0 and 1 keep their meaning: a multi-factor box is still refused under 1)."""
+        2: every matrix-free box (0 and 1 keep their meaning: a multi-factor box is still refused under 1).
+        "block_dia_code" = 1 (default 0, read at every block call): the forward block product reads the dictionary-coded image
+        of a banded generator where the single-vector product does (option "dia_code"); every other case keeps its kernel."""
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
         if not hasattr(self, "_options"):
             self._options = {}
