@@ -208,14 +208,17 @@ int kfsp_dia_code_rule(int32_t nd, const int64_t *distinct, int64_t lds_bytes, i
  *   state orders before them) repeated the slow way because a check at the end failed - a coordinate range crossed a power of
  *   two, or the slow path would have stored diagonals, v[2] the last generator built from resident arrays is a SELL one,
  *   v[3] a key layout is cached for the next state order, v[4] state orders made FROM the previous one - the appended states'
- *   keys sorted and merged into the kept list, or the list compacted after a drop - instead of sorting every key, v[5] 0.
+ *   keys sorted and merged into the kept list, or the list compacted after a drop - instead of sorting every key, v[5] the length of the base-trip order the
+ *   pencil kernel (format 7) is given for the current matrix-free box - its number of base trips when option "box_tile" put the tiled
+ *   order in effect, 0 when the trips are taken ascending or the generator is no pencil-eligible box.
  *   A group context answers for its first rank. */
 int kfsp_build_info(const kfsp_ctx *ctx, int64_t *v);
 /* The ORDER in which a product takes its wavefront trips (one trip = 128 consecutive rows of a banded or matrix-free
  * generator, 64 of a SELL one; ntrips = ceil(local rows / that)): position t of the sweep computes trip order[t].  Rows
  * are independent (FMATVEC as a row gather), so y does not depend on the order - bits included; what changes is which rows
- * of x are in an XCD's L2 when their far neighbours are computed.  kfsp_set_matrix_box chooses a tiled order itself for
- * boxes with strides beyond the L2 (option "box_tile"); this entry point is for experiments.  Belongs to the current
+ * of x are in an XCD's L2 when their far neighbours are computed.  kfsp_set_matrix_box chooses no such order: its format 4 and
+ * stored products are ascending unless this call says otherwise (the one order the library picks itself is that of the pencil
+ * kernel's base trips, option "box_tile", which this call does not touch); this entry point is for experiments.  Belongs to the current
  * generator (the next kfsp_set_matrix_* drops it); ntrips = 0 restores the ascending order.  Single rank, whole-product
  * launches. */
 int kfsp_set_trip_order(kfsp_ctx *ctx, int64_t ntrips, const int32_t *order);
@@ -815,9 +818,11 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * coordinates is worked out once per pencil; kernel format 7, products bit-identical to format 4; 0: never; 1: also on small boxes; 2: pencils in SLABS, format 8 - a workgroup's
  * wavefronts walk the lines of the second-slowest species in step and exchange their pairs through LDS: less traffic, bit-identical, but
  * measured slower than format 7 - one workgroup barrier per step at 11 wavefronts per CU - and therefore never chosen automatically; "box_slab_waves" = most lines a workgroup takes, default and maximum 12), "box_tile" (the order in which
- * products over a box take their 128-row trips: -1, default: tiled - blocks of 1024 rows below a stride of at most 16 K rows, per
- * block every slower line back to back - when neither the vector nor the windows of its far strides fit the 256 MiB Infinity
- * Cache (22^6: 14 % faster), ascending otherwise; 0 always ascending; 1 always tiled; same bits either way), "box_generic" (1: matrix-free boxes take
+ * the pencil kernel, format 7, takes its base trips - the 128-row trips of one plane of the slowest species; nothing else reads it: format 4,
+ * the slabs and a stored box take their trips ascending, or in the order of kfsp_set_trip_order.  -1, default: tiled - blocks of 1024 rows
+ * below a stride of at most 16 K rows, per block every slower line of the plane back to back - when a plane is larger than 4 MiB,
+ * ascending otherwise; 0 always ascending; 1 tiled wherever the rule has an order to give: at least three species below the slowest
+ * and a cut stride of at least 2048 rows, else ascending; kfsp_build_info v[5] tells; same bits either way), "box_generic" (1: matrix-free boxes take
  * the run-time interpreted kernel even when the single-factor fast path applies), "state_order" (1: use
  * kfsp_set_state_coords, the default; 0: never), "state_order_min" (smallest generator that is
  * reordered, default 32768), "state_order_products" (products the previous

@@ -488,43 +488,6 @@ int init_context(kfsp_ctx *ctx)
     return 0;
 }
 
-// The order in which a product over a lexicographic box takes its 128-row trips when the box is too large for the caches
-// (option "box_tile": -1 auto, 0 never, 1 always): rows are cut below the slowest stride that is still at most 16 K rows
-// (cut), r = hi * S_cut + lo; blocks of B = 1024 rows of lo; per block ALL lines hi back to back.  A row's +-S neighbours
-// for the strides above the cut are then whole lines away - one line = B rows = 8 KB of x - instead of whole strides:
-// 22^6 with the cut below species 4: the +-22^3 / 22^4 / 22^5 neighbours sit 1 / 22 / 484 lines = 8 KB / 180 KB / 4 MB
-// from the row in the order of the sweep.  Empty: keep the ascending order.
-std::vector<int32_t> box_tile_order(int ns, const int32_t *dims, int64_t n, bool force)
-{
-    std::vector<int32_t> out;
-    const int64_t trips = (n + 127) / 128;
-    if (ns < 3 || trips < 2 || trips > INT32_MAX) return out;
-    int64_t stride = 1, smax = 1;
-    int cut = -1;
-    int64_t scut = 1;
-    for (int s = 0; s < ns; ++s) {
-        if (stride <= 16384 && s > 0) {
-            cut = s;
-            scut = stride;
-        }
-        smax = stride;
-        stride *= dims[s];
-    }
-    const double mall = 256.0 * 1024 * 1024;
-    const bool large = (double)n * 8.0 > mall && 8.0 * 2.0 * (double)smax * 8.0 > mall;
-    if (cut < 1 || scut < 2048 || !(force || large)) return out;
-    const int64_t B = 1024, nhi = (n + scut - 1) / scut;
-    std::vector<std::pair<int64_t, int32_t>> key((size_t)trips);
-    for (int64_t c = 0; c < trips; ++c) {
-        const int64_t r = c * 128, lo = r % scut, hi = r / scut;
-        key[(size_t)c] = {((lo / B) * nhi + hi) * scut + lo, (int32_t)c};
-    }
-    std::sort(key.begin(), key.end());
-    out.resize((size_t)trips);
-    for (int64_t c = 0; c < trips; ++c) out[(size_t)c] = key[(size_t)c].second;
-    return out;
-}
-
 }  // namespace
 
 extern "C" {
@@ -960,6 +923,7 @@ int kfsp_set_matrix_box(kfsp_ctx *ctx, int32_t ns, const int32_t *dims, int32_t 
         // species' own entries reach exactly one plane (or are unused slots), no other entry moves the slowest species, planes
         // have an even number of rows (16-byte pairs), one rank, and there are enough base trips to fill the chip.
         ctx->box_pencil = false;
+        ctx->box_slab = false;                  // (a box that is not eligible must not keep the slabs of the one before it)
         ctx->pencil_order_n = 0;
         if (fast && ns >= 3 && ns == ns_inst && ctx->nranks == 1 && !ctx->use_comm) {
             const int Ls = ns - 1;
@@ -975,7 +939,6 @@ int kfsp_set_matrix_box(kfsp_ctx *ctx, int32_t ns, const int32_t *dims, int32_t 
             ctx->pencil_simple = simple;
             // Format 8 (slabs): additionally the lines of the second-slowest species have an even number of rows, there are at
             // least two of them, and at least 256 workgroups' worth of slabs (or the option insists)
-            ctx->box_slab = false;
             if (ok && ns >= 3) {
                 int64_t line = 1;
                 for (int s = 0; s < Ls - 1; ++s) line *= dims[s];
@@ -997,8 +960,10 @@ int kfsp_set_matrix_box(kfsp_ctx *ctx, int32_t ns, const int32_t *dims, int32_t 
                 ctx->pencil_plane_rows = plane;
                 ctx->pencil_planes = dims[Ls];
                 ctx->pencil_trips = (plane + 127) / 128;
-                // the base trips in small tiles of the plane (the same rule as box_tile_order, one species fewer)
-                const std::vector<int32_t> po = box_tile_order(Ls, dims, plane, plane * 8 > (int64_t)(4 << 20));
+                // the base trips in small tiles of the plane (box_tile_order on the plane's species; option "box_tile": 0 never,
+                // 1 wherever there is such an order, -1 a plane beyond 4 MiB)
+                std::vector<int32_t> po;
+                if (kfsp::box_tile_wanted(ctx->opt_box_tile)) po = kfsp::box_tile_order(Ls, dims, plane, kfsp::box_tile_force(ctx->opt_box_tile, plane));
                 if (!po.empty()) {
                     HIP_TRY(ctx->d_pencil_order.reserve(po.size(), false));
                     HIP_TRY(hipMemcpy(ctx->d_pencil_order.p, po.data(), po.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1214,7 +1179,7 @@ int kfsp_build_info(const kfsp_ctx *ctx, int64_t *v)
     v[2] = ctx->last_build_sell ? 1 : 0;
     v[3] = ctx->kc_ok ? 1 : 0;
     v[4] = ctx->order_merges;
-    v[5] = 0;
+    v[5] = (ctx->use_box && ctx->box_pencil && ctx->pencil_order_n == ctx->pencil_trips) ? ctx->pencil_order_n : 0;
     return 0;
 }
 

@@ -133,6 +133,50 @@ inline int vec_grid(int64_t pairs, int64_t opt_vgrid)
     return (int)std::max<int64_t>(std::min<int64_t>(g, std::min<int64_t>(opt_vgrid > 0 ? opt_vgrid : 1024, kMaxGrid)), 1);
 }
 
+// A tiled order of the 128-row trips over a lexicographic box of n rows (ns species, dims fastest first): rows are cut
+// below the slowest stride that is still at most 16 K rows (cut), r = hi * S_cut + lo; blocks of B = 1024 rows of lo; per
+// block ALL lines hi back to back.  A row's +-S neighbours for the strides above the cut are then whole lines away - one
+// line = B rows = 8 KB of x - instead of whole strides: 22^6 with the cut below species 4: the +-22^3 / 22^4 / 22^5
+// neighbours sit 1 / 22 / 484 lines = 8 KB / 180 KB / 4 MB from the row in the order of the sweep.  Empty: keep the
+// ascending order - fewer than three species, a cut stride under 2048 rows, or neither `force` nor a box beyond the
+// caches.  Its one caller is the base-trip order of the pencil kernel (format 7, kfsp_set_matrix_box: the box is a plane,
+// `force` comes from option "box_tile"); tests/box_tile_order_check.cpp calls it without a device.
+inline std::vector<int32_t> box_tile_order(int ns, const int32_t *dims, int64_t n, bool force)
+{
+    std::vector<int32_t> out;
+    const int64_t trips = (n + 127) / 128;
+    if (ns < 3 || trips < 2 || trips > INT32_MAX) return out;
+    int64_t stride = 1, smax = 1;
+    int cut = -1;
+    int64_t scut = 1;
+    for (int s = 0; s < ns; ++s) {
+        if (stride <= 16384 && s > 0) {
+            cut = s;
+            scut = stride;
+        }
+        smax = stride;
+        stride *= dims[s];
+    }
+    const double mall = 256.0 * 1024 * 1024;
+    const bool large = (double)n * 8.0 > mall && 8.0 * 2.0 * (double)smax * 8.0 > mall;
+    if (cut < 1 || scut < 2048 || !(force || large)) return out;
+    const int64_t B = 1024, nhi = (n + scut - 1) / scut;
+    std::vector<std::pair<int64_t, int32_t>> key((size_t)trips);
+    for (int64_t c = 0; c < trips; ++c) {
+        const int64_t r = c * 128, lo = r % scut, hi = r / scut;
+        key[(size_t)c] = {((lo / B) * nhi + hi) * scut + lo, (int32_t)c};
+    }
+    std::sort(key.begin(), key.end());
+    out.resize((size_t)trips);
+    for (int64_t c = 0; c < trips; ++c) out[(size_t)c] = key[(size_t)c].second;
+    return out;
+}
+
+// option "box_tile" -> the `force` of the pencil kernel's base-trip order: -1 a plane beyond 4 MiB, 0 never (no order at
+// all, whatever the size), 1 wherever box_tile_order has one to give
+inline bool box_tile_wanted(int64_t tile) { return tile != 0; }
+inline bool box_tile_force(int64_t tile, int64_t plane_rows) { return tile > 0 || (tile < 0 && plane_rows * 8 > (int64_t)(4 << 20)); }
+
 // the generator's stored images as the kernels take them
 inline void generator_args(const kfsp_ctx *c, SellDev &A, DiaDev &D)
 {

@@ -1428,12 +1428,15 @@ __global__ __launch_bounds__(768) void k_spmv_slab(SpmvArgs a, int64_t plane_row
     box_pair_t *xchg = reinterpret_cast<box_pair_t *>(box_lds + ((a.B.ntab + 1) & ~1));
     double s = 1.0;
     if (MODE != 0) {
-        // (finish_sum for a workgroup of W wavefronts: the first four sum the partials exactly as the 256-thread kernels do)
-        double t = 0.0;
-        if (threadIdx.x < kBlock)
-            for (int i = threadIdx.x; i < a.sq.n; i += kBlock) t += a.sq.p[i];
-        t = wave_allreduce_sum(t);
-        if (lane == 0 && wave < 4) red[wave] = t;
+        // (finish_sum for a workgroup of W wavefronts, W = 1 .. 12: the four wavefront sums of a 256-thread kernel - lane l of
+        // wavefront v adds the partials 64 v + l, + 256, ... - are taken by wavefront v where W >= 4 and shared out over the
+        // W wavefronts there are where W < 4; the same additions per lane, the same pairing of the four sums)
+        for (int v = wave; v < kBlock / 64; v += W) {
+            double t = 0.0;
+            for (int i = 64 * v + lane; i < a.sq.n; i += kBlock) t += a.sq.p[i];
+            t = wave_allreduce_sum(t);
+            if (lane == 0) red[v] = t;
+        }
         __syncthreads();
         const double S = (red[0] + red[1]) + (red[2] + red[3]);
         __syncthreads();

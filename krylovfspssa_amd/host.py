@@ -567,10 +567,11 @@ class KfspContext:
         return out
 
     def build_info(self):
-        """how the rebuilds of a resident FSP went (kfsp_build_info)"""
+        """how the rebuilds of a resident FSP went, and "pencil_order": the length of the tiled base-trip order the pencil
+        kernel (format 7) is given for the current box (option box_tile), 0 when it takes them ascending (kfsp_build_info)"""
         v = np.zeros(6, dtype=np.int64)
         self._chk(self._lib.kfsp_build_info(self._h, _p(v)), "kfsp_build_info")
-        return dict(zip(("speculative", "repeated", "sell", "key_layout_cached", "orders_carried_over"), (int(x) for x in v)))
+        return dict(zip(("speculative", "repeated", "sell", "key_layout_cached", "orders_carried_over", "pencil_order"), (int(x) for x in v)))
 
     def set_vector(self, w):
         w = np.ascontiguousarray(w, dtype=np.float64)

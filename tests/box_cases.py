@@ -66,6 +66,44 @@ def _four_slot(dims):
     return _synth().BoxModel("four_slot", dims, m.stoich, m.prop, deps=m.deps)
 
 
+def six_species_four_slot(dims):
+    """six species, the first with the four reactions of the four-slot box (nu = +-1, +-2), the others born and dying:
+    the <6,4> instantiation on a box whose species are the instantiation's, which the pencil kernels therefore take"""
+    d = len(dims)
+    assert d == 6
+    st = np.zeros((d, 4 + 2 * (d - 1)), dtype=np.int64)
+    st[0, :4] = (1, -1, 2, -2)
+    for i in range(1, d):
+        st[i, 2 + 2 * i], st[i, 3 + 2 * i] = 1, -1
+
+    def prop(r, X):
+        if r < 4:
+            x = X[0]
+            return (np.full_like(x, 5.0), 0.7 * x, 1.5 + 0.01 * x, 0.02 * x * (x - 1.0))[r]
+        i = (r - 2) // 2
+        return np.full_like(X[i], 2.0 + 0.5 * i) if r % 2 == 0 else (0.4 + 0.1 * i) * X[i]
+    return _synth().BoxModel("six_four_slot", dims, st, prop, deps=[(0,)] * 4 + [((r - 2) // 2,) for r in range(4, st.shape[1])])
+
+
+def conversion_box(dims):
+    """six species born and dying, and a conversion of the first into the last: an entry of species 0 (its propensity
+    depends on species 0 alone) that moves the slowest species - the pencil kernels then mask that entry plane by plane
+    with the slowest species' valid bit (their SIMPLE = false instantiation); three slots in species 0: <6,4>"""
+    d = len(dims)
+    assert d == 6
+    st = np.zeros((d, 2 * d + 1), dtype=np.int64)
+    for i in range(d):
+        st[i, 2 * i], st[i, 2 * i + 1] = 1, -1
+    st[0, 2 * d], st[d - 1, 2 * d] = -1, 1
+
+    def prop(r, X):
+        if r == 2 * d:
+            return 0.3 * X[0]
+        i = r // 2
+        return np.full_like(X[i], 3.0 + 0.25 * i) if r % 2 == 0 else (0.5 + 0.1 * i) * X[i]
+    return _synth().BoxModel("conversion", dims, st, prop, deps=[(r // 2,) for r in range(2 * d)] + [(0,)])
+
+
 @functools.lru_cache(maxsize=None)
 def _random_two_factor():
     """name -> model: _random_box's own sequence from a fixed seed, the two-factor models (k % 3 == 2) of a usable size"""
@@ -91,6 +129,25 @@ LOOP = {
     "loop_birth_death_4x4x4x4x4x5": lambda: _synth().birth_death((4, 4, 4, 4, 4, 5)),
     "loop_four_slot_75x60": lambda: _four_slot((75, 60)),
 }
+# Boxes for the size-gated variants of the pencil kernels (tests/test_gpu_box_slab_waves.py), instance <6,2> unless named
+# otherwise, all with lines of an even number of rows.  slab_*: format 8 with fewer wavefronts than the four a 256-thread
+# workgroup has (lines = dims[-2] = 2 or 3), lines of 3000 rows (a last trip with dead lanes) and the 22-line box of
+# tests/test_gpu_box.py.  tile_*: planes on which box_tile_order has a tiled base-trip order to give (a cut stride of at
+# least 2048 rows); two of them are slab boxes as well.
+SLAB = {
+    "slab_8x8x8x8x2x2": lambda: _synth().birth_death((8, 8, 8, 8, 2, 2)),
+    "slab_8x8x8x4x3x2": lambda: _synth().birth_death((8, 8, 8, 4, 3, 2)),
+    "slab_10x10x6x5x2x2": lambda: _synth().birth_death((10, 10, 6, 5, 2, 2)),
+    "slab_6x4x3x2x22x3": lambda: _synth().birth_death((6, 4, 3, 2, 22, 3)),
+}
+TILE = {
+    "tile_6x8x8x8x3x2": lambda: _synth().birth_death((6, 8, 8, 8, 3, 2)),
+    "tile_four_slot_8x8x8x4x2x2": lambda: six_species_four_slot((8, 8, 8, 4, 2, 2)),
+    "tile_small_8x8x8x4x2x2": lambda: _synth().birth_death((8, 8, 8, 4, 2, 2)),
+    "tile_conversion_8x8x8x4x2x3": lambda: conversion_box((8, 8, 8, 4, 2, 3)),
+}
+TILED = ("slab_8x8x8x8x2x2", "slab_10x10x6x5x2x2", "tile_6x8x8x8x3x2")          # the three boxes of the order tests
+SLAB_WAVES = (1, 2, 3, 5, 12)
 SMALL = tuple(AC.BOXES) + tuple(DECODE) + ("dup_12x9",)
 FAST = SMALL + tuple(LOOP)
 NAMED_GENERIC = ("goutsias", "three_factor")
@@ -120,6 +177,10 @@ def model(name):
         return LOOP[name]()
     if name == "dup_12x9":
         return dup_box()
+    if name in SLAB:
+        return SLAB[name]()
+    if name in TILE:
+        return TILE[name]()
     if name == "goutsias":
         return _synth().goutsias_box((5, 4, 3, 3, 2, 2))
     if name == "three_factor":
@@ -158,6 +219,38 @@ def pencil_format(mdl, pencil):
     return 8 if pencil == 2 and line % 2 == 0 and mdl.dims[-2] >= 2 else 7
 
 
+def slab_geometry(dims, slab_waves=12):
+    """(lines, groups, waves, lo_trips) of format 8, the rule of kfsp_set_matrix_box restated: the lines of the
+    second-slowest species are shared out over the fewest workgroups of at most min(12, box_slab_waves) wavefronts, and
+    evenly over those; a workgroup takes 128 rows of each of its lines"""
+    line, lines = int(np.prod(dims[:-2])), int(dims[-2])
+    wmax = max(1, min(12, slab_waves))
+    groups = -(-lines // wmax)
+    waves = -(-lines // groups)
+    return lines, groups, waves, -(-line // 128)
+
+
+def vec_grid(n, vec_grid_blocks=0):
+    """workgroups - partial sums - of the streaming kernels over n rows (kfsp_host.h, vec_grid, restated): the rows padded
+    to 64-row chunks, two to a pair, 1024 pairs per workgroup, at most 1024 workgroups (or the option) and the 2048 slots"""
+    pairs = -(-n // 64) * 32
+    return max(1, min(-(-pairs // 1024), vec_grid_blocks if vec_grid_blocks > 0 else 1024, 2048))
+
+
+def tile_order(dims):
+    """box_tile_order(force) of kfsp_host.h restated for the species `dims` of a plane (fastest first): () where it gives
+    no order, else the base trips sorted by (1024-row block of the row below the cut, line above the cut, row below the
+    cut), the cut being the slowest stride of a species but the first that is at most 16384 rows"""
+    n = int(np.prod(dims))
+    trips = -(-n // 128)
+    strides = [int(np.prod(dims[:s])) for s in range(len(dims))]
+    cuts = [st for s, st in enumerate(strides) if s > 0 and st <= 16384]
+    if len(dims) < 3 or trips < 2 or not cuts or cuts[-1] < 2048:
+        return ()
+    scut = cuts[-1]
+    return tuple(sorted(range(trips), key=lambda c: ((128 * c % scut) // 1024, 128 * c // scut, 128 * c % scut)))
+
+
 def decode_corrections(mdl, row0=0, nloc=None):
     """(rows whose coordinate decode takes the r >= d step, rows that take the r < 0 step) with the kernel's own formula:
     t = (uint32)((double) q * (1.0 / d)), r = q - t d, per species but the last"""
@@ -192,6 +285,18 @@ def case(name):
     for v in out.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def gated_case(name):
+    """a SLAB / TILE box -> dict(mdl, n, x, y: box_exact); computed once (about a second per 10 000 rows), left alone.
+    (These boxes stay out of FAST: the CPU tests over FAST restate every box row by row in both forms.)"""
+    mdl = model(name)
+    x = vector(mdl.n, 700 + (tuple(SLAB) + tuple(TILE)).index(name))
+    out = dict(mdl=mdl, n=mdl.n, x=x, y=np.array(RR.box_exact(mdl, x)))
+    out["x"].setflags(write=False)
+    out["y"].setflags(write=False)
     return out
 
 

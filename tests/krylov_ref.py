@@ -281,6 +281,12 @@ GENERAL_N = (2, 3, 63, 64, 65, 129, 513, 2047, 2049, 4095, 4096, 4097, 8193)
 BANDED_N = (131, 4095, 4097)
 BOXES = ("toggle", "repressilator", "birth_death6")
 BOX_DIMS = {"toggle": (33, 27), "repressilator": (31, 24, 19), "birth_death6": (5, 6, 4, 5, 4, 7)}
+# boxes for the fused modes of the slab kernel (format 8: lines of an even number of rows; BOX_DIMS' repressilator has
+# lines of 31) and of the pencil kernel under a tiled base-trip order; (kind, dims).  slab_narrow: 3 lines, so a workgroup
+# has at most 3 wavefronts - fewer than the four of the kernels whose sum of the incoming partials it must repeat;
+# slab_large: 196 608 rows, whose streaming kernels hand on MORE partials than a wavefront has lanes (box_cases.vec_grid)
+GATED_BOXES = {"repressilator_even": ("repressilator", (30, 23, 19)), "slab_narrow": ("birth_death", (8, 8, 8, 4, 3, 2)),
+               "slab_large": ("birth_death", (16, 16, 16, 8, 3, 2)), "tile_order": ("birth_death", (8, 8, 8, 8, 2, 2))}
 COMBINE_MX = (1, 2, 3, 4, 5, 7, 8, M_LONG + 1)
 _cache = {}
 
@@ -385,6 +391,9 @@ def banded_case(n, levels=0):
 
 def box_model(name):
     from krylovfspssa_amd import synth
+    if name in GATED_BOXES:
+        kind, dims = GATED_BOXES[name]
+        return synth.repressilator(dims=dims) if kind == "repressilator" else synth.birth_death(dims)
     dims = BOX_DIMS[name]
     return {"toggle": lambda: synth.toggle(*dims), "repressilator": lambda: synth.repressilator(dims=dims),
             "birth_death6": lambda: synth.birth_death(dims)}[name]()

@@ -99,13 +99,18 @@ def golden_case(fixture="assembly_goutsias_k10.npz"):
 CSR = ("random banded 0", "random banded 1", "random banded 3", "toggle 70x61")
 
 
+# a banded generator whose two row blocks each keep 64 trips clear of the halo strips: under option overlap = 2 a rank's
+# product is launched in two parts, interior and boundary (tests/test_gpu_nt_loads.py)
+CSR_SPLIT = "toggle 150x120"
+
+
 @functools.lru_cache(maxsize=None)
 def csr_case(name):
     if name.startswith("random banded"):
         n, rowptr, col, val, rng = _random_banded_csr(int(name.split()[-1]))
     else:
         from krylovfspssa_amd import synth
-        mdl = synth.toggle(70, 61)
+        mdl = synth.toggle(*map(int, name.split()[-1].split("x")))
         n = mdl.n
         rowptr, col, val = mdl.csr_rows()
         rng = np.random.default_rng(29)

@@ -288,13 +288,15 @@ def test_stored_formats(golden_dir, i):
 BOX_FORMS = [("toggle", {"box_generic": 1}, 3), ("toggle", {}, 4), ("toggle", {"box_lds": 1}, 6),
              ("repressilator", {"box_generic": 1}, 3), ("repressilator", {"box_pencil": 0}, 4), ("repressilator", {"box_lds": 1}, 6),
              ("repressilator", {"box_pencil": 1}, 7),
-             ("birth_death6", {"box_generic": 1}, 3), ("birth_death6", {"box_pencil": 0}, 4), ("birth_death6", {"box_pencil": 1}, 7)]
+             ("birth_death6", {"box_generic": 1}, 3), ("birth_death6", {"box_pencil": 0}, 4), ("birth_death6", {"box_pencil": 1}, 7),
+             # slabs: BOX_DIMS' repressilator has lines of 31 rows, an odd number; its sibling has lines of 30
+             ("repressilator_even", {"box_pencil": 2}, 8), ("birth_death6", {"box_pencil": 2}, 8)]
 
 
 @pytest.mark.parametrize("name,opts,fmt", BOX_FORMS, ids=[f"{n}-fmt{f}" for n, _, f in BOX_FORMS])
 def test_matrix_free_boxes(name, opts, fmt):
-    """the interpreted form (3), the single-factor form (4), its LDS window (6) and pencils (7); the rows of the
-    restatement are the model's own uploaded arrays"""
+    """the interpreted form (3), the single-factor form (4), its LDS window (6), pencils (7) and slabs (8); the rows of
+    the restatement are the model's own uploaded arrays"""
     case = K.box_case(name)
     with _ctx(opts) as c:
         case.upload(c)
