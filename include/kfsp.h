@@ -163,7 +163,8 @@ int kfsp_set_matrix_csr(kfsp_ctx *ctx, int64_t n, int64_t row0, int64_t nrows,
  *   tables       the factors, concatenated reaction by reaction, factor by factor; factor (k, i) has
  *                dims[dep_species[k][i]] entries (a constant propensity is one table of equal entries)
  * Works with a communicator like a banded generator (halo strips).  ns <= 8, nr <= 16, every reaction
- * changes <= 3 species, all tables together <= 6000 entries.
+ * changes <= 3 species, all tables together <= 6000 entries.  A call refused for its arguments (a negative status)
+ * leaves the context and its resident generator untouched.
  * Option "box_store" = 1: the same call WRITES THE GENERATOR OUT on the device as stored diagonals (the banded
  * form kfsp_set_matrix_csr would build from the gather rows of this box - with one factor per propensity the
  * very same entries) - a stored generator of any size without host arrays of that size. */

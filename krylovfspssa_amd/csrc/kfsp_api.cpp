@@ -48,10 +48,10 @@ void set_matrix_args(const kfsp_ctx *c, SpmvArgs &a)
 {
     generator_args(c, a.A, a.D);
     dia_code_args(c, a.C);
-    if (c->use_box) a.B = c->box;
+    if (c->box.on) a.B = c->box.dev;
     else a.B.ns = a.B.nr = a.B.ntab = 0;
     a.box_tab = c->d_box.p;
-    a.box_fast = reinterpret_cast<const BoxFast *>(c->d_box.p + (c->box_lds_bytes / sizeof(double)));
+    a.box_fast = reinterpret_cast<const BoxFast *>(c->d_box.p + (c->box.lds_bytes / sizeof(double)));
     a.udot2 = nullptr;
     a.partial2 = nullptr;
     a.trip_order = nullptr;
@@ -88,20 +88,20 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     const bool nt = use_nt(ctx);
     const int64_t trips = product_trips(ctx->nchunks, dia);
     int64_t dflt_cap = 1024;   // the grid without option grid_blocks (product_grid)
-    if (ctx->use_box && dia) {
+    if (ctx->box.on && dia) {
         // every workgroup of a matrix-free product copies the table image into its LDS first: no more
         // workgroups than are resident at once (160 KB of LDS per CU), or the later ones pay that copy
         // again for fewer rows each (toggle 1000 x 1000, 64 KB image: 8.3 us with 512, 12.1 us with 1024)
-        const int64_t per_cu = std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)(ctx->box_lds_bytes + 512));
+        const int64_t per_cu = std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)(ctx->box.lds_bytes + 512));
         dflt_cap = std::min<int64_t>(dflt_cap, 256 * per_cu);
     }
     double *P1 = mode != 0 ? next_partial(ctx) : nullptr;
     double *P2 = mode == 3 ? next_partial(ctx) : nullptr;
     a.row0 = ctx->row0;
-
-    const int fmt = (ctx->use_box && dia) ? (ctx->box_fast && !ctx->opt_box_generic ? 4 : 3)
-                                          : (dia ? (dia_code_on(ctx) ? 9 : (ctx->dia_masked ? 2 : 1))
-                                                 : (ctx->sell_coded && !force_plain_sell ? 5 : 0));
+    // the kernel format: product_format (kfsp_host.h); under a communicator - every split product - one of 0 - 5 and 9
+    const bool ordered = ctx->trip_order_n == trips && !force_sell;
+    const int fmt = product_format(product_form(ctx, ordered, force_sell, force_plain_sell));
+    const kfsp::BoxGeom &bx = ctx->box;
     const int64_t H = ctx->halo, L = ctx->L;
     const int64_t trip_rows = dia ? 128 : 64;
     // interior trips [lo, hi) read no halo row; whether launching them on their own pays: product_split (kfsp_host.h)
@@ -119,39 +119,33 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         a.trip_end = trips;
         a.trip_split = INT64_MAX;
         a.trip_jump = 0;
-        a.trip_order = (ctx->trip_order_n == trips && !force_sell) ? ctx->d_trip_order.p : nullptr;
-        const int g = product_grid(trips, ctx->opt_grid, dflt_cap);
-        if (fmt == 4 && ctx->box_slab && ctx->opt_box_pencil == 2 && !ctx->use_comm && ctx->opt_box_lds == 0) {
-            // format 8: one workgroup per 128 rows x W lines of the second-slowest species, walking the planes in step
-            const int64_t total = ctx->slab_lo_trips * ctx->slab_groups;
-            const size_t lds = ((ctx->box_lds_bytes + 15) & ~(size_t)15) + 2 * (size_t)ctx->slab_waves * 1024;
+        a.trip_order = ordered ? ctx->d_trip_order.p : nullptr;
+        int g = product_grid(trips, ctx->opt_grid, dflt_cap);
+        switch (fmt) {
+        case 8: {
+            // one workgroup per 128 rows x W lines of the second-slowest species, walking the planes in step
+            const int64_t total = bx.lo_trips * bx.groups;
+            const size_t lds = ((bx.lds_bytes + 15) & ~(size_t)15) + 2 * (size_t)bx.waves * 1024;
             // (workgroups of up to 1024 threads: as many as are resident at once, they loop over the slabs)
-            const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(12 / ctx->slab_waves, (int64_t)(160 * 1024) / (int64_t)(lds + 1024)));
+            const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(12 / bx.waves, (int64_t)(160 * 1024) / (int64_t)(lds + 1024)));
             const int64_t want = ctx->opt_grid > 0 ? ctx->opt_grid : 256 * per_cu;
-            const int gs = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(total, want), kMaxGrid));
-            launch_spmv_slab(mode, gs, ctx->slab_waves, a, st, lds, ctx->pencil_plane_rows, ctx->pencil_planes, ctx->slab_line_rows,
-                             ctx->slab_lines, ctx->slab_groups, ctx->slab_lo_trips, ctx->pencil_simple);
-            if (p1) *p1 = Pending{P1, gs};
-            if (p2) *p2 = Pending{P2, gs};
-            return 0;
+            g = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(total, want), kMaxGrid));
+            launch_spmv_slab(mode, g, bx.waves, a, st, lds, bx.plane_rows, bx.planes, bx.line_rows, bx.lines, bx.groups, bx.lo_trips, bx.simple);
+            break;
         }
-        if (fmt == 4 && ctx->box_pencil && ctx->opt_box_pencil != 0 && !ctx->use_comm && ctx->opt_box_lds == 0) {
-            // format 7: one wavefront per pencil of 128 rows x all planes of the slowest species
+        case 7:
+            // one wavefront per pencil of 128 rows x all planes of the slowest species
             // (3 workgroups per CU: measured best on the 22^6 box and its slab - 768: 798 / 77.7 us, 512: 866 / 84, 1024: 936 / 86,
             // 2048: 816 / 81; anything that is not a multiple of 256 leaves some CUs with one more - profiles/r04_pencil_grid_sweep.txt)
-            const int gp = product_grid(ctx->pencil_trips, ctx->opt_grid, 768);
-            launch_spmv_pencil(mode, gp, a, st, ctx->box_lds_bytes, ctx->pencil_plane_rows, ctx->pencil_planes, ctx->pencil_trips,
-                               ctx->pencil_order_n == ctx->pencil_trips ? ctx->d_pencil_order.p : nullptr, ctx->pencil_simple);
-            if (p1) *p1 = Pending{P1, gp};
-            if (p2) *p2 = Pending{P2, gp};
-            return 0;
-        }
-        if (fmt == 4 && ctx->box_reach > 0 && ctx->opt_box_lds != 0 && !ctx->use_comm && a.trip_order == nullptr) {
-            // format 6: near entries from an LDS window of x (single rank: x is readable exactly on [0, n))
-            const size_t img = (ctx->box_lds_bytes + 15) & ~(size_t)15;
-            launch_spmv_boxlds(mode, g, a, st, img + 2 * (size_t)(512 + 2 * ctx->box_reach) * sizeof(double), ctx->box_reach);
-        } else {
-            launch_spmv(mode, g, a, nt, fmt, st, ctx->box_lds_bytes);
+            g = product_grid(bx.trips, ctx->opt_grid, 768);
+            launch_spmv_pencil(mode, g, a, st, bx.lds_bytes, bx.plane_rows, bx.planes, bx.trips,
+                               bx.order_n == bx.trips ? ctx->d_pencil_order.p : nullptr, bx.simple);
+            break;
+        case 6:
+            // near entries from an LDS window of x (single rank: x is readable exactly on [0, n))
+            launch_spmv_boxlds(mode, g, a, st, ((bx.lds_bytes + 15) & ~(size_t)15) + 2 * (size_t)(512 + 2 * bx.reach) * sizeof(double), bx.reach);
+            break;
+        default: launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes);
         }
         if (p1) *p1 = Pending{P1, g};
         if (p2) *p2 = Pending{P2, g};
@@ -168,7 +162,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         a.trip_end = e;
         a.trip_split = split_at;
         a.trip_jump = jump;
-        launch_spmv(mode, g, a, nt, fmt, st, ctx->box_lds_bytes);
+        launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes);
         return g;
     };
     if (int rc = overlapped_product(ctx, ps, trips, src, 1, dflt_cap, launch_range, &used)) return rc;
@@ -461,6 +455,26 @@ int adopt_pending_vector(kfsp_ctx *ctx)
     return 0;
 }
 
+// A new generator replaces the resident one (kfsp_set_matrix_csr, kfsp_set_matrix_box; the reference-layout paths decide
+// their state order round these statements and keep them in their own order): pending coordinates are spent, the
+// product count moves on, and whatever was a box is none.
+void begin_generator(kfsp_ctx *ctx)
+{
+    ctx->perm_pending_n = 0;
+    ctx->prod_last = ctx->prod_count;
+    ctx->prod_count = 0;
+    ctx->box = {};
+}
+
+// ... and is ready (the builds on the device, which count their time whether they succeeded or not): exchange mode, pending vector
+int finish_generator(kfsp_ctx *ctx, int rc, std::chrono::steady_clock::time_point t0)
+{
+    if (!rc) rc = setup_exchange(ctx);
+    if (!rc) rc = adopt_pending_vector(ctx);
+    ctx->t_ms[KFSP_T_UPLOAD] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
 // stream, events and the fixed-size buffers of a fresh context
 int init_context(kfsp_ctx *ctx)
 {
@@ -620,8 +634,7 @@ static int set_matrix_ell_impl(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld,
         if (ctx->group) return kfsp::group_update_matrix_ell(ctx, n, bw, ld, adj, offdiag, diag, (int32_t)keep);
         HIP_TRY(hipSetDevice(ctx->device));
         auto t0 = std::chrono::steady_clock::now();
-        ctx->use_box = false;
-        ctx->box_lds_bytes = 0;
+        ctx->box = {};
         if (int rc = resize(ctx, n)) return rc;
         const int64_t row0 = ctx->row0, nloc = ctx->nloc;
         // coordinates handed over for exactly this generator switch the internal order on
@@ -633,10 +646,7 @@ static int set_matrix_ell_impl(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld,
         if (!ctx->opt_host_build) {
             // the arrays go to HBM verbatim and are transposed there (kfsp_build.hip)
             int rc = build_from_ell_device(ctx, n, bw, ld, adj, offdiag, diag, keep);
-            if (!rc) rc = setup_exchange(ctx);
-            if (!rc) rc = adopt_pending_vector(ctx);
-            ctx->t_ms[KFSP_T_UPLOAD] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            return rc;
+            return finish_generator(ctx, rc, t0);
         }
 
         // host transpose (kept for A/B checks of the device build)
@@ -708,11 +718,7 @@ int kfsp_set_matrix_csr(kfsp_ctx *ctx, int64_t n, int64_t row0, int64_t nrows, c
         if (ctx->group) return kfsp::group_set_matrix_csr(ctx, n, row0, nrows, rowptr, col, val);
         HIP_TRY(hipSetDevice(ctx->device));
         ctx->perm_on = false;
-        ctx->perm_pending_n = 0;
-        ctx->prod_last = ctx->prod_count;
-        ctx->prod_count = 0;
-        ctx->use_box = false;
-        ctx->box_lds_bytes = 0;
+        begin_generator(ctx);
         ctx->ell_cols = 0;
         if (int rc = resize(ctx, n)) return rc;
         if (row0 != std::min(ctx->row0, n)) return fail(ctx, -3, "row0 is not this rank's block start (kfsp_row_block)");
@@ -764,255 +770,45 @@ int kfsp_set_matrix_box(kfsp_ctx *ctx, int32_t ns, const int32_t *dims, int32_t 
 {
     return no_throw(ctx, [&]() -> int {
         if (!ctx) return -1;
-        if (ns < 1 || ns > kfsp::kBoxMaxS) return fail(ctx, -2, "1 <= ns <= 8");
-        if (!dims) return fail(ctx, -3, "null dims");
-        if (nr < 1 || nr > kfsp::kBoxMaxR) return fail(ctx, -4, "1 <= nr <= 16");
-        if (!stoich || !ndep || !dep_species) return fail(ctx, -5, "null reaction description");
-        if (!tables) return fail(ctx, -8, "null tables");
+        const char *what = "";
+        if (int rc = kfsp::box_plan_args(ns, dims, nr, stoich, ndep, dep_species, tables, &what)) return fail(ctx, rc, what);
         if (ctx->group) return kfsp::group_set_matrix_box(ctx, ns, dims, nr, stoich, ndep, dep_species, tables);
-        int64_t n = 1, stride[kfsp::kBoxMaxS];
-        for (int s = 0; s < ns; ++s) {
-            if (dims[s] < 1) return fail(ctx, -3, "dims must be positive");
-            stride[s] = n;
-            n *= dims[s];
-            if (n > 2147483647LL - 512) return fail(ctx, -3, "box has more than 2^31 states");
-        }
-        if (n < 2) return fail(ctx, -3, "box has fewer than 2 states");
+        // everything that can refuse the model, before the context changes: a refused call leaves it and its generator alone
+        kfsp::BoxPlan P;
+        const kfsp::BoxPlanOpts opt{ctx->opt_box_pencil, ctx->opt_box_slab_waves, ctx->opt_box_tile, ctx->opt_box_reach,
+                                    ctx->nranks == 1 && !ctx->use_comm};
+        if (int rc = kfsp::box_plan(ns, dims, nr, stoich, ndep, dep_species, tables, opt, P, &what)) return fail(ctx, rc, what);
         HIP_TRY(hipSetDevice(ctx->device));
         auto t0 = std::chrono::steady_clock::now();
         ctx->perm_on = false;
-        ctx->perm_pending_n = 0;
-        ctx->prod_last = ctx->prod_count;
-        ctx->prod_count = 0;
-        if (int rc = resize(ctx, n)) return rc;
-        // reactions sorted by the column offset of their entry (ascending, like the stored diagonals)
-        struct R { int64_t delta; int k; };
-        std::vector<R> order((size_t)nr);
-        for (int k = 0; k < nr; ++k) {
-            int64_t d = 0;
-            for (int s = 0; s < ns; ++s) d -= (int64_t)stoich[(size_t)k * ns + s] * stride[s];
-            order[(size_t)k] = R{d, k};
+        begin_generator(ctx);
+        if (int rc = resize(ctx, P.n)) return rc;
+        HIP_TRY(ctx->d_box.reserve(P.image.size() + 8, false));
+        HIP_TRY(hipMemcpy(ctx->d_box.p, P.image.data(), P.image.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (!P.order.empty()) {
+            HIP_TRY(ctx->d_pencil_order.reserve(P.order.size(), false));
+            HIP_TRY(hipMemcpy(ctx->d_pencil_order.p, P.order.data(), P.order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
-        std::stable_sort(order.begin(), order.end(), [](const R &a, const R &b) { return a.delta < b.delta; });
-        kfsp::BoxDev B;
-        std::memset(&B, 0, sizeof(B));
-        B.ns = ns;
-        B.nr = nr;
-        for (int s = 0; s < ns; ++s) {
-            B.dims[s] = dims[s];
-            B.inv_dim[s] = 1.0 / (double)dims[s];
-        }
-        // table offsets in the order the caller concatenated them: reaction by reaction, factor by factor
-        std::vector<int32_t> toff((size_t)nr * kfsp::kBoxMaxDep, 0);
-        int64_t ntab = 0;
-        for (int k = 0; k < nr; ++k) {
-            if (ndep[k] < 1 || ndep[k] > kfsp::kBoxMaxDep) return fail(ctx, -6, "1 <= ndep <= 3 factors per propensity");
-            for (int i = 0; i < ndep[k]; ++i) {
-                const int s = dep_species[(size_t)k * kfsp::kBoxMaxDep + i];
-                if (s < 0 || s >= ns) return fail(ctx, -7, "factor species out of range");
-                toff[(size_t)k * kfsp::kBoxMaxDep + i] = (int32_t)ntab;
-                ntab += dims[s];
-            }
-        }
-        const int head = kfsp::kBoxImageHead;              // image = [0.0, 0.0][factor tables][fast form's species tables]
-        if (head + ntab > 6000) return fail(ctx, -8, "factor tables exceed the 48 KB they may take in LDS");
-        for (int p = 0; p < nr; ++p) {
-            const int k = order[(size_t)p].k;
-            B.delta[p] = (int32_t)order[(size_t)p].delta;
-            B.ndep[p] = (int8_t)ndep[k];
-            for (int i = 0; i < ndep[k]; ++i) {
-                const int s = dep_species[(size_t)k * kfsp::kBoxMaxDep + i];
-                B.dep_s[p][i] = (int8_t)s;
-                B.dep_nu[p][i] = (int8_t)stoich[(size_t)k * ns + s];
-                B.dep_off[p][i] = head + toff[(size_t)k * kfsp::kBoxMaxDep + i];
-            }
-            int nm = 0;
-            for (int s = 0; s < ns; ++s) {
-                const int v = stoich[(size_t)k * ns + s];
-                if (v == 0) continue;
-                if (nm == kfsp::kBoxMaxDep) return fail(ctx, -5, "a reaction changes more than 3 species");
-                if (v < -100 || v > 100) return fail(ctx, -5, "stoichiometry out of range");
-                B.mov_s[p][nm] = (int8_t)s;
-                B.mov_nu[p][nm] = (int8_t)v;
-                B.mov_dim[p][nm] = dims[s];
-                ++nm;
-            }
-            B.nmov[p] = (int8_t)nm;
-            B.dorder[k] = p;                               // original reaction k sits at sorted position p
-        }
-        // single-factor fast form: every propensity one factor, no species changes by more than 2, at
-        // most kBoxFastPer propensities per species, the entries of a row within 2^32 bytes of x
-        kfsp::BoxFast F;
-        std::memset(&F, 0, sizeof(F));
-        bool fast = ns <= kfsp::kBoxFastS;
-        int per_species[kfsp::kBoxMaxS] = {0};
-        for (int k = 0; k < nr && fast; ++k) {
-            fast = ndep[k] == 1;
-            for (int s = 0; s < ns; ++s) fast = fast && std::abs(stoich[(size_t)k * ns + s]) <= 2;
-            if (fast) fast = ++per_species[dep_species[(size_t)k * kfsp::kBoxMaxDep]] <= kfsp::kBoxFastPer;
-        }
-        const int64_t back = std::max<int64_t>(0, -order.front().delta), fwd = std::max<int64_t>(0, order.back().delta);
-        if (back + fwd + 130 >= (1LL << 28)) fast = false;
-        int per = 2, ns_inst = kfsp::kBoxFastS;
-        int64_t df_at[kfsp::kBoxFastS] = {0};
-        int64_t nimage = head + ntab;
-        if (fast) {
-            for (int s = 0; s < ns; ++s) per = std::max(per, per_species[s]);
-            if (per > 2) per = kfsp::kBoxFastPer;
-            // instantiations (launch_spmv): 2, 3 or 6 species with 2 slots each, else 6 species with 4 slots
-            ns_inst = (per == 2 && ns <= 2) ? 2 : (per == 2 && ns == 3) ? 3 : kfsp::kBoxFastS;
-            nimage += nimage & 1;
-            for (int s = 0; s < ns_inst; ++s) {
-                df_at[s] = nimage;
-                nimage += 2 * (s < ns ? dims[s] : 1);
-            }
-            if (nimage > 8180) {                                  // 64 KB of LDS less the kernel's own few words
-                fast = false;
-                nimage = head + ntab;
-            }
-        }
-        std::vector<double> image((size_t)nimage + (sizeof(kfsp::BoxFast) + 7) / 8, 0.0);
-        std::memcpy(image.data() + head, tables, (size_t)ntab * sizeof(double));
-        if (fast) {
-            F.ns = ns_inst;
-            F.per = per;
-            F.bias8 = (int32_t)(8 * back);
-            for (int s = 0; s < kfsp::kBoxFastS; ++s) {
-                F.dims[s] = s < ns ? dims[s] : 1;                 // missing species: one population count, 0
-                F.inv_dim[s] = 1.0 / (double)F.dims[s];
-                F.df8[s] = (int32_t)(8 * df_at[s]);
-            }
-            struct DF { double dsum; uint32_t valid, pad; };
-            static_assert(sizeof(DF) == 16, "layout of the kernel's BoxDF");
-            int fill[kfsp::kBoxFastS] = {0};
-            int entry_k[kfsp::kBoxFastS * kfsp::kBoxFastPer];
-            for (int e = 0; e < ns_inst * per; ++e) entry_k[e] = -1;
-            for (int p = 0; p < nr; ++p) {                        // ascending column offset within a species
-                const int k = order[(size_t)p].k;
-                const int s = dep_species[(size_t)k * kfsp::kBoxMaxDep];
-                const int j = fill[s]++;
-                F.koff8[s][j] = 8 * (head + toff[(size_t)k * kfsp::kBoxMaxDep] - stoich[(size_t)k * ns + s]);
-                F.delta8[s][j] = (int32_t)(8 * order[(size_t)p].delta);
-                entry_k[s * per + j] = k;
-            }
-            for (int s = 0; s < ns_inst; ++s) {
-                const int d = s < ns ? dims[s] : 1;
-                DF *df = reinterpret_cast<DF *>(image.data() + df_at[s]);
-                for (int i = 0; i < d; ++i) {
-                    double sum = 0.0;
-                    uint32_t valid = 0;
-                    for (int e = 0; e < ns_inst * per; ++e) {
-                        const int k = entry_k[e];
-                        if (k < 0) continue;                      // unused slot: never valid
-                        const int v = s < ns ? stoich[(size_t)k * ns + s] : 0;   // source coordinate = i - v
-                        if (i - v >= 0 && i - v < d) valid |= 1u << e;
-                        if (e / per == s) sum += tables[(size_t)toff[(size_t)k * kfsp::kBoxMaxDep] + i];
-                    }
-                    df[i] = DF{sum, valid, 0u};
-                }
-            }
-            B.pad = ns_inst * 16 + per;
-        }
-        B.ntab = (int32_t)nimage;
-        std::memcpy(image.data() + nimage, &F, sizeof(F));
-        HIP_TRY(ctx->d_box.reserve(image.size() + 8, false));
-        HIP_TRY(hipMemcpy(ctx->d_box.p, image.data(), image.size() * sizeof(double), hipMemcpyHostToDevice));
-        ctx->box = B;
-        ctx->box_fast = fast;
-        // Format 7 (pencils, kfsp_kernels.hip): the instantiation's species are the model's (no padding species), the slowest
-        // species' own entries reach exactly one plane (or are unused slots), no other entry moves the slowest species, planes
-        // have an even number of rows (16-byte pairs), one rank, and there are enough base trips to fill the chip.
-        ctx->box_pencil = false;
-        ctx->box_slab = false;                  // (a box that is not eligible must not keep the slabs of the one before it)
-        ctx->pencil_order_n = 0;
-        if (fast && ns >= 3 && ns == ns_inst && ctx->nranks == 1 && !ctx->use_comm) {
-            const int Ls = ns - 1;
-            int64_t plane = 1;
-            for (int s = 0; s < Ls; ++s) plane *= dims[s];
-            // (1: also small boxes - tests.  Nothing else is required of the reactions: an entry that does not fit the register
-            // scheme - it depends on the slowest species but moves another, or moves the slowest by two - is gathered from
-            // memory as in format 4; entries of other species that move the slowest one get that species' valid bit per step)
-            const bool ok = (plane % 2 == 0) && dims[Ls] >= 2 && ((plane + 127) / 128 >= 4096 || ctx->opt_box_pencil > 0);
-            bool simple = true;
-            for (int k = 0; k < nr; ++k)
-                if (dep_species[(size_t)k * kfsp::kBoxMaxDep] != Ls && stoich[(size_t)k * ns + Ls] != 0) simple = false;
-            ctx->pencil_simple = simple;
-            // Format 8 (slabs): additionally the lines of the second-slowest species have an even number of rows, there are at
-            // least two of them, and at least 256 workgroups' worth of slabs (or the option insists)
-            if (ok && ns >= 3) {
-                int64_t line = 1;
-                for (int s = 0; s < Ls - 1; ++s) line *= dims[s];
-                const int lines = dims[Ls - 1];
-                const int wmax = (int)std::max<int64_t>(1, std::min<int64_t>(12, ctx->opt_box_slab_waves));   // (<= 12 wavefronts per workgroup)
-                const int groups = (lines + wmax - 1) / wmax, waves = (lines + groups - 1) / groups;
-                const int64_t lo_trips = (line + 127) / 128;
-                if (line % 2 == 0 && lines >= 2 && (lo_trips * groups >= 256 || ctx->opt_box_pencil == 2)) {
-                    ctx->box_slab = true;
-                    ctx->slab_line_rows = line;
-                    ctx->slab_lines = lines;
-                    ctx->slab_groups = groups;
-                    ctx->slab_waves = waves;
-                    ctx->slab_lo_trips = lo_trips;
-                }
-            }
-            if (ok) {
-                ctx->box_pencil = true;
-                ctx->pencil_plane_rows = plane;
-                ctx->pencil_planes = dims[Ls];
-                ctx->pencil_trips = (plane + 127) / 128;
-                // the base trips in small tiles of the plane (box_tile_order on the plane's species; option "box_tile": 0 never,
-                // 1 wherever there is such an order, -1 a plane beyond 4 MiB)
-                std::vector<int32_t> po;
-                if (kfsp::box_tile_wanted(ctx->opt_box_tile)) po = kfsp::box_tile_order(Ls, dims, plane, kfsp::box_tile_force(ctx->opt_box_tile, plane));
-                if (!po.empty()) {
-                    HIP_TRY(ctx->d_pencil_order.reserve(po.size(), false));
-                    HIP_TRY(hipMemcpy(ctx->d_pencil_order.p, po.data(), po.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                    ctx->pencil_order_n = (int64_t)po.size();
-                }
-            }
-        }
-        // format 6: the largest shift within opt_box_reach rows decides how much of x a workgroup stages in LDS;
-        // the windows must fit beside the table image in the 64 KB a workgroup gets without asking for more
-        ctx->box_reach = 0;
-        if (fast) {
-            int64_t reach = 0;
-            for (int p = 0; p < nr; ++p) {
-                const int64_t d = std::llabs((long long)order[(size_t)p].delta);
-                if (d <= ctx->opt_box_reach) reach = std::max(reach, d);
-            }
-            reach = (reach + 1) & ~(int64_t)1;
-            const size_t need = (((size_t)nimage * 8 + 15) & ~(size_t)15) + 2 * (size_t)(512 + 2 * reach) * 8 + 256;
-            if (reach > 0 && need <= 64 * 1024) ctx->box_reach = (int)reach;
-        }
-        ctx->box_lds_bytes = (size_t)nimage * sizeof(double);
+        ctx->box = P.g;
         // the same bookkeeping as a banded generator with one diagonal per reaction
         ctx->nchunks = (ctx->nloc + kChunk - 1) / kChunk;
         ctx->slots = 0;
-        int64_t nnz = n;
-        for (int k = 0; k < nr; ++k) {
-            int64_t c = 1;
-            for (int s = 0; s < ns; ++s) c *= std::max<int64_t>(0, dims[s] - std::abs(stoich[(size_t)k * ns + s]));
-            nnz += c;
-        }
-        ctx->nnz = ctx->nranks == 1 ? nnz : 0;             // (per-rank counts are not tracked for boxes)
+        ctx->nnz = ctx->nranks == 1 ? P.nnz : 0;           // (per-rank counts are not tracked for boxes)
         ctx->use_dia = true;
-        ctx->use_box = true;
         ctx->ell_cols = 0;
         ctx->dia_masked = false;
         ctx->dia_coded = false;
         ctx->have_sell = false;
         ctx->sell_coded = false;
         ctx->nd = nr;
-        for (int p = 0; p < nr; ++p) ctx->delta[p] = B.delta[p];
+        for (int p = 0; p < nr; ++p) ctx->delta[p] = P.g.dev.delta[p];
         ctx->dia_ld = round_up(ctx->nchunks * kChunk, 2 * kChunk);
         HIP_TRY(ctx->d_diag.reserve((size_t)ctx->dia_ld + 2 * kChunk, true));
         if (ctx->opt_box_store) {
             // the same generator as STORED diagonals, written by the device from the tables: from here on an
             // ordinary banded generator (no host arrays of the size of the FSP ever exist)
             if (int rc = kfsp::box_materialize(ctx)) return rc;
-            ctx->use_box = false;
-            ctx->box_fast = false;
-            ctx->box_lds_bytes = 0;
+            ctx->box = {};
             if (int rc = kfsp::build_dia_mask(ctx)) return rc;
             if (int rc = kfsp::build_dia_code(ctx)) return rc;
         }
@@ -1077,7 +873,7 @@ int kfsp_matrix_info(const kfsp_ctx *ctx, int64_t *nrows, int64_t *slots, int64_
     if (!ctx) return -1;
     if (ctx->group) return kfsp::group_matrix_info(ctx, nrows, slots, nnz);
     if (nrows) *nrows = ctx->nloc;
-    if (slots) *slots = ctx->use_box ? 0 : (ctx->use_dia ? (int64_t)ctx->nd * ctx->dia_ld : ctx->slots);
+    if (slots) *slots = ctx->box.on ? 0 : (ctx->use_dia ? (int64_t)ctx->nd * ctx->dia_ld : ctx->slots);
     if (nnz) *nnz = ctx->nnz;
     return 0;
 }
@@ -1090,8 +886,8 @@ int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes)
     if (ctx->group) return kfsp::group_matrix_bytes(ctx, force_sell, bytes);
     const int64_t rows = ctx->nchunks * kChunk;
     int64_t b = rows * 24;                                    // diag, x (once), y
-    if (ctx->use_box && !force_sell) {
-        b = rows * 16 + (int64_t)ctx->box_lds_bytes;          // x once, y; the tables are read once per workgroup from cache
+    if (ctx->box.on && !force_sell) {
+        b = rows * 16 + (int64_t)ctx->box.lds_bytes;          // x once, y; the tables are read once per workgroup from cache
     } else if (dia_code_on(ctx) && !force_sell) {
         // what the coded kernel moves: one record per row instead of nd doubles, the dictionaries once
         b += rows * ctx->dia_code_rec + (int64_t)ctx->dia_doff[ctx->nd] * 8;
@@ -1113,9 +909,8 @@ int kfsp_layout_info(const kfsp_ctx *ctx, int64_t *v)
     if (!ctx) return -1;
     if (!v) return -2;
     if (ctx->group) return kfsp::group_layout_info(ctx, v);
-    v[0] = ctx->use_box ? (ctx->box_fast && !ctx->opt_box_generic ? (ctx->box_reach > 0 && ctx->opt_box_lds && !ctx->use_comm ? 6 :
-                           (ctx->box_slab && ctx->opt_box_pencil == 2 && !ctx->use_comm ? 8 :
-                            ctx->box_pencil && ctx->opt_box_pencil != 0 && !ctx->use_comm ? 7 : 4)) : 3) : ctx->use_dia ? (ctx->dia_masked ? 2 : 1) : (ctx->sell_coded ? 5 : 0);
+    const int fmt = product_format(product_form(ctx, false));   // (a product under kfsp_set_trip_order runs format 6 as 4)
+    v[0] = fmt == 9 ? 1 : fmt;
     v[1] = !ctx->use_comm ? 0 : (ctx->use_halo ? 1 : 2);
     v[2] = ctx->halo;
     v[3] = ctx->use_dia ? -1 : ctx->sell_reach;
@@ -1131,12 +926,12 @@ int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v)
     if (!ctx) return -1;
     if (!v) return -2;
     if (ctx->group) ctx = kfsp::group_rank0(ctx);
-    const bool have = ctx->use_dia && !ctx->use_box && ctx->dia_coded;
+    const bool have = ctx->use_dia && !ctx->box.on && ctx->dia_coded;
     v[0] = have ? ctx->dia_code_w : 0;
     v[1] = have ? ctx->dia_code_rec : 0;
     v[2] = have ? ctx->nchunks * kChunk * ctx->dia_code_rec : 0;
     v[3] = have ? (int64_t)ctx->dia_doff[ctx->nd] * 8 : 0;
-    v[4] = ctx->use_dia && !ctx->use_box ? ctx->nd : 0;
+    v[4] = ctx->use_dia && !ctx->box.on ? ctx->nd : 0;
     v[5] = ctx->dia_code_us;
     v[6] = dia_code_on(ctx) ? 1 : 0;
     v[7] = 0;
@@ -1149,7 +944,7 @@ int kfsp_dia_code_dict(kfsp_ctx *ctx, int32_t d, int64_t cap, double *dict, int6
     if (!ctx) return -1;
     if (!count) return -4;
     if (ctx->group) ctx = kfsp::group_rank0(ctx);
-    if (!(ctx->use_dia && !ctx->use_box && ctx->dia_coded)) return fail(ctx, -1, "no coded banded image");
+    if (!(ctx->use_dia && !ctx->box.on && ctx->dia_coded)) return fail(ctx, -1, "no coded banded image");
     if (d < 0 || d >= ctx->nd) return fail(ctx, -2, "no such diagonal");
     const int64_t n = ctx->dia_doff[d + 1] - ctx->dia_doff[d];
     *count = n;
@@ -1179,7 +974,7 @@ int kfsp_build_info(const kfsp_ctx *ctx, int64_t *v)
     v[2] = ctx->last_build_sell ? 1 : 0;
     v[3] = ctx->kc_ok ? 1 : 0;
     v[4] = ctx->order_merges;
-    v[5] = (ctx->use_box && ctx->box_pencil && ctx->pencil_order_n == ctx->pencil_trips) ? ctx->pencil_order_n : 0;
+    v[5] = (ctx->box.on && ctx->box.pencil && ctx->box.order_n == ctx->box.trips) ? ctx->box.order_n : 0;
     return 0;
 }
 
@@ -1305,7 +1100,7 @@ int kfsp_arnoldi(kfsp_ctx *ctx, int m, int jold, int qiop, double break_tol, dou
     double *gfin = ctx->d_g.p;
     // small state spaces: the whole pass in one launch of one workgroup
     const bool small = fused && !ctx->use_comm && ctx->opt_small != 0 && ctx->nchunks * kChunk <= kSmallRows &&
-                       (ctx->use_dia || ctx->have_sell) && !ctx->use_box;
+                       (ctx->use_dia || ctx->have_sell) && !ctx->box.on;
     if (small) {
         SmallArnoldiArgs sa;
         generator_args(ctx, sa.A, sa.D);
@@ -1870,8 +1665,7 @@ int kfsp_drop_rebuild(kfsp_ctx *ctx)
             ctx->coords_ld = cld;
             ctx->coords_ns = cns;
         }
-        ctx->use_box = false;
-        ctx->box_lds_bytes = 0;
+        ctx->box = {};
         if (int rc = resize(ctx, n_new)) return rc;
         ctx->perm_on = ordered;
         ctx->prod_last = ctx->prod_count;
@@ -1885,10 +1679,7 @@ int kfsp_drop_rebuild(kfsp_ctx *ctx)
             }
             rc = kfsp::build_from_resident_ell(ctx, (int32_t)n_new, bw, ld);
         }
-        if (!rc) rc = setup_exchange(ctx);
-        if (!rc) rc = adopt_pending_vector(ctx);
-        ctx->t_ms[KFSP_T_UPLOAD] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return rc;
+        return finish_generator(ctx, rc, t0);
     });
 }
 
@@ -1906,7 +1697,7 @@ int kfsp_expand_resident(kfsp_ctx *ctx, double t_ssa, int64_t seedmix, int32_t n
         // kernels, same output - and rebuilds its own block; the vector is assembled and re-dealt through the communicator)
         if (ctx->group) return kfsp::group_expand_resident(ctx, t_ssa, seedmix, ns, nr, stoich, max_count, capacity, n_new, n_from_ssa);
         const int64_t n = ctx->n;
-        if (ctx->use_box || ctx->opt_host_build || ctx->w_pending || n < 1 || ctx->ell_cols != n || ctx->ell_bw != nr)
+        if (ctx->box.on || ctx->opt_host_build || ctx->w_pending || n < 1 || ctx->ell_cols != n || ctx->ell_bw != nr)
             return fail(ctx, -9, "the reference arrays of the current FSP are not resident on the device (kfsp_set_matrix_ell)");
         if (ctx->coords_n != n || ctx->coords_ns != ns)
             return fail(ctx, -9, "the state coordinates of the current FSP are not resident on the device (option keep_coords, kfsp_set_state_coords)");
@@ -1963,10 +1754,7 @@ int kfsp_expand_resident(kfsp_ctx *ctx, double t_ssa, int64_t seedmix, int32_t n
             }
             rc = kfsp::build_from_resident_ell(ctx, (int32_t)n2, nr, ctx->ell_ld);
         }
-        if (!rc) rc = setup_exchange(ctx);
-        if (!rc) rc = adopt_pending_vector(ctx);
-        ctx->t_ms[KFSP_T_UPLOAD] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return rc;
+        return finish_generator(ctx, rc, t0);
     });
 }
 

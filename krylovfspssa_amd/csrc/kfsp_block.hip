@@ -761,7 +761,7 @@ int spmm_grid(const kfsp_ctx *c) { return product_grid(spmm_trips(c), c->opt_gri
 // streaming kernels of the general path.
 bool small_path(const kfsp_ctx *c)
 {
-    return c->opt_block_small != 0 && !c->blk_tgt && c->opt_adjoint == 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->use_box &&
+    return c->opt_block_small != 0 && !c->blk_tgt && c->opt_adjoint == 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->box.on &&
            c->nchunks * kChunk <= kSmallRows && (c->use_dia || (c->have_sell && !c->sell_coded)) && c->slots < (1LL << 31);
 }
 
@@ -819,7 +819,7 @@ SpmmFn spmm_box_kernel(int kp, int inst, bool dots)
 
 // Option block_box = 2: the generic kernels (k_spmm_boxg, kfsp_block_boxg.hip; k_spmm_boxg_t, kfsp_block_adj.hip) answer
 // for a box without the single-factor form and for any box under box_generic = 1.  Read at every block call.
-bool box_generic_path(const kfsp_ctx *c) { return c->use_box && c->opt_block_box == 2 && (!c->box_fast || c->opt_box_generic != 0); }
+bool box_generic_path(const kfsp_ctx *c) { return c->box.on && c->opt_block_box == 2 && (!c->box.fast || c->opt_box_generic != 0); }
 
 // In the block layout a reach of delta rows is 8 kp delta bytes, and the single-factor kernels (k_spmm_box, k_spmm_box_t)
 // address X as scalar base + unsigned 32-bit lane offset: the backward plus the forward reach plus one 128-row group must
@@ -834,7 +834,7 @@ bool box_block_reach_ok(const kfsp_ctx *c, int kp)
 // generic kernels, which address X by 64-bit row index, may meet the single-factor ones later)
 int box_reach_check(kfsp_ctx *c, int kp)
 {
-    if (!c->use_box || box_generic_path(c) || box_block_reach_ok(c, kp)) return 0;
+    if (!c->box.on || box_generic_path(c) || box_block_reach_ok(c, kp)) return 0;
     return fail(c, -12, "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
                         "at this block width (fewer columns, or option box_store = 1)");
 }
@@ -870,18 +870,18 @@ int spmm_staged(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
 {
     a.box_tab = ctx->d_box.p;
     if (box_generic_path(ctx)) {
-        a.box_ntab = box_generic_image(ctx->box);
+        a.box_ntab = box_generic_image(ctx->box.dev);
         a.box_fast = nullptr;
         if (a.box_ntab == 0) return -1;
         return launch_staged(ctx, transposed ? kStagedBoxgT : kStagedBoxg, kp, dots, a.trips, (size_t)a.box_ntab * sizeof(double),
-                             transposed ? spmm_boxg_t_kernel(kp, dots) : spmm_boxg_kernel(kp, dots), BoxgArgs{a, ctx->box});
+                             transposed ? spmm_boxg_t_kernel(kp, dots) : spmm_boxg_kernel(kp, dots), BoxgArgs{a, ctx->box.dev});
     }
-    a.box_ntab = ctx->box.ntab;
-    a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box_lds_bytes / sizeof(double)));
-    if (!transposed) return launch_staged(ctx, kStagedBox, kp, dots, a.trips, ctx->box_lds_bytes, spmm_box_kernel(kp, ctx->box.pad, dots), a);
+    a.box_ntab = ctx->box.dev.ntab;
+    a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box.lds_bytes / sizeof(double)));
+    if (!transposed) return launch_staged(ctx, kStagedBox, kp, dots, a.trips, ctx->box.lds_bytes, spmm_box_kernel(kp, ctx->box.dev.pad, dots), a);
     BoxAdjDev b;
-    if (!box_adj_build(ctx->box, b)) return -1;
-    return launch_staged(ctx, kStagedBoxT, kp, dots, a.trips, ctx->box_lds_bytes, spmm_box_t_kernel(kp, ctx->box.pad, dots), a, b);
+    if (!box_adj_build(ctx->box.dev, b)) return -1;
+    return launch_staged(ctx, kStagedBoxT, kp, dots, a.trips, ctx->box.lds_bytes, spmm_box_t_kernel(kp, ctx->box.dev.pad, dots), a, b);
 }
 
 // Option block_dia_code: the kernel that reads the coded banded image for this call, or null - the rule of
@@ -941,7 +941,7 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
     hipStream_t st = ctx->stream;
     const int g = spmm_grid(ctx);
     *G = g;
-    if (ctx->use_box) {
+    if (ctx->box.on) {
         if (int rc = box_reach_check(ctx, kp)) return rc;
         const int gs = spmm_staged(ctx, kp, dots, ctx->opt_adjoint != 0, a);
         if (gs < 0) return fail(ctx, -12, kAdjFormMsg);      // (block_supported refuses those first)
@@ -1163,24 +1163,24 @@ int block_supported(kfsp_ctx *ctx)
         if (ctx->opt_adjoint)
             return fail(ctx, -12, "several vectors at once, option adjoint: not under a row partition (the transposed banded "
                                   "product reads the neighbour's generator rows, not only its rows of X)");
-        if (ctx->use_box)
+        if (ctx->box.on)
             return fail(ctx, -12, "several vectors at once: not for a matrix-free generator under a row partition "
                                   "(option box_store = 1 stores it)");
     }
     if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
-    if (ctx->use_box) {
+    if (ctx->box.on) {
         if (!ctx->opt_block_box)
             return fail(ctx, -12, "several vectors at once: not for a matrix-free generator (option box_store = 1 stores it, "
                                   "option block_box = 1 takes it matrix-free)");
         if (box_generic_path(ctx)) {
-            if (box_generic_image(ctx->box) == 0)
+            if (box_generic_image(ctx->box.dev) == 0)
                 return fail(ctx, -12, "several vectors at once: the descriptor of this matrix-free box is not one the generic block "
                                       "kernels can walk (option box_store = 1 stores it)");
             return 0;
         }
         if (ctx->opt_box_generic)
             return fail(ctx, -12, "several vectors at once: not for the interpreted matrix-free product (option box_generic = 1)");
-        if (!ctx->box_fast)
+        if (!ctx->box.fast)
             return fail(ctx, -12, "several vectors at once: this matrix-free box has no single-factor form (option box_store = 1 stores it)");
         return 0;
     }

@@ -46,7 +46,7 @@ decltype(auto) dispatch_kp_dots(int kp, bool dots, F &&f)
 }
 
 // f(species, slots per species) of the single-factor box instantiation; inst = species * 16 + slots per species
-// (BoxDev::pad, kfsp_set_matrix_box), anything else takes the widest one
+// (BoxDev::pad, box_plan), anything else takes the widest one
 template <class F>
 decltype(auto) dispatch_box_inst(int inst, F &&f)
 {

@@ -927,7 +927,7 @@ int build_dia_code(kfsp_ctx *ctx)
     ctx->dia_code_us = 0;
     for (int d = 0; d <= kMaxDiag; ++d) ctx->dia_doff[d] = 0;
     for (int d = 0; d < kMaxDiag; ++d) ctx->dia_distinct[d] = 0;
-    if (!ctx->use_dia || ctx->use_box || ctx->nd < 1 || ctx->dia_ld < 128 || ctx->opt_dia_code == 0) return 0;
+    if (!ctx->use_dia || ctx->box.on || ctx->nd < 1 || ctx->dia_ld < 128 || ctx->opt_dia_code == 0) return 0;
     // the coded kernel exists for the unmasked single-rank product only
     if (ctx->use_comm || ctx->dia_masked) return 0;
     // auto: only where the product is bound by the bytes of the value streams - a generator that cannot stay in the
@@ -1263,10 +1263,10 @@ int box_materialize(kfsp_ctx *ctx)
 {
     hipStream_t st = ctx->stream;
     const int64_t ld = ctx->dia_ld;
-    HIP_TRY(ctx->d_dia.reserve((size_t)ctx->box.nr * (size_t)ld, false));
+    HIP_TRY(ctx->d_dia.reserve((size_t)ctx->box.dev.nr * (size_t)ld, false));
     HIP_TRY(ctx->d_diag.reserve((size_t)ld + 2 * kChunk, true));
     if (ld > 0)
-        hipLaunchKernelGGL(k_box_materialize, dim3((int)((ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ctx->box,
+        hipLaunchKernelGGL(k_box_materialize, dim3((int)((ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ctx->box.dev,
                            ctx->d_box.p, ctx->row0, ctx->nloc, ld, ctx->d_dia.p, ctx->d_diag.p);
     HIP_TRY(hipStreamSynchronize(st));
     return 0;

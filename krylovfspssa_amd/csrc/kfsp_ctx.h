@@ -4,6 +4,7 @@
 
 #include "../../include/kfsp.h"
 #include "kfsp_internal.h"
+#include "kfsp_box_plan.h"
 
 #include <rccl/rccl.h>
 
@@ -216,24 +217,12 @@ struct kfsp_ctx {
     // optional order of the product's wavefront trips (kfsp_set_trip_order / the box tiling): trips of the CURRENT generator
     DevBuf<int32_t> d_trip_order;
     int64_t trip_order_n = 0;          // 0: ascending order
-    // matrix-free box generator (kfsp_set_matrix_box): descriptor (host copy, passed as a kernel
-    // argument) and the factor tables in device memory
-    kfsp::BoxDev box;
+    // matrix-free box generator (kfsp_set_matrix_box): what box_plan decided about it (kfsp_box_plan.h; the descriptor is
+    // passed as a kernel argument), the table image in device memory and the pencil kernel's base-trip order.  Every
+    // generator that is not a box clears `box` whole.
+    kfsp::BoxGeom box;
     DevBuf<double> d_box;
-    bool use_box = false;
-    bool box_fast = false;        // the single-factor form (BoxFast) sits behind the tables
-    // format 7 (pencils along the slowest species, kfsp_kernels.hip): eligible box, rows per plane, planes, base trips
-    // (= ceil(rows per plane / 128)) and their tiled order (0 entries: ascending)
-    bool box_pencil = false, pencil_simple = false;
-    // format 8 (slabs): rows per line of the second-slowest species, lines, wavefronts per workgroup, workgroups per line set
-    bool box_slab = false;
-    int64_t slab_line_rows = 0, slab_lo_trips = 0;
-    int slab_lines = 0, slab_waves = 0, slab_groups = 0;
-    int64_t pencil_plane_rows = 0, pencil_trips = 0, pencil_order_n = 0;
-    int pencil_planes = 0;
     DevBuf<int32_t> d_pencil_order;
-    size_t box_lds_bytes = 0;
-    int box_reach = 0;                // rows of x staged in LDS on either side of a workgroup's 512 (format 6), 0: format 4
     int64_t dia_empty_segments = 0;   // (diagonal, 128-row group) pairs without entries
     // device-side build from the reference layout (kfsp_build.hip)
     DevBuf<int32_t> d_ell_adj, d_cnt, d_ticket;

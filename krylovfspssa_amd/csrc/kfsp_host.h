@@ -133,50 +133,6 @@ inline int vec_grid(int64_t pairs, int64_t opt_vgrid)
     return (int)std::max<int64_t>(std::min<int64_t>(g, std::min<int64_t>(opt_vgrid > 0 ? opt_vgrid : 1024, kMaxGrid)), 1);
 }
 
-// A tiled order of the 128-row trips over a lexicographic box of n rows (ns species, dims fastest first): rows are cut
-// below the slowest stride that is still at most 16 K rows (cut), r = hi * S_cut + lo; blocks of B = 1024 rows of lo; per
-// block ALL lines hi back to back.  A row's +-S neighbours for the strides above the cut are then whole lines away - one
-// line = B rows = 8 KB of x - instead of whole strides: 22^6 with the cut below species 4: the +-22^3 / 22^4 / 22^5
-// neighbours sit 1 / 22 / 484 lines = 8 KB / 180 KB / 4 MB from the row in the order of the sweep.  Empty: keep the
-// ascending order - fewer than three species, a cut stride under 2048 rows, or neither `force` nor a box beyond the
-// caches.  Its one caller is the base-trip order of the pencil kernel (format 7, kfsp_set_matrix_box: the box is a plane,
-// `force` comes from option "box_tile"); tests/box_tile_order_check.cpp calls it without a device.
-inline std::vector<int32_t> box_tile_order(int ns, const int32_t *dims, int64_t n, bool force)
-{
-    std::vector<int32_t> out;
-    const int64_t trips = (n + 127) / 128;
-    if (ns < 3 || trips < 2 || trips > INT32_MAX) return out;
-    int64_t stride = 1, smax = 1;
-    int cut = -1;
-    int64_t scut = 1;
-    for (int s = 0; s < ns; ++s) {
-        if (stride <= 16384 && s > 0) {
-            cut = s;
-            scut = stride;
-        }
-        smax = stride;
-        stride *= dims[s];
-    }
-    const double mall = 256.0 * 1024 * 1024;
-    const bool large = (double)n * 8.0 > mall && 8.0 * 2.0 * (double)smax * 8.0 > mall;
-    if (cut < 1 || scut < 2048 || !(force || large)) return out;
-    const int64_t B = 1024, nhi = (n + scut - 1) / scut;
-    std::vector<std::pair<int64_t, int32_t>> key((size_t)trips);
-    for (int64_t c = 0; c < trips; ++c) {
-        const int64_t r = c * 128, lo = r % scut, hi = r / scut;
-        key[(size_t)c] = {((lo / B) * nhi + hi) * scut + lo, (int32_t)c};
-    }
-    std::sort(key.begin(), key.end());
-    out.resize((size_t)trips);
-    for (int64_t c = 0; c < trips; ++c) out[(size_t)c] = key[(size_t)c].second;
-    return out;
-}
-
-// option "box_tile" -> the `force` of the pencil kernel's base-trip order: -1 a plane beyond 4 MiB, 0 never (no order at
-// all, whatever the size), 1 wherever box_tile_order has one to give
-inline bool box_tile_wanted(int64_t tile) { return tile != 0; }
-inline bool box_tile_force(int64_t tile, int64_t plane_rows) { return tile > 0 || (tile < 0 && plane_rows * 8 > (int64_t)(4 << 20)); }
-
 // the generator's stored images as the kernels take them
 inline void generator_args(const kfsp_ctx *c, SellDev &A, DiaDev &D)
 {
@@ -195,7 +151,7 @@ inline void generator_args(const kfsp_ctx *c, SellDev &A, DiaDev &D)
 
 // ---- the dictionary-coded image of the banded values (kernel format 9), single vector and block alike
 // the product may read it: banded, stored, the image resident for d_dia, unmasked, single rank
-inline bool dia_code_on(const kfsp_ctx *c) { return c->use_dia && !c->use_box && c->dia_coded && !c->dia_masked && !c->use_comm; }
+inline bool dia_code_on(const kfsp_ctx *c) { return c->use_dia && !c->box.on && c->dia_coded && !c->dia_masked && !c->use_comm; }
 
 inline void dia_code_args(const kfsp_ctx *c, DiaCodeDev &C)
 {
@@ -214,6 +170,41 @@ inline void dia_code_args(const kfsp_ctx *c, DiaCodeDev &C)
 inline bool block_dia_code_path(bool coded_on, int64_t opt_block_dia_code, bool adjoint, bool small)
 {
     return coded_on && opt_block_dia_code != 0 && !adjoint && !small;
+}
+
+// ---- the kernel format a WHOLE-product launch takes (run_product), from plain flags, so that a stand-alone program can
+// walk all combinations (tests/box_plan_check.cpp): 0 SELL-64, 5 with coded columns, 1 banded, 2 with group masks, 9 with
+// coded values, 3 matrix-free box, 4 its single-factor form, 8 / 7 that form in slabs / pencils (eligible box, option
+// box_pencil, not under box_lds), 6 with the near part of x in LDS (option box_lds, a reach, the ascending trip order).
+// kfsp_layout_info reports the same function with trip_order = false - the one input a product can change under a
+// resident generator (kfsp_set_trip_order: format 6 then runs as 4) - and 9 as 1.  The launches of a product split
+// round the halo exchange take only 0 - 5 and 9: a communicator rules 6, 7 and 8 out.
+struct ProductForm {
+    bool banded, box;                    // use_dia; a matrix-free box (which is banded)
+    bool fast;                           // ... whose single-factor form may be used (fast && !box_generic)
+    bool slab, pencil, reach;            // what box_plan found the box eligible for (reach > 0)
+    int64_t box_pencil, box_lds;         // the options
+    bool comm, trip_order;
+    bool coded, masked, sell_coded;      // dia_code_on; dia_masked; sell_coded
+    bool force_sell, force_plain_sell;   // kfsp_spmv_bench's variants
+};
+inline int product_format(const ProductForm &f)
+{
+    const bool dia = f.banded && !f.force_sell;
+    if (!dia) return f.sell_coded && !f.force_plain_sell ? 5 : 0;
+    if (!f.box) return f.coded ? 9 : (f.masked ? 2 : 1);
+    if (!f.fast) return 3;
+    if (f.comm) return 4;
+    if (f.slab && f.box_pencil == 2 && f.box_lds == 0) return 8;
+    if (f.pencil && f.box_pencil != 0 && f.box_lds == 0) return 7;
+    if (f.reach && f.box_lds != 0 && !f.trip_order) return 6;
+    return 4;
+}
+inline ProductForm product_form(const kfsp_ctx *c, bool trip_order, bool force_sell = false, bool force_plain_sell = false)
+{
+    return ProductForm{c->use_dia, c->box.on, c->box.fast && !c->opt_box_generic, c->box.slab, c->box.pencil, c->box.reach > 0,
+                       c->opt_box_pencil, c->opt_box_lds, c->use_comm, trip_order, dia_code_on(c), c->dia_masked, c->sell_coded,
+                       force_sell, force_plain_sell};
 }
 
 }  // namespace kfsp

@@ -488,7 +488,7 @@ __device__ __forceinline__ d2 rows_box(const BoxDev &B, const double *tab, const
 // instructions a CU can issue, not by bytes.  If only one of the two rows has the entry, the other slot
 // holds some other element of x, or the element just before / behind x (every device buffer carries
 // guard words, DevBuf): finite, and multiplied by the 0.0.  x is addressed as wave base (scalar) +
-// 32-bit lane offset (kfsp_set_matrix_box checks the reach).  The descriptor is read ONCE per wavefront
+// 32-bit lane offset (box_plan checks the reach).  The descriptor is read ONCE per wavefront
 // into scalar registers (BoxRegs): left as loads inside the row code they would be re-issued for every
 // row, as per-lane vector loads.  BoxRegs, box_load and box_df are shared with the block product: kfsp_box_dev.h.
 template <int S, int NS, int PER>
@@ -1003,7 +1003,7 @@ void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nt, int fmt, hipStr
         return;
     }
     if (fmt == 4) {
-        // a.B.pad = species count of the instantiation * 16 + slots per species (kfsp_set_matrix_box)
+        // a.B.pad = species count of the instantiation * 16 + slots per species (box_plan, kfsp_box_plan.h)
         switch (a.B.pad) {
         case 2 * 16 + 2: launch_box_mode<4, 2, 2>(mode, g, b, a, st, lds_bytes); break;
         case 3 * 16 + 2: launch_box_mode<4, 3, 2>(mode, g, b, a, st, lds_bytes); break;
@@ -1171,7 +1171,7 @@ void launch_pass_reset(double *H, int count, int *flag, hipStream_t st)
 // crosses the fabric is x once plus whatever the second-slowest stride misses in the L2 (the base trips are taken in small tiles,
 // box_tile_order, so that those neighbours are in flight on the same XCD at the same step).
 // Every row is the same sequence of fused multiply-adds over the same operands as in format 4: products are bit-identical
-// (tests/test_gpu_box.py, tests/test_gpu_configs.py).  Eligibility (kfsp_set_matrix_box): the slowest species' entries reach
+// (tests/test_gpu_box.py, tests/test_gpu_configs.py).  Eligibility (box_plan, kfsp_box_plan.h): the slowest species' entries reach
 // exactly one plane, no other entry moves that species, planes have an even number of rows, enough base trips to fill the chip.
 // SIMPLE: no entry of another species moves the slowest one (every birth-death / mass-action box whose reactions change one
 // species each): the entries served from memory keep their validity along the pencil.  Otherwise their valid bit of the

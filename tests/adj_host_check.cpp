@@ -1,6 +1,9 @@
 // Stand-alone check of the host-side helpers of the transposed block product (kfsp_block_dev.h): box_adj_build and
-// ell_adj_resident.  Built by tests/test_block_adjoint_host.py with -fsanitize=address,undefined; prints "ok".
+// ell_adj_resident - and that box_plan (kfsp_box_plan.h) yields the descriptor written by hand below, but for the table
+// offsets (the fixture spaces its tables 10 doubles apart, a caller's lie back to back).  Built by
+// tests/test_block_adjoint_host.py with -fsanitize=address,undefined; prints "ok".
 #include "kfsp_block_dev.h"
+#include "kfsp_box_plan.h"
 
 #include <cstdio>
 #include <cstring>
@@ -42,8 +45,29 @@ static BoxDev toggle_like()
     return B;
 }
 
+// the same model planned, the reactions in the order of the fixture: what box_adj_build reads is the hand-written descriptor
+static void planned_is_the_hand_written_one()
+{
+    const std::vector<int32_t> dims = {7, 5}, stoich = {0, 1, 1, 0, -1, 0, 0, -1}, ndep = {1, 1, 1, 1}, dep = {0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0};
+    const std::vector<double> tables(7 + 5 + 7 + 5, 0.5);
+    std::vector<BoxPlan> plan(1);
+    const char *what = "";
+    CHECK(box_plan(2, dims.data(), 4, stoich.data(), ndep.data(), dep.data(), tables.data(), BoxPlanOpts(), plan[0], &what) == 0);
+    const BoxDev &P = plan[0].g.dev;
+    const BoxDev B = toggle_like();
+    const int off[4] = {2, 9, 14, 21};                       // tables of 7, 5, 7 and 5 doubles behind the head
+    CHECK(plan[0].g.fast && P.ns == B.ns && P.nr == B.nr && P.pad == B.pad && P.dims[0] == B.dims[0] && P.dims[1] == B.dims[1]);
+    for (int p = 0; p < 4; ++p) {
+        CHECK(P.delta[p] == B.delta[p] && P.dorder[p] == p && P.ndep[p] == B.ndep[p] && P.nmov[p] == B.nmov[p]);
+        CHECK(P.dep_s[p][0] == B.dep_s[p][0] && P.dep_off[p][0] == off[p] && P.mov_s[p][0] == B.mov_s[p][0] && P.mov_nu[p][0] == B.mov_nu[p][0]);
+    }
+    std::vector<BoxAdjDev> out(1);
+    CHECK(box_adj_build(P, out[0]) && out[0].bias8 == 8 * 7);
+}
+
 int main()
 {
+    planned_is_the_hand_written_one();
     {
         const BoxDev B = toggle_like();
         std::vector<BoxAdjDev> out(1);                       // on the heap: an overrun is the sanitizer's to find

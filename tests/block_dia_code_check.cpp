@@ -71,9 +71,9 @@ int main()
         c->use_comm = true;
         CHECK(!dia_code_on(c));
         c->use_comm = false;
-        c->use_box = true;
+        c->box.on = true;
         CHECK(!dia_code_on(c));
-        c->use_box = false;
+        c->box.on = false;
         c->dia_coded = false;
         CHECK(!dia_code_on(c));
         c->dia_coded = true;

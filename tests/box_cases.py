@@ -156,7 +156,7 @@ BLOCK_K = (1, 5, 16)
 PARTITIONED = (("box_toggle_2x2", 2, False), ("box_toggle_2x2", 3, False), ("box_repressilator_3x2", 2, False),
                ("box_repressilator_3x2", 3, True), ("box_birth_death_6x2", 2, False), ("box_birth_death_6x2", 3, False),
                ("goutsias", 2, False), ("goutsias", 3, False))
-# the instantiation <species, slots> of each single-factor case (the rule of kfsp_set_matrix_box)
+# the instantiation <species, slots> of each single-factor case (the rule of box_plan, csrc/kfsp_box_plan.h)
 INSTANCE = {"box_toggle_2x2": (2, 2), "box_repressilator_3x2": (3, 2), "box_birth_death_6x2": (6, 2), "box_four_slot_6x4": (6, 4),
             "box_one_species": (2, 2), "decode_49x4x3": (3, 2), "decode_8x49x2": (3, 2), "decode_2x49x2x2x2x2": (6, 2),
             "decode_toggle_98x6": (2, 2), "dup_12x9": (6, 4), "loop_toggle_97x61": (2, 2), "loop_repressilator_17x16x16": (3, 2),
@@ -198,7 +198,8 @@ def vector(n, seed):
 
 
 def instance_of(mdl):
-    """<species, slots> the host instantiates for a single-factor model (kfsp_set_matrix_box)"""
+    """<species, slots> the host instantiates for a single-factor model: the `per` / `ns_inst` rule of box_plan
+    (csrc/kfsp_box_plan.h) restated; tests/test_box_plan_host.py holds the two against each other"""
     per = max(2, max(map(len, RR.box_slots(mdl))))
     if per > 2:
         per = 4
@@ -207,8 +208,9 @@ def instance_of(mdl):
 
 def pencil_format(mdl, pencil):
     """the kernel format option box_pencil = 1 / 2 selects on a small single-factor box (the eligibility rule of
-    kfsp_set_matrix_box): pencils need the model's species to be the instantiation's, at least three of them, planes of
-    an even number of rows and two planes; slabs also lines of an even number of rows and two lines"""
+    box_plan, csrc/kfsp_box_plan.h, restated; tests/test_box_plan_host.py compares them): pencils need the model's
+    species to be the instantiation's, at least three of them, planes of an even number of rows and two planes; slabs
+    also lines of an even number of rows and two lines"""
     if not pencil:
         return 4
     ns = mdl.d
@@ -220,7 +222,7 @@ def pencil_format(mdl, pencil):
 
 
 def slab_geometry(dims, slab_waves=12):
-    """(lines, groups, waves, lo_trips) of format 8, the rule of kfsp_set_matrix_box restated: the lines of the
+    """(lines, groups, waves, lo_trips) of format 8, the rule of box_plan (csrc/kfsp_box_plan.h) restated: the lines of the
     second-slowest species are shared out over the fewest workgroups of at most min(12, box_slab_waves) wavefronts, and
     evenly over those; a workgroup takes 128 rows of each of its lines"""
     line, lines = int(np.prod(dims[:-2])), int(dims[-2])
@@ -238,8 +240,8 @@ def vec_grid(n, vec_grid_blocks=0):
 
 
 def tile_order(dims):
-    """box_tile_order(force) of kfsp_host.h restated for the species `dims` of a plane (fastest first): () where it gives
-    no order, else the base trips sorted by (1024-row block of the row below the cut, line above the cut, row below the
+    """box_tile_order(force) of kfsp_box_plan.h - the order box_plan hands to the pencil kernel - restated for the
+    species `dims` of a plane (fastest first): () where it gives no order, else the base trips sorted by (1024-row block of the row below the cut, line above the cut, row below the
     cut), the cut being the slowest stride of a species but the first that is at most 16384 rows"""
     n = int(np.prod(dims))
     trips = -(-n // 128)

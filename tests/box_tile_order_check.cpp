@@ -1,4 +1,4 @@
-// Stand-alone check of box_tile_order and of what option "box_tile" asks of it (kfsp_host.h): the order is a permutation
+// Stand-alone check of box_tile_order and of what option "box_tile" asks of it (kfsp_box_plan.h): the order is a permutation
 // of the trips or empty, and empty exactly where the rule says so.  With arguments - force, then the dimensions fastest
 // first - it prints the order, one trip per line, for tests/test_box_gated_cases.py to compare with its own restatement.
 // Built there with -fsanitize=address,undefined; without arguments it prints "ok".

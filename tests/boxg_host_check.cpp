@@ -1,6 +1,8 @@
 // Stand-alone check of the host-side helper of the generic matrix-free block product (kfsp_block_dev.h):
-// box_generic_image.  Built by tests/test_block_boxg_host.py with -fsanitize=address,undefined; prints "ok".
+// box_generic_image - and that box_plan (kfsp_box_plan.h) yields, field by field, the descriptor written by hand below.
+// Built by tests/test_block_boxg_host.py with -fsanitize=address,undefined; prints "ok".
 #include "kfsp_block_dev.h"
+#include "kfsp_box_plan.h"
 
 #include <cstdio>
 #include <cstring>
@@ -17,7 +19,7 @@ static int failures = 0;
         }                                                           \
     } while (0)
 
-// a box of dims (7, 5, 3) as kfsp_set_matrix_box stores it, by ascending source offset:
+// a box of dims (7, 5, 3) as box_plan describes it for kfsp_set_matrix_box, by ascending source offset:
 //   p = 0: the conversion x0 -> x1 (delta 1 - 7 = -6) at f(x0) g(x1); p = 1: a birth of species 0 (delta -1) at three factors;
 //   p = 2: a death of species 2 (delta 35).  The caller listed the birth first: dorder = (1, 0, 2), and its tables come
 //   first behind the head of 2 doubles - 7 + 5 + 3, then the conversion's 7 + 5, then the death's 3: 32 doubles in all
@@ -59,8 +61,32 @@ static BoxDev three_species()
     return B;
 }
 
+// the same model as a caller hands it over - the birth, the conversion, the death - planned: the descriptor above
+static void planned_is_the_hand_written_one()
+{
+    const std::vector<int32_t> dims = {7, 5, 3}, stoich = {1, 0, 0, -1, 1, 0, 0, 0, -1}, ndep = {3, 2, 1}, dep = {0, 1, 2, 0, 1, 0, 2, 0, 0};
+    const std::vector<double> tables(30, 1.5);
+    std::vector<BoxPlan> plan(1);
+    const char *what = "";
+    CHECK(box_plan(3, dims.data(), 3, stoich.data(), ndep.data(), dep.data(), tables.data(), BoxPlanOpts(), plan[0], &what) == 0);
+    const BoxDev &P = plan[0].g.dev;
+    BoxDev B = three_species();
+    B.ntab = 32;                                             // three factors: no single-factor form, the image ends behind the tables
+    CHECK(P.ns == B.ns && P.nr == B.nr && P.ntab == B.ntab && P.pad == 0 && !plan[0].g.fast && plan[0].g.on && plan[0].n == 105);
+    for (int s = 0; s < kBoxMaxS; ++s) CHECK(P.dims[s] == B.dims[s] && P.inv_dim[s] == (s < 3 ? 1.0 / (double)B.dims[s] : 0.0));
+    for (int p = 0; p < kBoxMaxR; ++p) {
+        CHECK(P.delta[p] == B.delta[p] && P.dorder[p] == B.dorder[p] && P.ndep[p] == B.ndep[p] && P.nmov[p] == B.nmov[p]);
+        for (int i = 0; i < kBoxMaxDep; ++i) {
+            CHECK(P.dep_s[p][i] == B.dep_s[p][i] && P.dep_nu[p][i] == B.dep_nu[p][i] && P.dep_off[p][i] == B.dep_off[p][i]);
+            CHECK(P.mov_s[p][i] == B.mov_s[p][i] && P.mov_nu[p][i] == B.mov_nu[p][i] && P.mov_dim[p][i] == B.mov_dim[p][i]);
+        }
+    }
+    CHECK(box_generic_image(P) == 32);
+}
+
 int main()
 {
+    planned_is_the_hand_written_one();
     std::vector<BoxDev> box(1);                              // on the heap: an overrun is the sanitizer's to find
     box[0] = three_species();
     BoxDev &B = box[0];

@@ -1,8 +1,8 @@
 """The CPU side of tests/test_gpu_box_slab_waves.py and tests/test_gpu_nt_loads.py: that the shapes of tests/box_cases.py
 and tests/krylov_ref.py reach the kernel variants they are there for - by the host's rules restated (the slab geometry
-and the streaming grid of kfsp_set_matrix_box / kfsp_host.h) -, box_tile_order itself in a stand-alone program under
-AddressSanitizer / UBSan against the restatement in box_cases, and that every option kfsp_set_option stores is read
-somewhere."""
+of box_plan, kfsp_box_plan.h, and the streaming grid of kfsp_host.h) -, box_tile_order itself in a stand-alone program
+under AddressSanitizer / UBSan against the restatement in box_cases, and that every option kfsp_set_option stores is
+read somewhere."""
 import glob
 import os
 import re
@@ -66,7 +66,7 @@ def test_tiled_orders_are_far_from_ascending():
 
 
 def test_conversion_box_takes_the_masked_instantiation():
-    """the rule of kfsp_set_matrix_box restated: a reaction that moves the slowest species and depends on another one
+    """the rule of box_plan (kfsp_box_plan.h) restated: a reaction that moves the slowest species and depends on another one
     makes the pencil kernels mask its entry plane by plane; none of the other gated boxes has one"""
     def simple(mdl):
         st = np.asarray(mdl.stoich)
