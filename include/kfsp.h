@@ -180,7 +180,8 @@ int kfsp_matrix_info(const kfsp_ctx *ctx, int64_t *nrows, int64_t *slots, int64_
  * are.  force_sell = 1: the figure for kfsp_spmv_bench variant 2; 3: for variant 3 (plain columns).
  * SELL-64 with dictionary-coded columns (format 5): coded chunks count 8 B per entry + their code words + their
  * offset tables (in 64-byte lines) instead of 12 B per entry.  Banded with dictionary-coded values (kfsp_dia_code_info
- * v[6] = 1): rows x (24 + record bytes) + the dictionaries. */
+ * v[6] = 1): rows x (24 + record bytes) + the dictionaries; with DIAG folded into the records (v[7] > 0, option
+ * "dia_code_diag") no DIAG stream: rows x (16 + 8) + the dictionaries + v[7]. */
 int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes);
 /* what the device holds and how a partitioned product exchanges its source vector, v[8]:
  *   v[0] kernel format: 0 SELL-64, 1 banded, 2 banded with group masks, 3 / 4 matrix-free box (interpreted / fast path),
@@ -194,7 +195,8 @@ int kfsp_layout_info(const kfsp_ctx *ctx, int64_t *v);
  * kfsp_layout_info keeps answering 1), v[24]:
  *   v[0] bits per code, 8 or 16 (0: no coded image is resident), v[1] bytes per row record (8 / 16), v[2] record bytes one
  *   product reads, v[3] bytes of all dictionaries, v[4] stored diagonals, v[5] microseconds the last build (or the attempt)
- *   took, v[6] 1 when the product kernel reads the coded image (unmasked, no communicator), v[7] 0,
+ *   took, v[6] 1 when the product kernel reads the coded image (unmasked, no communicator), v[7] bytes of the DIAG tables
+ *   when DIAG is folded into bits 48-63 of the 8-byte records (option "dia_code_diag"), 0 while DIAG is an 8-byte stream,
  *   v[8 + d] distinct values of diagonal d (counting stops soon after 5120; 0: not counted).
  * A group context answers for its first rank. */
 int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v);
@@ -806,6 +808,14 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * 0 never, 1 always try), "dia_code" (dictionary-coded values of a banded generator, DESIGN.md 4.1e: per diagonal the distinct
  * doubles once, per row one 8- or 16-bit code per diagonal; bit-identical products from 8 or 16 B per row instead of 8 B per
  * stored entry; -1, default: generators whose value streams exceed 192 MiB, single rank, unmasked; 0 never; 1 always try),
+ * "dia_code_diag" (DIAG of such a coded generator folded into the spare bits of its 8-byte records, DESIGN.md 4.1e: DIAG is a
+ * sum of one table entry per mixed-radix digit of the row index up to a few ulps, and bits 48-63 of the record hold the signed
+ * difference of the two 64-bit patterns, so the product rebuilds the stored double bit for bit and reads no DIAG stream; taken
+ * only when the diagonals' offsets are strides of at most three digits starting at 1, nd x code bits <= 48, n < 2^31, the
+ * tables fit the LDS beside the dictionaries and EVERY row round-trips, otherwise the image stays what "dia_code" built;
+ * -1: only generators that pass the size gate of "dia_code"'s own default, whether or not "dia_code" was forced; 0, default:
+ * never - on the benchmark's generator the fold measured 8 % less time per product, which is inside three times the run-to-run
+ * spread of the benchmark, so it is not made the default; 1 always try; read when the generator is set),
  * "m_max" (largest Krylov dimension the basis is allocated for, default and maximum 100 = M_MAX of
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so

@@ -48,6 +48,7 @@ void set_matrix_args(const kfsp_ctx *c, SpmvArgs &a)
 {
     generator_args(c, a.A, a.D);
     dia_code_args(c, a.C);
+    a.G = dia_code_on(c) ? c->dia_diag : DiaDiagDev{};
     if (c->box.on) a.B = c->box.dev;
     else a.B.ns = a.B.nr = a.B.ntab = 0;
     a.box_tab = c->d_box.p;
@@ -891,6 +892,8 @@ int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes)
     } else if (dia_code_on(ctx) && !force_sell) {
         // what the coded kernel moves: one record per row instead of nd doubles, the dictionaries once
         b += rows * ctx->dia_code_rec + (int64_t)ctx->dia_doff[ctx->nd] * 8;
+        // DIAG folded into the records: no DIAG stream, its tables once
+        if (ctx->dia_diag.nk > 0) b += (int64_t)ctx->dia_diag.ntab * 8 - rows * 8;
     } else if (ctx->use_dia && !force_sell) {
         b += (int64_t)ctx->nd * ctx->dia_ld * 8;
         if (ctx->dia_masked) b += (ctx->dia_ld >> 7) * 4 - ctx->dia_empty_segments * 128 * 8;
@@ -934,7 +937,7 @@ int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v)
     v[4] = ctx->use_dia && !ctx->box.on ? ctx->nd : 0;
     v[5] = ctx->dia_code_us;
     v[6] = dia_code_on(ctx) ? 1 : 0;
-    v[7] = 0;
+    v[7] = have && ctx->dia_diag.nk > 0 ? (int64_t)ctx->dia_diag.ntab * 8 : 0;
     for (int d = 0; d < kMaxDiag; ++d) v[8 + d] = ctx->use_dia && d < ctx->nd ? ctx->dia_distinct[d] : 0;
     return 0;
 }
@@ -1971,6 +1974,7 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "box_slab_waves") ctx->opt_box_slab_waves = value;
     else if (k == "sell_code") ctx->opt_sell_code = value;
     else if (k == "dia_code") ctx->opt_dia_code = value;
+    else if (k == "dia_code_diag") ctx->opt_dia_code_diag = value;
     else if (k == "ssa_resident") ctx->opt_ssa_resident = value;
     else if (k == "keep_coords") ctx->opt_keep_coords = value;
     else if (k == "ssa_general") ctx->opt_ssa_general = value;

@@ -920,9 +920,66 @@ __global__ __launch_bounds__(kBlock) void k_dia_encode(int64_t ld, int nd, const
     }
 }
 
+// ---- DIAG folded into the spare bits of the 8-byte records (option dia_code_diag; kfsp_dia_diag.h) --------------
+// 1. k_dia_diag_tables: one table per digit of the row index from the rows of DIAG along that axis.
+// 2. k_dia_diag_fold<false>: every one of the ld rows the product computes is encoded (dia_diag_encode: the predictor, the
+//    residual, the decode, +0.0 in the padding); the first row that fails raises the flag and nothing has been written.
+// 3. k_dia_diag_fold<true>, only when no row failed: the residual goes into bits 48-63 of each record.
+__global__ __launch_bounds__(kBlock) void k_dia_diag_tables(DiaDiagDev G, int64_t n, const double *__restrict__ diag, double *__restrict__ tab)
+{
+    const double at0 = diag[0];
+    for (int k = 0; k < G.nk; ++k)
+        for (int j = threadIdx.x; j < G.size[k]; j += kBlock) {
+            const int64_t r = (int64_t)j * G.stride[k];
+            tab[G.toff[k] + j] = dia_diag_entry(k == G.nk - 1, r < n ? diag[r] : 0.0, at0);
+        }
+}
+
+extern __shared__ double diag_tab_lds[];
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void k_dia_diag_fold(DiaDiagDev G, int64_t ld, int64_t n, const double *__restrict__ diag,
+                                                          const double *__restrict__ tab, unsigned long long *__restrict__ rec,
+                                                          unsigned int *__restrict__ failed)
+{
+    for (int i = threadIdx.x; i < G.ntab; i += kBlock) diag_tab_lds[i] = tab[i];
+    __syncthreads();
+    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < ld; r += (int64_t)gridDim.x * kBlock) {
+        uint64_t field;
+        const bool ok = dia_diag_encode(G, diag_tab_lds, r, n, diag[r], &field);
+        if (WRITE) rec[r] = (rec[r] & ((1ull << kDiagFoldBit) - 1ull)) | field;
+        else if (!ok) *failed = 1u;
+    }
+}
+
+// The fold of the image build_dia_code has just written (C), or none: a generator that fails anywhere keeps that image
+// untouched and its product reads the DIAG stream.  `failed`: a device word that is 0.
+static int fold_dia_diag(kfsp_ctx *ctx, const DiaCodeDev &C, int grid, unsigned int *failed)
+{
+    hipStream_t st = ctx->stream;
+    const int nd = ctx->nd;
+    DiaDiagDev G;
+    if (!dia_diag_plan(nd, ctx->delta, ctx->n, C.w, C.rec_bytes, (int64_t)kDiaCodeLds - (int64_t)C.doff[nd] * 8, &G)) return 0;
+    if (ctx->row0 != 0 || ctx->nloc != ctx->n) return 0;
+    G.base = C.doff[nd];
+    double *tab = ctx->d_ddict.p + G.base;                 // behind the dictionaries: kDictCap doubles hold both (the plan's LDS check)
+    const size_t lds = (size_t)G.ntab * sizeof(double);
+    const int64_t ld = ctx->dia_ld;
+    hipLaunchKernelGGL(k_dia_diag_tables, dim3(1), dim3(kBlock), 0, st, G, ctx->n, ctx->d_diag.p, tab);
+    hipLaunchKernelGGL((k_dia_diag_fold<false>), dim3(grid), dim3(kBlock), lds, st, G, ld, ctx->n, ctx->d_diag.p, tab, ctx->d_dcode.p, failed);
+    unsigned int hf = 0;
+    HIP_TRY(hipMemcpyAsync(&hf, failed, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hf != 0) return 0;
+    hipLaunchKernelGGL((k_dia_diag_fold<true>), dim3(grid), dim3(kBlock), lds, st, G, ld, ctx->n, ctx->d_diag.p, tab, ctx->d_dcode.p, failed);
+    HIP_TRY(hipStreamSynchronize(st));
+    ctx->dia_diag = G;
+    return 0;
+}
+
 int build_dia_code(kfsp_ctx *ctx)
 {
     ctx->dia_coded = false;
+    ctx->dia_diag = DiaDiagDev{};
     ctx->dia_code_w = ctx->dia_code_rec = 0;
     ctx->dia_code_us = 0;
     for (int d = 0; d <= kMaxDiag; ++d) ctx->dia_doff[d] = 0;
@@ -991,6 +1048,9 @@ int build_dia_code(kfsp_ctx *ctx)
         ctx->dia_code_w = w;
         ctx->dia_code_rec = rec;
         ctx->dia_coded = true;
+        // option dia_code_diag: 1 always; -1 only where dia_code's own size gate (above) lets the generator through, forced or not
+        if (ctx->opt_dia_code_diag > 0 || (ctx->opt_dia_code_diag < 0 && plain > 192.0 * 1024 * 1024))
+            if (int rc = fold_dia_diag(ctx, C, grid, missed)) return rc;
     }
     ctx->dia_code_us = (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     return 0;

@@ -209,6 +209,7 @@ struct kfsp_ctx {
     int dia_code_w = 0, dia_code_rec = 0;          // bits per code, bytes per record
     int32_t dia_doff[kMaxDiag + 1] = {0};
     int64_t dia_distinct[kMaxDiag] = {0};          // distinct values per diagonal as far as they were counted
+    kfsp::DiaDiagDev dia_diag{};                         // DIAG folded into the records (kfsp_dia_diag.h): nk = 0 when it is a stream; tables behind the dictionaries in d_ddict
     int64_t dia_code_us = 0;                       // what the last build_dia_code took
     // which 128-row groups of which diagonals hold entries at all (used when enough are empty)
     DevBuf<uint32_t> d_gmask;
@@ -378,6 +379,8 @@ struct kfsp_ctx {
     int32_t coords_ld = 0, coords_ns = 0;
     int64_t opt_sell_code = -1;            // dictionary-coded SELL columns: -1 auto (under the internal state order), 0 never, 1 always try
     int64_t opt_dia_code = -1;             // dictionary-coded banded values: -1 auto (generators beyond the Infinity Cache), 0 never, 1 always try
+    int64_t opt_dia_code_diag = 0;         // DIAG folded into the coded records' spare bits: -1 generators that pass dia_code's size gate, 0 never (default:
+                                           // the gain on c3 did not clear the margin asked of it), 1 always try
     int64_t opt_box_store = 0;            // 1: kfsp_set_matrix_box writes the generator out as stored diagonals on the device (banded form)
     int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12);
                                           // 2: as 1, and every other box (or any under box_generic) through k_spmm_boxg

@@ -1,0 +1,178 @@
+// Private: DIAG of a coded banded generator folded into the spare bits of its 8-byte row records (option dia_code_diag;
+// kernel format 9 with FOLD, kfsp_kernels.hip; build_dia_code, kfsp_build.hip).  DIAG is the sum of all
+// propensities at the row's state and every propensity depends on one species, so DIAG is - up to rounding - a sum of
+// one table entry per mixed-radix digit of the row index.  The record keeps, in bits 48-63, the signed difference
+// between the 64-bit pattern of the stored DIAG and that of the predictor, read as integers: pattern(P) + residual is
+// the stored pattern, bit for bit, and the 8-byte DIAG stream is not read by the product.
+// Plain inline code without a context and without a HIP call: the build kernels, the product kernel and the
+// stand-alone host program tests/dia_diag_fold_check.cpp call the SAME functions.
+#pragma once
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define KFSP_HD __host__ __device__
+#else
+#define KFSP_HD
+#endif
+
+namespace kfsp {
+
+constexpr int kDiagFoldDigits = 3;      // at most three digits (distinct |delta|)
+constexpr int kDiagFoldBit = 48;        // the residual's field: bits 48-63 of the record
+
+// Row r = x0 + size[0] (x1 + size[1] x2): digit k has size[k] values and stride[k] rows, fastest first; the slowest
+// digit's size is ceil(n / stride).  nk = 0: no fold.
+struct DiaDiagDev {
+    int32_t nk;
+    int32_t size[kDiagFoldDigits];
+    int32_t stride[kDiagFoldDigits];
+    int32_t toff[kDiagFoldDigits];      // table of digit k starts at toff[k] of the tables (toff[0] = 0)
+    uint32_t magic[2];                  // q / size[k] = mul_hi(q, magic[k]) >> shift[k] for q < 2^31 (dia_diag_div)
+    int32_t shift[2];
+    int32_t ntab;                       // entries of all tables: sum of size[]
+    int32_t base;                       // where the tables start in the kernel's LDS image, in doubles (behind the dictionaries)
+};
+
+// Exact q / d for q < 2^31 and d >= 2 (Granlund & Montgomery): l = ceil(log2 d), magic = floor(2^(31 + l) / d) + 1 < 2^32,
+// q / d = (q * magic) >> (31 + l).
+inline void dia_diag_magic(uint32_t d, uint32_t *magic, int32_t *shift)
+{
+    int l = 0;
+    while (((uint64_t)1 << l) < d) ++l;
+    *magic = (uint32_t)((((uint64_t)1 << (31 + l)) / d) + 1);
+    *shift = l - 1;
+}
+KFSP_HD inline uint32_t dia_diag_div(uint32_t q, uint32_t magic, int shift)
+{
+    return (uint32_t)(((uint64_t)q * magic) >> 32) >> shift;
+}
+
+// The plan: from the stored diagonals' offsets, the number of rows, the code width, the record size and the LDS bytes
+// left beside the dictionaries.  The distinct |delta| ascending are the strides; accepted only when the first is 1,
+// every stride is a multiple (>= 2 x) of the one before, there are at most 3, n < 2^31, the record is 8 bytes with
+// bits 48-63 free (nd w <= 48) and the tables (8 B per digit value) fit the LDS left.  Anything else: false, *G zeroed.
+inline bool dia_diag_plan(int nd, const int32_t *delta, int64_t n, int w, int rec_bytes, int64_t lds_left, DiaDiagDev *G)
+{
+    *G = DiaDiagDev{};
+    if (nd < 1 || nd > 16 || !delta || n < 1 || n >= ((int64_t)1 << 31)) return false;
+    if (rec_bytes != 8 || w < 1 || nd * w > kDiagFoldBit) return false;
+    int64_t s[kDiagFoldDigits + 1];
+    int nk = 0;
+    for (int d = 0; d < nd; ++d) {                       // distinct |delta|, ascending (insertion)
+        const int64_t a = delta[d] < 0 ? -(int64_t)delta[d] : (int64_t)delta[d];
+        int at = 0;
+        while (at < nk && s[at] < a) ++at;
+        if (at < nk && s[at] == a) continue;
+        if (nk == kDiagFoldDigits) return false;
+        for (int i = nk; i > at; --i) s[i] = s[i - 1];
+        s[at] = a;
+        ++nk;
+    }
+    if (s[0] != 1) return false;
+    for (int k = 0; k + 1 < nk; ++k)
+        if (s[k + 1] % s[k] != 0 || s[k + 1] / s[k] < 2) return false;
+    if (s[nk - 1] >= n) return false;                    // (a diagonal that long has no entry)
+    int64_t total = 0;
+    DiaDiagDev P{};
+    P.nk = nk;
+    for (int k = 0; k < nk; ++k) {
+        const int64_t size = k + 1 < nk ? s[k + 1] / s[k] : (n + s[k] - 1) / s[k];
+        P.size[k] = (int32_t)size;
+        P.stride[k] = (int32_t)s[k];
+        P.toff[k] = (int32_t)total;
+        total += size;
+        if (total * 8 > lds_left) return false;
+        if (k + 1 < nk) dia_diag_magic((uint32_t)size, &P.magic[k], &P.shift[k]);
+    }
+    P.ntab = (int32_t)total;
+    *G = P;
+    return true;
+}
+
+// the digits of row g (< 2^31) ...
+KFSP_HD inline void dia_diag_digits(const DiaDiagDev &G, uint32_t g, int &x0, int &x1, int &x2)
+{
+    x0 = (int)g;
+    x1 = x2 = 0;
+    if (G.nk >= 2) {
+        const uint32_t t = dia_diag_div(g, G.magic[0], G.shift[0]);
+        x0 = (int)(g - t * (uint32_t)G.size[0]);
+        x1 = (int)t;
+        if (G.nk == 3) {
+            const uint32_t u = dia_diag_div(t, G.magic[1], G.shift[1]);
+            x1 = (int)(t - u * (uint32_t)G.size[1]);
+            x2 = (int)u;
+        }
+    }
+}
+// ... and of the row behind it: + 1 with carry (the slowest digit never wraps)
+KFSP_HD inline void dia_diag_next(const DiaDiagDev &G, int &x0, int &x1, int &x2)
+{
+    ++x0;
+    if (G.nk >= 2 && x0 >= G.size[0]) {
+        x0 = 0;
+        ++x1;
+        if (G.nk == 3 && x1 >= G.size[1]) {
+            x1 = 0;
+            ++x2;
+        }
+    }
+}
+
+// A table entry from DIAG along one axis: the slowest digit carries the value itself, the others their difference to row 0.
+KFSP_HD inline double dia_diag_entry(bool slowest, double on_axis, double at_row0) { return slowest ? on_axis : on_axis - at_row0; }
+
+// The predictor: the slowest digit first, additions only.  t: the tables.  The slowest digit is clamped to its table
+// (rows of the padding beyond n have no entry; their value is not the predictor's, see dia_diag_value).
+KFSP_HD inline double dia_diag_predict(const DiaDiagDev &G, const double *t, int x0, int x1, int x2)
+{
+    if (G.nk == 3) {
+        x2 = x2 < G.size[2] ? x2 : G.size[2] - 1;
+        return (t[G.toff[2] + x2] + t[G.toff[1] + x1]) + t[x0];
+    }
+    if (G.nk == 2) {
+        x1 = x1 < G.size[1] ? x1 : G.size[1] - 1;
+        return t[G.toff[1] + x1] + t[x0];
+    }
+    x0 = x0 < G.size[0] ? x0 : G.size[0] - 1;
+    return t[x0];
+}
+
+KFSP_HD inline uint64_t dia_diag_bits(double v)
+{
+    uint64_t b;
+    __builtin_memcpy(&b, &v, 8);
+    return b;
+}
+KFSP_HD inline double dia_diag_from_bits(uint64_t b)
+{
+    double v;
+    __builtin_memcpy(&v, &b, 8);
+    return v;
+}
+
+// Decode: pattern(P) + the sign-extended bits 48-63 of the record; rows of the padding (in_range false) hold +0.0.
+KFSP_HD inline double dia_diag_value(double p, uint64_t rec, bool in_range)
+{
+    const uint64_t b = dia_diag_bits(p) + (uint64_t)((int64_t)rec >> kDiagFoldBit);
+    return in_range ? dia_diag_from_bits(b) : 0.0;
+}
+
+// Encode row r of the ld rows the product computes: *field receives the residual, placed at bits 48-63.  False - the
+// fold is refused - when the residual does not fit a signed 16-bit field, when the decode does not give the stored
+// pattern back, or when a row of the padding (r >= n) holds anything but +0.0.
+KFSP_HD inline bool dia_diag_encode(const DiaDiagDev &G, const double *t, int64_t r, int64_t n, double stored, uint64_t *field)
+{
+    *field = 0;
+    if (r >= n) return dia_diag_bits(stored) == 0;
+    int x0, x1, x2;
+    dia_diag_digits(G, (uint32_t)r, x0, x1, x2);
+    const double p = dia_diag_predict(G, t, x0, x1, x2);
+    const int64_t resid = (int64_t)(dia_diag_bits(stored) - dia_diag_bits(p));
+    if (resid < -32768 || resid > 32767) return false;
+    *field = (uint64_t)resid << kDiagFoldBit;
+    return dia_diag_bits(dia_diag_value(p, *field, true)) == dia_diag_bits(stored);
+}
+
+}   // namespace kfsp

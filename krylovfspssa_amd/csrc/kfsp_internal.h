@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kfsp_dia_diag.h"
+
 #include <string>
 #include <vector>
 
@@ -90,7 +92,8 @@ struct DiaDev {
 // that the two rows a lane owns are adjacent and one 16-byte load (two for 16-byte records) fetches all their
 // codes.  The kernel keeps every dictionary in LDS and computes with dict[d][code]: the very doubles of the plain
 // streams, the same multiply-adds in the same order, bit-identical products.  DIAG stays an 8-byte stream (it has
-// about as many distinct values as rows).  One code width per matrix, chosen by dia_code_rule; a matrix that does not
+// about as many distinct values as rows) unless it is folded into bits 48-63 of the 8-byte records (DiaDiagDev,
+// kfsp_dia_diag.h: every reader of the codes masks them to W bits, so the spare bits are invisible to it).  One code width per matrix, chosen by dia_code_rule; a matrix that does not
 // fit keeps the plain kernel.  The plain streams stay resident (the transposed and the small-pass block products, every
 // block product without option block_dia_code, masked / halo / partitioned forms and kfsp_get_matrix read them): the
 // coded image costs 8 or 16 B per row on top.  The forward block product reads the coded image under option
@@ -178,6 +181,7 @@ struct SpmvArgs {
     SellDev A;
     DiaDev D;             // used instead of A by the banded kernels
     DiaCodeDev C;         // format 9: the coded values of D's diagonals
+    DiaDiagDev G;         // format 9: DIAG folded into the records' spare bits (kfsp_dia_diag.h); nk = 0: DIAG is D's stream
     BoxDev B;             // matrix-free box generator (format 3): the descriptor, by value (uniform kernel argument)
     const double *box_tab;   // ... and its factor tables (device memory, staged to LDS by the kernel)
     const BoxFast *box_fast; // format 4: the single-factor form of the same box (device memory)

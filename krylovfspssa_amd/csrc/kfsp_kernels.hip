@@ -308,9 +308,12 @@ __device__ __forceinline__ d2 coded_vals(const DiaCodeDev &C, const DiaCodes<REC
 
 // W > 0: the values come from the dictionaries (coded_vals) instead of from the 16-byte value streams; everything else - the
 // x pairs, the clamp, the order of the multiply-adds - is the same code, so the sums are the same bits.
-template <bool NT, bool MASKED, int W = 0, int REC = 8>
-__device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, const double *__restrict__ xg, int64_t row0,
-                                       int64_t c, int lane, unsigned m)
+// FOLD (W > 0, REC = 8): DIAG is not loaded either.  Its 64-bit pattern is that of the predictor - one table entry (LDS,
+// behind the dictionaries) per mixed-radix digit of the row index, added slowest digit first - plus the signed residual in
+// bits 48-63 of the row's record (kfsp_dia_diag.h; build_dia_code verified every row): the stored double, bit for bit.
+template <bool NT, bool MASKED, int W = 0, int REC = 8, bool FOLD = false>
+__device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, const DiaDiagDev &G, const double *__restrict__ xg,
+                                       int64_t row0, int64_t c, int lane, unsigned m)
 {
     const int64_t r = (c << 7) + 2 * lane;
     const int64_t g = row0 + r;
@@ -321,7 +324,21 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, con
     if (W) codes = ld_codes<NT, REC>(C, r);
     // m: which diagonals have entries in this group (same for the whole wavefront; the
     // caller fetched it one trip ahead, so no load sits in front of the address arithmetic)
-    const d2 dg = ld_stream2<NT>(D.diag + r);
+    d2 dg;
+    if (FOLD) {
+        // the digits of row g (< 2^31) by exact division with the uniform radices, those of row g + 1 by increment with carry
+        int a0, a1, a2;
+        // (rows of the padding take the digits of the last row: the division is exact below 2^31 only, and their value is +0.0)
+        const uint32_t gq = (uint32_t)g < (uint32_t)last ? (uint32_t)g : (uint32_t)last;
+        dia_diag_digits(G, gq, a0, a1, a2);
+        int b0 = a0, b1 = a1, b2 = a2;
+        dia_diag_next(G, b0, b1, b2);
+        const double *t = box_lds + G.base;
+        dg.x = dia_diag_value(dia_diag_predict(G, t, a0, a1, a2), codes.a[0], g <= last);
+        dg.y = dia_diag_value(dia_diag_predict(G, t, b0, b1, b2), codes.b[0], g < last);
+    } else {
+        dg = ld_stream2<NT>(D.diag + r);
+    }
     const xpair_t xd = ld_xpair(xg, g, last);
     d2 sum;
     sum.x = -dg.x * xd.x;
@@ -586,13 +603,15 @@ __device__ __forceinline__ d2 rows_box1(const BoxRegs<NS, PER> &R, const double 
 
 // FMT: 0 SELL-64, 1 banded, 2 banded with group masks, 3 matrix-free box (descriptor interpreted at run time),
 // 4 matrix-free box, single-factor fast path with NS species and NE entry slots per species, 5 SELL-64 with coded columns,
-// 9 banded with dictionary-coded values (NS = bits per code, NE = bytes per row record)
+// 9 banded with dictionary-coded values (NS = bits per code, NE = bytes per row record), 10 the same with DIAG folded into the
+// records' spare bits (8-byte records; kfsp_dia_diag.h)
 template <int MODE, bool NT, int FMT, int NS = 0, int NE = 0>
 __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
 {
     constexpr bool DIA = FMT != 0 && FMT != 5;
     constexpr bool BOX = FMT == 3 || FMT == 4;
-    constexpr bool CODED = FMT == 9;
+    constexpr bool CODED = FMT == 9 || FMT == 10;
+    constexpr bool FOLD = FMT == 10;
     constexpr int CW = CODED ? NS : 0, CREC = CODED && NE == 16 ? 16 : 8;
     __shared__ double red[12];
     const int lane = threadIdx.x & 63;
@@ -610,8 +629,24 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
     }
     if (CODED) {
         // the dictionaries of all diagonals, back to back (<= kDiaCodeLds bytes: 4 workgroups per CU)
-        const int nent = a.C.doff[a.D.nd];
-        for (int i = threadIdx.x; i < nent; i += kBlock) box_lds[i] = a.C.dict[i];
+        // ... and behind them (FOLD) the DIAG tables, which build_dia_code keeps behind the dictionaries in memory too
+        const int nent = a.C.doff[a.D.nd] + (FOLD ? a.G.ntab : 0);
+        // All loads of a pass are issued before its first store, 16 bytes per lane: 2048 entries - the whole image of
+        // the benchmark's generator - cost ONE trip to memory.  (One entry per lane and pass waited for every load
+        // before the next was issued: seven latencies in front of the first row of every workgroup.)
+        const int npair = nent >> 1;
+        const d2 *src = reinterpret_cast<const d2 *>(a.C.dict);     // (device buffers are 256-byte aligned)
+        d2 *dst = reinterpret_cast<d2 *>(box_lds);
+        for (int i0 = threadIdx.x; i0 < npair; i0 += 4 * kBlock) {
+            d2 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u * kBlock < npair) v[u] = src[i0 + u * kBlock];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u * kBlock < npair) dst[i0 + u * kBlock] = v[u];
+        }
+        if ((nent & 1) && threadIdx.x == 0) box_lds[nent - 1] = a.C.dict[nent - 1];
         __syncthreads();
     }
 
@@ -635,7 +670,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
     if (c < cend) {
         if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
         else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-        else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC>(a.D, a.C, a.xg, a.row0, ct, lane, gm);
+        else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
         else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
     }
@@ -696,7 +731,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
         if (c < cend) {
             if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
             else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-            else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC>(a.D, a.C, a.xg, a.row0, ct, lane, gm);
+            else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
             else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
         }
@@ -968,18 +1003,25 @@ static void launch_box_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStre
     else hipLaunchKernelGGL((k_spmv<3, false, FMT, NS, NE>), g, b, lds, st, a);
 }
 
-template <bool NT, int W, int REC>
+template <bool NT, int W, int REC, int FMT = 9>
 static void launch_coded_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, size_t lds)
 {
-    if (mode == 0) hipLaunchKernelGGL((k_spmv<0, NT, 9, W, REC>), g, b, lds, st, a);
-    else if (mode == 1) hipLaunchKernelGGL((k_spmv<1, NT, 9, W, REC>), g, b, lds, st, a);
-    else if (mode == 2) hipLaunchKernelGGL((k_spmv<2, NT, 9, W, REC>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((k_spmv<3, NT, 9, W, REC>), g, b, lds, st, a);
+    if (mode == 0) hipLaunchKernelGGL((k_spmv<0, NT, FMT, W, REC>), g, b, lds, st, a);
+    else if (mode == 1) hipLaunchKernelGGL((k_spmv<1, NT, FMT, W, REC>), g, b, lds, st, a);
+    else if (mode == 2) hipLaunchKernelGGL((k_spmv<2, NT, FMT, W, REC>), g, b, lds, st, a);
+    else hipLaunchKernelGGL((k_spmv<3, NT, FMT, W, REC>), g, b, lds, st, a);
 }
 
 template <bool NT>
 static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st)
 {
+    if (a.G.nk > 0 && a.C.rec_bytes == 8) {
+        // DIAG folded into the records: its tables sit behind the dictionaries, in memory and in LDS
+        const size_t lds = (size_t)(a.C.doff[a.D.nd] + a.G.ntab) * sizeof(double);
+        if (a.C.w == 8) launch_coded_mode<NT, 8, 8, 10>(mode, g, b, a, st, lds);
+        else launch_coded_mode<NT, 16, 8, 10>(mode, g, b, a, st, lds);
+        return;
+    }
     const size_t lds = (size_t)a.C.doff[a.D.nd] * sizeof(double);
     if (a.C.w == 8) {
         if (a.C.rec_bytes == 8) launch_coded_mode<NT, 8, 8>(mode, g, b, a, st, lds);
