@@ -192,12 +192,14 @@ int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes);
  *   v[4] chunks with coded columns, v[5] chunks, v[6] 64-bit code words, v[7] internal state order active */
 int kfsp_layout_info(const kfsp_ctx *ctx, int64_t *v);
 /* The dictionary-coded image of a banded generator's values (option "dia_code", kernel format 9 inside the library;
- * kfsp_layout_info keeps answering 1), v[24]:
+ * kfsp_layout_info keeps answering 1), v[25]:
  *   v[0] bits per code, 8 or 16 (0: no coded image is resident), v[1] bytes per row record (8 / 16), v[2] record bytes one
  *   product reads, v[3] bytes of all dictionaries, v[4] stored diagonals, v[5] microseconds the last build (or the attempt)
  *   took, v[6] 1 when the product kernel reads the coded image (unmasked, no communicator), v[7] bytes of the DIAG tables
  *   when DIAG is folded into bits 48-63 of the 8-byte records (option "dia_code_diag"), 0 while DIAG is an 8-byte stream,
- *   v[8 + d] distinct values of diagonal d (counting stops soon after 5120; 0: not counted).
+ *   v[8 + d] distinct values of diagonal d, d < 16 (counting stops soon after 5120; 0: not counted),
+ *   v[24] where the product takes the pairs of x of the -1 / +1 diagonals from: 2 the neighbour lanes (DIAG folded and option
+ *   "dia_code_lanes" on), 1 loads with DIAG folded, 0 no fold (loads).
  * A group context answers for its first rank. */
 int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v);
 /* dictionary of diagonal d of that image, ascending as unsigned 64-bit patterns: *count entries, copied to dict (cap entries
@@ -813,9 +815,14 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * difference of the two 64-bit patterns, so the product rebuilds the stored double bit for bit and reads no DIAG stream; taken
  * only when the diagonals' offsets are strides of at most three digits starting at 1, nd x code bits <= 48, n < 2^31, the
  * tables fit the LDS beside the dictionaries and EVERY row round-trips, otherwise the image stays what "dia_code" built;
- * -1: only generators that pass the size gate of "dia_code"'s own default, whether or not "dia_code" was forced; 0, default:
- * never - on the benchmark's generator the fold measured 8 % less time per product, which is inside three times the run-to-run
- * spread of the benchmark, so it is not made the default; 1 always try; read when the generator is set),
+ * -1, default: only generators that pass the size gate of "dia_code"'s own default, whether or not "dia_code" was forced - on
+ * the benchmark's generator 7 % less time per product, six times the run-to-run spread of the benchmark;
+ * 0 never; 1 always try; read when the generator is set),
+ * "dia_code_lanes" (the product of a generator folded that way takes the pairs of x of its -1 and +1 diagonals from the
+ * neighbour lanes' registers - a lane holds x of its two rows, so only the first word of lane 0 and the second of lane 63
+ * are loaded - in every 128-row group the clamp at the ends of x cannot touch; the same doubles, bit-identical products;
+ * 0, default: every pair is loaded - the lanes measured slower on the benchmark's generator; 1: the lanes;
+ * read at every launch; kfsp_dia_code_info v[24]),
  * "m_max" (largest Krylov dimension the basis is allocated for, default and maximum 100 = M_MAX of
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so

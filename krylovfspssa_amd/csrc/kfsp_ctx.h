@@ -379,8 +379,10 @@ struct kfsp_ctx {
     int32_t coords_ld = 0, coords_ns = 0;
     int64_t opt_sell_code = -1;            // dictionary-coded SELL columns: -1 auto (under the internal state order), 0 never, 1 always try
     int64_t opt_dia_code = -1;             // dictionary-coded banded values: -1 auto (generators beyond the Infinity Cache), 0 never, 1 always try
-    int64_t opt_dia_code_diag = 0;         // DIAG folded into the coded records' spare bits: -1 generators that pass dia_code's size gate, 0 never (default:
-                                           // the gain on c3 did not clear the margin asked of it), 1 always try
+    int64_t opt_dia_code_diag = -1;        // DIAG folded into the coded records' spare bits: -1 (default) generators that pass dia_code's size gate,
+                                           // 0 never, 1 always try
+    int64_t opt_dia_code_lanes = 0;        // 1: the folded product takes the +-1 neighbours of x from the neighbour lanes; 0 (default: the lanes
+                                           // measured 1.5-4 us slower on c3): it loads them like every other pair; read at every launch
     int64_t opt_box_store = 0;            // 1: kfsp_set_matrix_box writes the generator out as stored diagonals on the device (banded form)
     int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12);
                                           // 2: as 1, and every other box (or any under box_generic) through k_spmm_boxg

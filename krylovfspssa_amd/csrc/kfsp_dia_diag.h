@@ -175,4 +175,20 @@ KFSP_HD inline bool dia_diag_encode(const DiaDiagDev &G, const double *t, int64_
     return dia_diag_bits(dia_diag_value(p, *field, true)) == dia_diag_bits(stored);
 }
 
+// ---- the +-1 neighbours of x from the neighbour lanes instead of from memory (option dia_code_lanes; the folded kernel only) ----
+// The banded kernel reads x[p], x[p + 1] as one 16-byte pair (ld_xpair, kfsp_kernels.hip) with p clamped to [-1, last]:
+// the word in front of x and the one behind row `last` are guard words every device buffer carries.
+KFSP_HD inline int64_t dia_xpair_clamp(int64_t p, int64_t last) { return p < -1 ? -1 : (p > last ? last : p); }
+
+// A trip is the 128-row group from global row g0; lane l owns rows g0 + 2 l and g0 + 2 l + 1 and holds their pair
+// xd = (x[g0 + 2 l], x[g0 + 2 l + 1]).  The pair of the -1 diagonal, (x[g0 + 2 l - 1], x[g0 + 2 l]), is (lane l - 1's xd.y,
+// xd.x) and that of the +1 diagonal, (x[g0 + 2 l + 1], x[g0 + 2 l + 2]), is (xd.y, lane l + 1's xd.x); only lane 0's first
+// and lane 63's second word are held by no lane (dia_lanes_edge).  The trip may take them from the lanes when the clamp
+// acts on none of the three pairs of any lane: their indices p run over g0 - 1 ... g0 + 127, so g0 >= 0 and
+// g0 + 127 <= last = n - 1.  Every trip passes but the one that holds row `last` in front of rows of the padding: at most
+// one trip of a generator, none when n is a multiple of 128 (lane 63 of the last trip then reads the guard word x[n]).
+KFSP_HD inline bool dia_lanes_trip(int64_t g0, int64_t n) { return g0 >= 0 && g0 + 127 <= n - 1; }
+// the x index of the word lane 0 / lane 63 of such a trip reads on its own (the other lanes read none)
+KFSP_HD inline int64_t dia_lanes_edge(int64_t g0, int lane) { return lane == 0 ? g0 - 1 : g0 + 128; }
+
 }   // namespace kfsp

@@ -259,7 +259,7 @@ typedef double __attribute__((ext_vector_type(2))) xpair_t;
 typedef xpair_t __attribute__((aligned(8))) xpair_u;
 __device__ __forceinline__ xpair_t ld_xpair(const double *__restrict__ xg, int64_t p, int64_t last)
 {
-    p = p < -1 ? -1 : (p > last ? last : p);
+    p = dia_xpair_clamp(p, last);
     return *reinterpret_cast<const xpair_u *>(xg + p);
 }
 
@@ -306,12 +306,30 @@ __device__ __forceinline__ d2 coded_vals(const DiaCodeDev &C, const DiaCodes<REC
     return v;
 }
 
+// the x pair of the diagonal at offset delta: loaded, or (rows_dia, LANES) the pair xm / xp the trip took from its lanes
+template <bool LANES>
+__device__ __forceinline__ xpair_t dia_x(const double *__restrict__ xg, int64_t g, int delta, int64_t last, bool lanes,
+                                         const xpair_t &xm, const xpair_t &xp)
+{
+    if (LANES && lanes) {                                // (uniform: the trip and the descriptor sit in SGPRs)
+        if (delta == -1) return xm;
+        if (delta == 1) return xp;
+    }
+    return ld_xpair(xg, g + delta, last);
+}
+
 // W > 0: the values come from the dictionaries (coded_vals) instead of from the 16-byte value streams; everything else - the
 // x pairs, the clamp, the order of the multiply-adds - is the same code, so the sums are the same bits.
 // FOLD (W > 0, REC = 8): DIAG is not loaded either.  Its 64-bit pattern is that of the predictor - one table entry (LDS,
 // behind the dictionaries) per mixed-radix digit of the row index, added slowest digit first - plus the signed residual in
 // bits 48-63 of the row's record (kfsp_dia_diag.h; build_dia_code verified every row): the stored double, bit for bit.
-template <bool NT, bool MASKED, int W = 0, int REC = 8, bool FOLD = false>
+// LANES (with FOLD): the pairs of the -1 and +1 diagonals are not loaded where the trip allows it (dia_lanes_trip: the clamp
+// of ld_xpair acts on no lane): their four words are xd's own two and the neighbour lanes' - a whole-wavefront shift by one
+// lane in registers (DPP wave_shr:1 / wave_shl:1, no LDS traffic) - but for lane 0's x[g0 - 1] and lane 63's x[g0 + 128],
+// which ONE 8-byte load with only those two lanes active brings.  The same doubles from the same memory: the same bits.
+// A trip that dia_lanes_trip refuses keeps the loads.  (Measured slower than the loads on c3 and c3x: option dia_code_lanes
+// is off by default)
+template <bool NT, bool MASKED, int W = 0, int REC = 8, bool FOLD = false, bool LANES = false>
 __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, const DiaDiagDev &G, const double *__restrict__ xg,
                                        int64_t row0, int64_t c, int lane, unsigned m)
 {
@@ -340,6 +358,22 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, con
         dg = ld_stream2<NT>(D.diag + r);
     }
     const xpair_t xd = ld_xpair(xg, g, last);
+    xpair_t xm = {0.0, 0.0}, xp = {0.0, 0.0};            // the pairs of the -1 and of the +1 diagonal (read only under `lanes`)
+    bool lanes = false;
+    if (LANES) {
+        const int64_t g0 = row0 + (c << 7);
+        lanes = dia_lanes_trip(g0, D.n);
+        if (lanes) {
+            double edge = 0.0;
+            if (lane == 0 || lane == 63) edge = xg[dia_lanes_edge(g0, lane)];
+            const double below = dpp_get<0x138, 0xf, 0xf>(xd.y);    // wave_shr:1, lane l - 1's second word
+            const double above = dpp_get<0x130, 0xf, 0xf>(xd.x);    // wave_shl:1, lane l + 1's first word
+            xm.x = lane == 0 ? edge : below;
+            xm.y = xd.x;
+            xp.x = xd.y;
+            xp.y = lane == 63 ? edge : above;
+        }
+    }
     d2 sum;
     sum.x = -dg.x * xd.x;
     sum.y = -dg.y * xd.y;
@@ -349,8 +383,8 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, con
         // an empty segment costs no HBM traffic: zeros from a cached line, x from the row itself
         const d2 v0 = W ? coded_vals<(W ? W : 8), REC>(C, codes, d + 0) : ld_stream2<NT>(on0 ? vp + (int64_t)(d + 0) * D.ld : zp);
         const d2 v1 = W ? coded_vals<(W ? W : 8), REC>(C, codes, d + 1) : ld_stream2<NT>(on1 ? vp + (int64_t)(d + 1) * D.ld : zp);
-        const xpair_t x0 = ld_xpair(xg, g + (on0 ? D.delta[d + 0] : 0), last);
-        const xpair_t x1 = ld_xpair(xg, g + (on1 ? D.delta[d + 1] : 0), last);
+        const xpair_t x0 = dia_x<LANES>(xg, g, on0 ? D.delta[d + 0] : 0, last, lanes, xm, xp);
+        const xpair_t x1 = dia_x<LANES>(xg, g, on1 ? D.delta[d + 1] : 0, last, lanes, xm, xp);
         sum.x += v0.x * x0.x;
         sum.y += v0.y * x0.y;
         sum.x += v1.x * x1.x;
@@ -359,7 +393,7 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, con
     for (; d < D.nd; ++d) {
         const bool on0 = !MASKED || ((m >> d) & 1u);
         const d2 v0 = W ? coded_vals<(W ? W : 8), REC>(C, codes, d) : ld_stream2<NT>(on0 ? vp + (int64_t)d * D.ld : zp);
-        const xpair_t x0 = ld_xpair(xg, g + (on0 ? D.delta[d] : 0), last);
+        const xpair_t x0 = dia_x<LANES>(xg, g, on0 ? D.delta[d] : 0, last, lanes, xm, xp);
         sum.x += v0.x * x0.x;
         sum.y += v0.y * x0.y;
     }
@@ -604,8 +638,9 @@ __device__ __forceinline__ d2 rows_box1(const BoxRegs<NS, PER> &R, const double 
 // FMT: 0 SELL-64, 1 banded, 2 banded with group masks, 3 matrix-free box (descriptor interpreted at run time),
 // 4 matrix-free box, single-factor fast path with NS species and NE entry slots per species, 5 SELL-64 with coded columns,
 // 9 banded with dictionary-coded values (NS = bits per code, NE = bytes per row record), 10 the same with DIAG folded into the
-// records' spare bits (8-byte records; kfsp_dia_diag.h)
-template <int MODE, bool NT, int FMT, int NS = 0, int NE = 0>
+// records' spare bits (8-byte records; kfsp_dia_diag.h); LANES (format 10 only, option dia_code_lanes): its +-1 neighbours
+// of x from the neighbour lanes (rows_dia)
+template <int MODE, bool NT, int FMT, int NS = 0, int NE = 0, bool LANES = false>
 __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
 {
     constexpr bool DIA = FMT != 0 && FMT != 5;
@@ -670,7 +705,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
     if (c < cend) {
         if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
         else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-        else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
+        else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD, FOLD && LANES>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
         else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
     }
@@ -731,7 +766,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
         if (c < cend) {
             if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
             else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-            else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
+            else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD, FOLD && LANES>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
             else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
         }
@@ -1003,23 +1038,28 @@ static void launch_box_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStre
     else hipLaunchKernelGGL((k_spmv<3, false, FMT, NS, NE>), g, b, lds, st, a);
 }
 
-template <bool NT, int W, int REC, int FMT = 9>
+template <bool NT, int W, int REC, int FMT = 9, bool LANES = false>
 static void launch_coded_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, size_t lds)
 {
-    if (mode == 0) hipLaunchKernelGGL((k_spmv<0, NT, FMT, W, REC>), g, b, lds, st, a);
-    else if (mode == 1) hipLaunchKernelGGL((k_spmv<1, NT, FMT, W, REC>), g, b, lds, st, a);
-    else if (mode == 2) hipLaunchKernelGGL((k_spmv<2, NT, FMT, W, REC>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((k_spmv<3, NT, FMT, W, REC>), g, b, lds, st, a);
+    if (mode == 0) hipLaunchKernelGGL((k_spmv<0, NT, FMT, W, REC, LANES>), g, b, lds, st, a);
+    else if (mode == 1) hipLaunchKernelGGL((k_spmv<1, NT, FMT, W, REC, LANES>), g, b, lds, st, a);
+    else if (mode == 2) hipLaunchKernelGGL((k_spmv<2, NT, FMT, W, REC, LANES>), g, b, lds, st, a);
+    else hipLaunchKernelGGL((k_spmv<3, NT, FMT, W, REC, LANES>), g, b, lds, st, a);
 }
 
 template <bool NT>
-static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st)
+static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, bool lanes)
 {
     if (a.G.nk > 0 && a.C.rec_bytes == 8) {
         // DIAG folded into the records: its tables sit behind the dictionaries, in memory and in LDS
         const size_t lds = (size_t)(a.C.doff[a.D.nd] + a.G.ntab) * sizeof(double);
-        if (a.C.w == 8) launch_coded_mode<NT, 8, 8, 10>(mode, g, b, a, st, lds);
-        else launch_coded_mode<NT, 16, 8, 10>(mode, g, b, a, st, lds);
+        if (lanes) {
+            if (a.C.w == 8) launch_coded_mode<NT, 8, 8, 10, true>(mode, g, b, a, st, lds);
+            else launch_coded_mode<NT, 16, 8, 10, true>(mode, g, b, a, st, lds);
+        } else {
+            if (a.C.w == 8) launch_coded_mode<NT, 8, 8, 10>(mode, g, b, a, st, lds);
+            else launch_coded_mode<NT, 16, 8, 10>(mode, g, b, a, st, lds);
+        }
         return;
     }
     const size_t lds = (size_t)a.C.doff[a.D.nd] * sizeof(double);
@@ -1032,12 +1072,12 @@ static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_
     }
 }
 
-void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nt, int fmt, hipStream_t st, size_t lds_bytes)
+void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nt, int fmt, hipStream_t st, size_t lds_bytes, bool dia_lanes)
 {
     dim3 g(grid), b(kBlock);
     if (fmt == 9) {
-        if (nt) launch_coded<true>(mode, g, b, a, st);
-        else launch_coded<false>(mode, g, b, a, st);
+        if (nt) launch_coded<true>(mode, g, b, a, st, dia_lanes);
+        else launch_coded<false>(mode, g, b, a, st, dia_lanes);
         return;
     }
     if (fmt == 3) {

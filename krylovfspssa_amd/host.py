@@ -551,13 +551,16 @@ class KfspContext:
 
     def dia_code_info(self):
         """the dictionary-coded image of a banded generator's values (kfsp_dia_code_info).  "diag_table_bytes": bytes of the
-        DIAG tables when DIAG is folded into the records' spare bits (option "dia_code_diag": -1 where "dia_code"'s size
-        gate passes, 0 - the default - never, 1 always try), 0 while DIAG is read as an 8-byte stream"""
-        v = np.zeros(24, dtype=np.int64)
+        DIAG tables when DIAG is folded into the records' spare bits (option "dia_code_diag": -1 - the default - where
+        "dia_code"'s size gate passes, 0 never, 1 always try), 0 while DIAG is read as an 8-byte stream.  "neighbours": where the
+        product takes the pairs of x of the +-1 diagonals from - "lanes" (the neighbour lanes' registers: DIAG folded and
+        option "dia_code_lanes" = 1), "loads" (DIAG folded, "dia_code_lanes" = 0, the default) or "" (no fold: loads, as ever)"""
+        v = np.zeros(25, dtype=np.int64)
         self._chk(self._lib.kfsp_dia_code_info(self._h, _p(v)), "kfsp_dia_code_info")
         keys = ("width", "record_bytes", "coded_bytes", "dict_bytes", "diagonals", "build_us", "active", "diag_table_bytes")
         out = dict(zip(keys, (int(x) for x in v[:8])))
         out["distinct"] = [int(x) for x in v[8:8 + out["diagonals"]]]
+        out["neighbours"] = ("", "loads", "lanes")[int(v[24])]
         return out
 
     def dia_code_dict(self, d):
@@ -901,9 +904,12 @@ class KfspContext:
         2: every matrix-free box (0 and 1 keep their meaning: a multi-factor box is still refused under 1).
         "block_dia_code" = 1 (default 0, read at every block call): the forward block product reads the dictionary-coded image
         of a banded generator where the single-vector product does (option "dia_code"); every other case keeps its kernel.
-        "dia_code_diag" (-1: generators that pass "dia_code"'s size gate; 0, default: never; 1 always try; read when the generator
+        "dia_code_diag" (-1, default: generators that pass "dia_code"'s size gate; 0 never; 1 always try; read when the generator
         is set): DIAG of a coded banded generator is folded into bits 48-63 of its 8-byte records - the product reads no DIAG
-        stream and computes the same bits (dia_code_info()["diag_table_bytes"] > 0 says that it was taken)."""
+        stream and computes the same bits (dia_code_info()["diag_table_bytes"] > 0 says that it was taken).
+        "dia_code_lanes" (0, default / 1; read at every launch): 1, the folded product takes the pairs of x of its +-1 diagonals
+        from the neighbour lanes' registers instead of loading them (dia_code_info()["neighbours"]); the same bits, and on
+        the benchmark's generator slower than the loads."""
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
         if not hasattr(self, "_options"):
             self._options = {}
