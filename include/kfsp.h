@@ -192,14 +192,16 @@ int kfsp_matrix_bytes(const kfsp_ctx *ctx, int force_sell, int64_t *bytes);
  *   v[4] chunks with coded columns, v[5] chunks, v[6] 64-bit code words, v[7] internal state order active */
 int kfsp_layout_info(const kfsp_ctx *ctx, int64_t *v);
 /* The dictionary-coded image of a banded generator's values (option "dia_code", kernel format 9 inside the library;
- * kfsp_layout_info keeps answering 1), v[25]:
+ * kfsp_layout_info keeps answering 1), v[26]:
  *   v[0] bits per code, 8 or 16 (0: no coded image is resident), v[1] bytes per row record (8 / 16), v[2] record bytes one
  *   product reads, v[3] bytes of all dictionaries, v[4] stored diagonals, v[5] microseconds the last build (or the attempt)
  *   took, v[6] 1 when the product kernel reads the coded image (unmasked, no communicator), v[7] bytes of the DIAG tables
  *   when DIAG is folded into bits 48-63 of the 8-byte records (option "dia_code_diag"), 0 while DIAG is an 8-byte stream,
  *   v[8 + d] distinct values of diagonal d, d < 16 (counting stops soon after 5120; 0: not counted),
  *   v[24] where the product takes the pairs of x of the -1 / +1 diagonals from: 2 the neighbour lanes (DIAG folded and option
- *   "dia_code_lanes" on), 1 loads with DIAG folded, 0 no fold (loads).
+ *   "dia_code_lanes" on), 1 loads with DIAG folded, 0 no fold (loads),
+ *   v[25] 1 when the folded product runs its interior 128-row groups on the path without clamps (option "dia_code_inner" on,
+ *   v[24] = 1 and a diagonal count the path is built for: 6 with three digits, 4 with two), else 0.
  * A group context answers for its first rank. */
 int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v);
 /* dictionary of diagonal d of that image, ascending as unsigned 64-bit patterns: *count entries, copied to dict (cap entries
@@ -823,6 +825,12 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * are loaded - in every 128-row group the clamp at the ends of x cannot touch; the same doubles, bit-identical products;
  * 0, default: every pair is loaded - the lanes measured slower on the benchmark's generator; 1: the lanes;
  * read at every launch; kfsp_dia_code_info v[24]),
+ * "dia_code_inner" (the product of a generator folded that way with 6 diagonals on three strides or 4 on two runs every 128-row
+ * group whose pairs of x the clamp at the ends of x cannot touch and that holds no padding row through a body without per-lane
+ * 64-bit index arithmetic: addresses are a uniform base plus a 32-bit lane offset, the diagonal loop is unrolled and the loads
+ * go out in two rounds; the other groups and every other generator keep the present code; the same loads, look-ups and order
+ * of additions, bit-identical products; 1, default - on the benchmark's generator 1.7 us of 22.5 less per product in steady
+ * state - / 0; read at every launch; "dia_code_lanes" = 1 takes precedence; kfsp_dia_code_info v[25]),
  * "m_max" (largest Krylov dimension the basis is allocated for, default and maximum 100 = M_MAX of
  * KrylovSolver.f90:47; a smaller value saves 8 * rows bytes per column - 90 GB at 10^8 states - and makes kfsp_arnoldi refuse
  * a larger m; it takes effect when the NEXT generator is set - until then every bound follows the basis that is allocated, so

@@ -146,7 +146,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
             // near entries from an LDS window of x (single rank: x is readable exactly on [0, n))
             launch_spmv_boxlds(mode, g, a, st, ((bx.lds_bytes + 15) & ~(size_t)15) + 2 * (size_t)(512 + 2 * bx.reach) * sizeof(double), bx.reach);
             break;
-        default: launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes, ctx->opt_dia_code_lanes != 0);
+        default: launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes, ctx->opt_dia_code_lanes != 0, ctx->opt_dia_code_inner != 0);
         }
         if (p1) *p1 = Pending{P1, g};
         if (p2) *p2 = Pending{P2, g};
@@ -163,7 +163,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         a.trip_end = e;
         a.trip_split = split_at;
         a.trip_jump = jump;
-        launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes, ctx->opt_dia_code_lanes != 0);
+        launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes, ctx->opt_dia_code_lanes != 0, ctx->opt_dia_code_inner != 0);
         return g;
     };
     if (int rc = overlapped_product(ctx, ps, trips, src, 1, dflt_cap, launch_range, &used)) return rc;
@@ -941,6 +941,9 @@ int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v)
     for (int d = 0; d < kMaxDiag; ++d) v[8 + d] = ctx->use_dia && d < ctx->nd ? ctx->dia_distinct[d] : 0;
     // where the folded product takes the +-1 pairs of x from: 0 not folded (or not read by the product), 1 loads, 2 lanes
     v[8 + kMaxDiag] = v[6] && v[7] ? (ctx->opt_dia_code_lanes != 0 ? 2 : 1) : 0;
+    // 1 where the folded product runs interior trips through rows_dia_inner (launch_coded: option dia_code_inner on, the lanes
+    // off, a diagonal count with an instantiation), else 0
+    v[9 + kMaxDiag] = v[24] == 1 && ctx->opt_dia_code_inner != 0 && dia_inner_count(ctx->nd, ctx->dia_diag.nk, ctx->dia_code_w) != 0 ? 1 : 0;
     return 0;
 }
 
@@ -1978,6 +1981,7 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "dia_code") ctx->opt_dia_code = value;
     else if (k == "dia_code_diag") ctx->opt_dia_code_diag = value;
     else if (k == "dia_code_lanes") ctx->opt_dia_code_lanes = value;
+    else if (k == "dia_code_inner") ctx->opt_dia_code_inner = value;
     else if (k == "ssa_resident") ctx->opt_ssa_resident = value;
     else if (k == "keep_coords") ctx->opt_keep_coords = value;
     else if (k == "ssa_general") ctx->opt_ssa_general = value;

@@ -383,6 +383,9 @@ struct kfsp_ctx {
                                            // 0 never, 1 always try
     int64_t opt_dia_code_lanes = 0;        // 1: the folded product takes the +-1 neighbours of x from the neighbour lanes; 0 (default: the lanes
                                            // measured 1.5-4 us slower on c3): it loads them like every other pair; read at every launch
+    int64_t opt_dia_code_inner = 1;        // 1 (default): the folded product runs its interior trips (dia_inner_trip) through rows_dia_inner where
+                                           // the generator's diagonal count has an instantiation (dia_inner_count); 0: every trip runs rows_dia;
+                                           // read at every launch; dia_code_lanes = 1 takes precedence
     int64_t opt_box_store = 0;            // 1: kfsp_set_matrix_box writes the generator out as stored diagonals on the device (banded form)
     int64_t opt_block_box = 0;            // 1: the block path (kfsp_block.hip) takes a matrix-free box through k_spmm_box; 0: refuses it (-12);
                                           // 2: as 1, and every other box (or any under box_generic) through k_spmm_boxg

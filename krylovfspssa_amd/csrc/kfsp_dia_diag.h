@@ -191,4 +191,27 @@ KFSP_HD inline bool dia_lanes_trip(int64_t g0, int64_t n) { return g0 >= 0 && g0
 // the x index of the word lane 0 / lane 63 of such a trip reads on its own (the other lanes read none)
 KFSP_HD inline int64_t dia_lanes_edge(int64_t g0, int lane) { return lane == 0 ? g0 - 1 : g0 + 128; }
 
+// ---- interior trips of the folded kernel (option dia_code_inner; rows_dia_inner, kfsp_kernels.hip) ----
+// With dmin <= 0 <= dmax the smallest and the largest stored offset (0, the diagonal, included) the pair indices of a trip
+// run over g0 + dmin ... g0 + 126 + dmax.  The trip is interior when the clamp of ld_xpair changes none of them
+// (g0 + dmin >= -1 and g0 + 126 + dmax <= last) and no row belongs to the padding (g0 + 127 <= last): then gq == g in
+// every lane, both flags of dia_diag_value are true, and a lane's x pair of diagonal delta is the 16 bytes at byte offset
+// 16 l of the uniform address x + g0 + delta - no per-lane 64-bit index is needed.  (dmax >= 1 makes the second condition
+// follow from the third; it is kept because a generator may store no offset above 0.)
+KFSP_HD inline bool dia_inner_trip(int64_t g0, int64_t n, int64_t dmin, int64_t dmax)
+{
+    const int64_t last = n - 1;
+    return g0 + dmin >= -1 && g0 + 127 <= last && g0 + 126 + dmax <= last;
+}
+// The diagonal counts the interior body is instantiated for, by the folded generator's diagonals nd, digits nk and code
+// width w: 6 with three digits (three-species boxes), 4 with two (two-species), 8-bit codes; 0: no instantiation, the
+// generator keeps the present kernel.
+KFSP_HD inline int dia_inner_count(int nd, int nk, int w)
+{
+    if (w != 8) return 0;
+    return nd == 6 && nk == 3 ? 6 : (nd == 4 && nk == 2 ? 4 : 0);
+}
+// the index of the first word of lane l's pair of diagonal delta in such a trip: uniform base g0 + delta, lane part 2 l
+KFSP_HD inline int64_t dia_inner_base(int64_t g0, int64_t delta) { return g0 + delta; }
+
 }   // namespace kfsp

@@ -297,7 +297,9 @@ int launch_barnoldi_small(const SmallArnoldiArgs &a, const SmallBlockArgs &b, in
 // 4 matrix-free box, single-factor fast path, 5 SELL-64 with dictionary-coded columns, 9 banded with dictionary-coded
 // values (a.C; the dictionaries' LDS is sized by the launcher)
 // dia_lanes: format 9 with DIAG folded takes the +-1 neighbours of x from the neighbour lanes (option dia_code_lanes)
-void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nontemporal, int fmt, hipStream_t s, size_t lds_bytes = 0, bool dia_lanes = false);
+// dia_inner: ... runs its interior trips without clamps (option dia_code_inner; k_spmv_dia_inner where dia_inner_count admits the generator)
+void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nontemporal, int fmt, hipStream_t s, size_t lds_bytes = 0, bool dia_lanes = false,
+                 bool dia_inner = false);
 // format 6: the single-factor matrix-free product with the near part of x staged in LDS (reach rows on either side of a
 // workgroup's 512; lds_bytes = table image + two windows)
 void launch_spmv_boxlds(int mode, int grid, const SpmvArgs &a, hipStream_t s, size_t lds_bytes, int reach);

@@ -400,6 +400,77 @@ __device__ __forceinline__ d2 rows_dia(const DiaDev &D, const DiaCodeDev &C, con
     return sum;
 }
 
+// 16 bytes per lane at a uniform 64-bit address plus the lane's unsigned 32-bit byte offset (global_load_dwordx4 with a scalar
+// base: no per-lane 64-bit address arithmetic); 8-byte aligned in general
+template <typename T, bool NT>
+__device__ __forceinline__ T ld_lane16(const void *base, unsigned voff)
+{
+    const uint64_t b = reinterpret_cast<uint64_t>(base);
+    const global_bytes_t p = (global_bytes_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b) |
+                                              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32);
+    const __attribute__((address_space(1), aligned(8))) T *q = (const __attribute__((address_space(1), aligned(8))) T *)(p + voff);
+    return NT ? __builtin_nontemporal_load(q) : *q;
+}
+
+// The folded kernel's rows (W-bit codes, 8-byte records, FOLD) in an INTERIOR trip (dia_inner_trip, kfsp_dia_diag.h: the clamp
+// of ld_xpair acts on no lane's pair of any diagonal and no row belongs to the padding) of a generator with ND diagonals and
+// ND / 2 digits, both compile-time.  The same loads of the same words, the same table look-ups and the same order of
+// additions and multiply-adds as rows_dia - the same bits - with what an interior trip does not need taken out: every
+// address is a uniform 64-bit base plus the lane's 32-bit byte offset (no clamp, no per-lane 64-bit compare, select or
+// add) and the diagonal loop is unrolled (delta and doff stay in SGPRs, the codes are extracted with constant shifts).
+// The loads go out in TWO groups - the record, xd and the first half of the pairs, then, behind the first half's
+// multiply-adds, the second half: with all of them in flight at once the kernel is SLOWER than rows_dia (c3 23.6 against
+// 22.5 us, c3x 48.6 against 43.7), in two groups faster (20.8 / 38.2 us).
+template <bool NT, int W, int ND>
+__device__ __forceinline__ d2 rows_dia_inner(const DiaDev &D, const DiaCodeDev &C, const DiaDiagDev &G0, const double *__restrict__ xg,
+                                             int64_t row0, int64_t c, int lane)
+{
+    constexpr int NFIRST = ND / 2;
+    DiaDiagDev G = G0;
+    G.nk = ND / 2;                                       // (the dispatch admits ND diagonals with ND / 2 digits only)
+    const int64_t g0 = row0 + (c << 7);
+    // (the empty statement keeps the offset a 32-bit register of THIS trip: hoisted out of the trip loop as a 64-bit pair it
+    // would turn every load back into a per-lane 64-bit address)
+    unsigned voff = 16u * (unsigned)lane;
+    asm volatile("" : "+v"(voff));
+    const ull2 rec = ld_lane16<ull2, NT>(C.rec + (c << 7), voff);
+    DiaCodes<8> codes;
+    codes.a[0] = rec.x;
+    codes.b[0] = rec.y;
+    const xpair_t xd = ld_lane16<xpair_t, false>(xg + g0, voff);
+    xpair_t xs[ND];
+#pragma unroll
+    for (int d = 0; d < NFIRST; ++d) xs[d] = ld_lane16<xpair_t, false>(xg + dia_inner_base(g0, D.delta[d]), voff);
+    __builtin_amdgcn_sched_barrier(0);                   // (nothing moves across: the second group stays behind the first)
+    int a0, a1, a2;
+    dia_diag_digits(G, (uint32_t)g0 + 2u * (unsigned)lane, a0, a1, a2);
+    int b0 = a0, b1 = a1, b2 = a2;
+    dia_diag_next(G, b0, b1, b2);
+    const double *t = box_lds + G.base;
+    d2 dg;
+    dg.x = dia_diag_value(dia_diag_predict(G, t, a0, a1, a2), codes.a[0], true);
+    dg.y = dia_diag_value(dia_diag_predict(G, t, b0, b1, b2), codes.b[0], true);
+    d2 sum;
+    sum.x = -dg.x * xd.x;
+    sum.y = -dg.y * xd.y;
+#pragma unroll
+    for (int d = 0; d < NFIRST; ++d) {
+        const d2 v = coded_vals<W, 8>(C, codes, d);
+        sum.x += v.x * xs[d].x;
+        sum.y += v.y * xs[d].y;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = NFIRST; d < ND; ++d) xs[d] = ld_lane16<xpair_t, false>(xg + dia_inner_base(g0, D.delta[d]), voff);
+#pragma unroll
+    for (int d = NFIRST; d < ND; ++d) {
+        const d2 v = coded_vals<W, 8>(C, codes, d);
+        sum.x += v.x * xs[d].x;
+        sum.y += v.y * xs[d].y;
+    }
+    return sum;
+}
+
 // Matrix-free box generator, two consecutive rows per lane like the banded form.  The descriptor B
 // is a kernel argument (uniform: scalar loads), the factor tables sit in LDS, the coordinates of a
 // row in registers (NS compile-time for the benchmark models; species picked by select chains, a
@@ -640,8 +711,23 @@ __device__ __forceinline__ d2 rows_box1(const BoxRegs<NS, PER> &R, const double 
 // 9 banded with dictionary-coded values (NS = bits per code, NE = bytes per row record), 10 the same with DIAG folded into the
 // records' spare bits (8-byte records; kfsp_dia_diag.h); LANES (format 10 only, option dia_code_lanes): its +-1 neighbours
 // of x from the neighbour lanes (rows_dia)
-template <int MODE, bool NT, int FMT, int NS = 0, int NE = 0, bool LANES = false>
-__global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
+// INNER (format 10 without LANES, option dia_code_inner): the number of diagonals, 6 or 4, of a generator whose interior trips
+// (dia_inner_trip) run rows_dia_inner; 0: every trip runs rows_dia.  INNER kernels are held to the occupancy of the loaded
+// path (8 waves per SIMD, 7 with two fused dot products).
+template <bool NT, int FMT, int CW, int CREC, bool LANES, int INNER>
+__device__ __forceinline__ d2 rows_dia_trip(const DiaDev &D, const DiaCodeDev &C, const DiaDiagDev &G, const double *__restrict__ xg,
+                                            int64_t row0, int64_t ct, int lane, unsigned gm, int dmin, int dmax, const DiaDiagDev &Gi)
+{
+    constexpr bool FOLD = FMT == 10;
+    if constexpr (INNER != 0) {
+        // uniform: the trip, the row range and the offsets sit in SGPRs
+        if (dia_inner_trip(row0 + (ct << 7), D.n, dmin, dmax)) return rows_dia_inner<NT, CW, INNER>(D, C, Gi, xg, row0, ct, lane);
+    }
+    return rows_dia<NT, FMT == 2, CW, CREC, FOLD, FOLD && LANES>(D, C, G, xg, row0, ct, lane, gm);
+}
+
+template <int MODE, bool NT, int FMT, int NS = 0, int NE = 0, bool LANES = false, int INNER = 0>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(INNER ? (MODE == 3 ? 7 : 8) : 1, 8))) void k_spmv(SpmvArgs a)
 {
     constexpr bool DIA = FMT != 0 && FMT != 5;
     constexpr bool BOX = FMT == 3 || FMT == 4;
@@ -684,6 +770,20 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
         if ((nent & 1) && threadIdx.x == 0) box_lds[nent - 1] = a.C.dict[nent - 1];
         __syncthreads();
     }
+    int dmin = 0, dmax = 0;                               // INNER: the smallest and the largest stored offset, 0 included
+    DiaDiagDev Gi = DiaDiagDev{};                         // INNER: the fold's descriptor as rows_dia_inner reads it
+    if constexpr (INNER != 0) {
+        // (the empty statement hides that these are kernel arguments: they stay in SGPRs across the trip loop instead of being
+        // fetched again, with a wait, inside every trip)
+        Gi = a.G;
+        asm volatile("" : "+s"(Gi.magic[0]), "+s"(Gi.magic[1]), "+s"(Gi.shift[0]), "+s"(Gi.shift[1]), "+s"(Gi.size[0]), "+s"(Gi.size[1]),
+                          "+s"(Gi.size[2]), "+s"(Gi.toff[1]), "+s"(Gi.toff[2]), "+s"(Gi.base));
+#pragma unroll
+        for (int d = 0; d < INNER; ++d) {
+            dmin = min(dmin, a.D.delta[d]);
+            dmax = max(dmax, a.D.delta[d]);
+        }
+    }
 
     // SELL: one 64-row chunk per wavefront trip; DIA: one 128-row group
     const int xcd = blockIdx.x & 7;
@@ -705,7 +805,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
     if (c < cend) {
         if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
         else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-        else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD, FOLD && LANES>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
+        else if (DIA) sum = rows_dia_trip<NT, FMT, CW, CREC, LANES, INNER>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm, dmin, dmax, Gi);
         else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
     }
@@ -766,7 +866,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(SpmvArgs a)
         if (c < cend) {
             if (FMT == 4) sum = rows_box1<(NS ? NS : 1), (NE ? NE : 1)>(boxr, a.xg, a.row0, a.A.nrows, ct, lane);
             else if (BOX) sum = rows_box<0, 0>(a.B, tab, a.xg, a.row0, a.A.nrows, ct, lane);
-            else if (DIA) sum = rows_dia<NT, FMT == 2, CW, CREC, FOLD, FOLD && LANES>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm);
+            else if (DIA) sum = rows_dia_trip<NT, FMT, CW, CREC, LANES, INNER>(a.D, a.C, a.G, a.xg, a.row0, ct, lane, gm, dmin, dmax, Gi);
             else if (FMT == 5) sum.x = row_sell_coded<NT>(a.A, a.xg, a.row0, ct, lane);
             else sum.x = row_sell<NT>(a.A, a.xg, a.row0, ct, lane);
         }
@@ -1047,13 +1147,28 @@ static void launch_coded_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipSt
     else hipLaunchKernelGGL((k_spmv<3, NT, FMT, W, REC, LANES>), g, b, lds, st, a);
 }
 
+template <bool NT, int W, int ND>
+static void launch_inner_mode(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, size_t lds)
+{
+    if (mode == 0) hipLaunchKernelGGL((k_spmv<0, NT, 10, W, 8, false, ND>), g, b, lds, st, a);
+    else if (mode == 1) hipLaunchKernelGGL((k_spmv<1, NT, 10, W, 8, false, ND>), g, b, lds, st, a);
+    else if (mode == 2) hipLaunchKernelGGL((k_spmv<2, NT, 10, W, 8, false, ND>), g, b, lds, st, a);
+    else hipLaunchKernelGGL((k_spmv<3, NT, 10, W, 8, false, ND>), g, b, lds, st, a);
+}
+
 template <bool NT>
-static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, bool lanes)
+static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_t st, bool lanes, bool inner)
 {
     if (a.G.nk > 0 && a.C.rec_bytes == 8) {
         // DIAG folded into the records: its tables sit behind the dictionaries, in memory and in LDS
         const size_t lds = (size_t)(a.C.doff[a.D.nd] + a.G.ntab) * sizeof(double);
-        if (lanes) {
+        // (a fold with 4 or 6 diagonals has 8-bit codes: nd w <= 48, dia_diag_plan)
+        const int nd_inner = inner && !lanes ? dia_inner_count(a.D.nd, a.G.nk, a.C.w) : 0;
+        if (nd_inner == 6) {
+            launch_inner_mode<NT, 8, 6>(mode, g, b, a, st, lds);
+        } else if (nd_inner == 4) {
+            launch_inner_mode<NT, 8, 4>(mode, g, b, a, st, lds);
+        } else if (lanes) {
             if (a.C.w == 8) launch_coded_mode<NT, 8, 8, 10, true>(mode, g, b, a, st, lds);
             else launch_coded_mode<NT, 16, 8, 10, true>(mode, g, b, a, st, lds);
         } else {
@@ -1072,12 +1187,12 @@ static void launch_coded(int mode, dim3 g, dim3 b, const SpmvArgs &a, hipStream_
     }
 }
 
-void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nt, int fmt, hipStream_t st, size_t lds_bytes, bool dia_lanes)
+void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nt, int fmt, hipStream_t st, size_t lds_bytes, bool dia_lanes, bool dia_inner)
 {
     dim3 g(grid), b(kBlock);
     if (fmt == 9) {
-        if (nt) launch_coded<true>(mode, g, b, a, st, dia_lanes);
-        else launch_coded<false>(mode, g, b, a, st, dia_lanes);
+        if (nt) launch_coded<true>(mode, g, b, a, st, dia_lanes, dia_inner);
+        else launch_coded<false>(mode, g, b, a, st, dia_lanes, dia_inner);
         return;
     }
     if (fmt == 3) {

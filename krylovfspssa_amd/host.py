@@ -554,13 +554,16 @@ class KfspContext:
         DIAG tables when DIAG is folded into the records' spare bits (option "dia_code_diag": -1 - the default - where
         "dia_code"'s size gate passes, 0 never, 1 always try), 0 while DIAG is read as an 8-byte stream.  "neighbours": where the
         product takes the pairs of x of the +-1 diagonals from - "lanes" (the neighbour lanes' registers: DIAG folded and
-        option "dia_code_lanes" = 1), "loads" (DIAG folded, "dia_code_lanes" = 0, the default) or "" (no fold: loads, as ever)"""
-        v = np.zeros(25, dtype=np.int64)
+        option "dia_code_lanes" = 1), "loads" (DIAG folded, "dia_code_lanes" = 0, the default) or "" (no fold: loads, as ever).
+        "inner": 1 where the folded product runs its interior 128-row groups on the path without clamps (option
+        "dia_code_inner" = 1, "neighbours" = "loads", 6 diagonals on three strides or 4 on two), else 0"""
+        v = np.zeros(26, dtype=np.int64)
         self._chk(self._lib.kfsp_dia_code_info(self._h, _p(v)), "kfsp_dia_code_info")
         keys = ("width", "record_bytes", "coded_bytes", "dict_bytes", "diagonals", "build_us", "active", "diag_table_bytes")
         out = dict(zip(keys, (int(x) for x in v[:8])))
         out["distinct"] = [int(x) for x in v[8:8 + out["diagonals"]]]
         out["neighbours"] = ("", "loads", "lanes")[int(v[24])]
+        out["inner"] = int(v[25])
         return out
 
     def dia_code_dict(self, d):
@@ -909,7 +912,10 @@ class KfspContext:
         stream and computes the same bits (dia_code_info()["diag_table_bytes"] > 0 says that it was taken).
         "dia_code_lanes" (0, default / 1; read at every launch): 1, the folded product takes the pairs of x of its +-1 diagonals
         from the neighbour lanes' registers instead of loading them (dia_code_info()["neighbours"]); the same bits, and on
-        the benchmark's generator slower than the loads."""
+        the benchmark's generator slower than the loads.
+        "dia_code_inner" (1, default / 0; read at every launch): 1, the folded product of a generator with 6 diagonals on three
+        strides or 4 on two runs every 128-row group the ends of x cannot touch through a body without per-lane 64-bit index
+        arithmetic (dia_code_info()["inner"]); the same bits; "dia_code_lanes" = 1 takes precedence."""
         self._chk(self._lib.kfsp_set_option(self._h, name.encode(), int(value)), "kfsp_set_option")
         if not hasattr(self, "_options"):
             self._options = {}

@@ -5,7 +5,7 @@ warm-ups in a counter CSV belongs to the k-th case.  With --calib first 3 x k_st
 
     python3 profiles/pmc_target.py [--calib] [--no-time] case [case ...]
     case = workload:form   workload c3 | c3x | c4 | c5s | c5 | fsp (Goutsias ellipsoid, 1.0e7 states, search order)
-                           form     stored | stored_plain / stored_coded (stored with option dia_code = 0 / 1) | stored_stream / stored_fold / stored_fold_lanes (stored with option dia_code_diag = 0 / -1 / -1 and dia_code_lanes = 1) | mf (matrix-free: format 7 pencils where eligible, else format 4) | mf4 (format 4, ascending trips) | mf7 / mf8 (format 7 / format 8 forced) | mf6 / mf6r2 (matrix-free with x staged in LDS, reach 512 / 2: format 6) | sell (plain SELL-64) | coded (SELL-64, coded columns)
+                           form     stored | stored_plain / stored_coded (stored with option dia_code = 0 / 1) | stored_stream / stored_fold / stored_fold_lanes (stored with option dia_code_diag = 0 / -1 / -1 and dia_code_lanes = 1) | stored_fold_inner / stored_fold_present (stored_fold with option dia_code_inner = 1 / 0; the setting stays for the cases behind it) | mf (matrix-free: format 7 pencils where eligible, else format 4) | mf4 (format 4, ascending trips) | mf7 / mf8 (format 7 / format 8 forced) | mf6 / mf6r2 (matrix-free with x staged in LDS, reach 512 / 2: format 6) | sell (plain SELL-64) | coded (SELL-64, coded columns)
                                     | sell_search (plain SELL in the caller's search order; fsp only)
 Every case prints one line `CASE <case> n=<states> ms=<per launch> real_bytes=<kfsp_matrix_bytes> info=<layout>`;
 launch markers `MARK <case> <first launch index> 5` count the k_spmv<0,...> launches of this process."""
@@ -68,6 +68,9 @@ for case in cases:
     # neighbours of x from the neighbour lanes (dia_code_lanes = 1)
     ctx.set_option("dia_code_diag", 0 if form == "stored_stream" else -1)
     ctx.set_option("dia_code_lanes", 1 if form == "stored_fold_lanes" else 0)
+    if form in ("stored_fold_inner", "stored_fold_present"):
+        ctx.set_option("dia_code_inner", 1 if form == "stored_fold_inner" else 0)   # interior trips through rows_dia_inner / every trip through rows_dia
+        form = "stored"
     if form in ("stored_fold", "stored_fold_lanes", "stored_stream"):
         form = "stored"
     if form in ("stored_plain", "stored_coded"):
