@@ -86,7 +86,6 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     hipStream_t st = ctx->stream;
     ++ctx->prod_count;
     const bool dia = ctx->use_dia && !force_sell;
-    const bool nt = use_nt(ctx);
     const int64_t trips = product_trips(ctx->nchunks, dia);
     int64_t dflt_cap = 1024;   // the grid without option grid_blocks (product_grid)
     if (ctx->box.on && dia) {
@@ -102,6 +101,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
     // the kernel format: product_format (kfsp_host.h); under a communicator - every split product - one of 0 - 5 and 9
     const bool ordered = ctx->trip_order_n == trips && !force_sell;
     const int fmt = product_format(product_form(ctx, ordered, force_sell, force_plain_sell));
+    const ProductKernel pk{fmt, use_nt(ctx), ctx->box.lds_bytes, fmt == 9 ? dia_code_kernel(ctx) : DiaCodeKernel{}};
     const kfsp::BoxGeom &bx = ctx->box;
     const int64_t H = ctx->halo, L = ctx->L;
     const int64_t trip_rows = dia ? 128 : 64;
@@ -146,7 +146,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
             // near entries from an LDS window of x (single rank: x is readable exactly on [0, n))
             launch_spmv_boxlds(mode, g, a, st, ((bx.lds_bytes + 15) & ~(size_t)15) + 2 * (size_t)(512 + 2 * bx.reach) * sizeof(double), bx.reach);
             break;
-        default: launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes, ctx->opt_dia_code_lanes != 0, ctx->opt_dia_code_inner != 0);
+        default: launch_spmv(mode, g, a, pk, st);
         }
         if (p1) *p1 = Pending{P1, g};
         if (p2) *p2 = Pending{P2, g};
@@ -163,7 +163,7 @@ int run_product(kfsp_ctx *ctx, int mode, SpmvArgs a, const double *src, bool src
         a.trip_end = e;
         a.trip_split = split_at;
         a.trip_jump = jump;
-        launch_spmv(mode, g, a, nt, fmt, st, bx.lds_bytes, ctx->opt_dia_code_lanes != 0, ctx->opt_dia_code_inner != 0);
+        launch_spmv(mode, g, a, pk, st);
         return g;
     };
     if (int rc = overlapped_product(ctx, ps, trips, src, 1, dflt_cap, launch_range, &used)) return rc;
@@ -939,11 +939,11 @@ int kfsp_dia_code_info(const kfsp_ctx *ctx, int64_t *v)
     v[6] = dia_code_on(ctx) ? 1 : 0;
     v[7] = have && ctx->dia_diag.nk > 0 ? (int64_t)ctx->dia_diag.ntab * 8 : 0;
     for (int d = 0; d < kMaxDiag; ++d) v[8 + d] = ctx->use_dia && d < ctx->nd ? ctx->dia_distinct[d] : 0;
-    // where the folded product takes the +-1 pairs of x from: 0 not folded (or not read by the product), 1 loads, 2 lanes
-    v[8 + kMaxDiag] = v[6] && v[7] ? (ctx->opt_dia_code_lanes != 0 ? 2 : 1) : 0;
-    // 1 where the folded product runs interior trips through rows_dia_inner (launch_coded: option dia_code_inner on, the lanes
-    // off, a diagonal count with an instantiation), else 0
-    v[9 + kMaxDiag] = v[24] == 1 && ctx->opt_dia_code_inner != 0 && dia_inner_count(ctx->nd, ctx->dia_diag.nk, ctx->dia_code_w) != 0 ? 1 : 0;
+    // from the rule that launches the product's kernel: where the folded product takes the +-1 pairs of x from - 0 not folded
+    // (or not read by the product), 1 loads, 2 lanes - and 1 where it runs interior trips through rows_dia_inner, else 0
+    const DiaCodeKernel k = dia_code_on(ctx) ? dia_code_kernel(ctx) : DiaCodeKernel{};
+    v[8 + kMaxDiag] = k.info_neighbours();
+    v[9 + kMaxDiag] = k.info_inner();
     return 0;
 }
 

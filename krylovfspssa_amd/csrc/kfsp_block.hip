@@ -8,7 +8,7 @@
 //
 // SpMM.  One lane per row, kp accumulators in registers, the x of an entry read as kp/2 16-byte loads: the generator
 // streams are read once per block.  Column c of a row is summed in EXACTLY the order of the single-vector kernel
-// (kfsp_kernels.hip: row_sell, row_sell_coded, rows_dia): -DIAG x first (one v_mul_f64), then one fused multiply-add
+// (kfsp_spmv_dev.h: row_sell, row_sell_coded, rows_dia): -DIAG x first (one v_mul_f64), then one fused multiply-add
 // per entry in FMATVEC's order (KrylovSolver.f90:598-604).  The fused operations are written out below and the file
 // is compiled with contraction off, so no other fusion can creep in: column c of A X is bit-identical to kfsp_spmv of
 // column c (tests/test_gpu_block.py).  The banded rows take the operands the two-rows-per-lane kernel takes, clamp
@@ -21,7 +21,7 @@
 //
 // Matrix-free boxes (option block_box, k_spmm_box below; DESIGN.md 12, "Matrix-free boxes"): the row of a single-factor box is rebuilt
 // once - coordinates, {sum, valid} look-ups, one LDS read per entry - and applied to all kp columns, in the operation
-// order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_kernels.hip).
+// order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_spmv_dev.h, kfsp_spmv_box.hip).
 // Multi-factor boxes (option block_box = 2; DESIGN.md 12, "Multi-factor boxes"): every other matrix-free box, and any box
 // under box_generic = 1, takes the interpreted row of kernel format 3 - k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t
 // (kfsp_block_adj.hip), the row code in kfsp_boxg_dev.h; box_generic_path() and spmm_staged() below.  Values 0 and 1 of the
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm(SpmmArgs a)
 }
 
 // Row r0 + lane of a single-factor matrix-free box (BoxFast) applied to the kp columns of X.  Per column the operations of
-// rows_box1 (kfsp_kernels.hip) as its ISA has them: the accumulator starts at +0.0, ONE v_fma_f64 per entry slot in
+// rows_box1 (kfsp_spmv_dev.h) as its ISA has them: the accumulator starts at +0.0, ONE v_fma_f64 per entry slot in
 // species-then-slot order (the first one against the literal 0, so a leading 0.0 * x of either sign leaves +0.0), then
 // fma(-dsum, x_row, acc) with dsum the species' shares added in species order.  An invalid slot reads the 0.0 at the head
 // of the LDS image and the row's OWN row of X (the single-vector kernel may read a neighbour's element there: any finite

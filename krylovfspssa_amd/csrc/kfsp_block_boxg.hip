@@ -1,5 +1,5 @@
 // Several start vectors at once on ANY matrix-free box (option block_box = 2; include/kfsp.h, "several vectors at once";
-// DESIGN.md 12, "Multi-factor boxes"): Y = A X with the interpreted row of kernel format 3 (row_box, kfsp_kernels.hip) -
+// DESIGN.md 12, "Multi-factor boxes"): Y = A X with the interpreted row of kernel format 3 (row_box, kfsp_spmv_dev.h) -
 // propensities of up to three factors, any jump, up to 16 reactions on up to 8 species.  The row code and the kernel
 // body are kfsp_boxg_dev.h's, shared with the transposed product (k_spmm_boxg_t, kfsp_block_adj.hip); this file holds the
 // forward instantiations on their own, so that the register allocation of the kernels of kfsp_block.hip stays what it was.

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "kfsp_block.h"
+#include "kfsp_dispatch.h"
 #include "kfsp_internal.h"
 
 #include <type_traits>
@@ -14,8 +15,8 @@ namespace kfsp {
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef int i2 __attribute__((ext_vector_type(2)));
 
-// ---- from run-time widths and variants to kernel instantiations: the one place that spells the cases out (plain host
-// code: tests/block_dispatch_check.cpp)
+// ---- from run-time block widths to kernel instantiations (plain host code: tests/block_dispatch_check.cpp; the variants
+// every product shares - dispatch_bool, dispatch_box_inst, dispatch_diac - are in kfsp_dispatch.h)
 // log2(kp) - 1 for a block width kp in {2, 4, 8, 16}: the slot of the width in a table, and the shift from a 16-byte pair
 // of a block column to its row (pair i lies in row i >> kp_index(kp))
 constexpr int kp_index(int kp) { return kp == 2 ? 0 : (kp == 4 ? 1 : (kp == 8 ? 2 : 3)); }
@@ -32,12 +33,6 @@ decltype(auto) dispatch_kp(int kp, F &&f)
     }
 }
 
-template <class F>
-decltype(auto) dispatch_bool(bool on, F &&f)
-{
-    return on ? f(std::true_type{}) : f(std::false_type{});
-}
-
 // f(width, std::bool_constant<dots>): what nearly every product kernel is instantiated by
 template <class F>
 decltype(auto) dispatch_kp_dots(int kp, bool dots, F &&f)
@@ -45,36 +40,7 @@ decltype(auto) dispatch_kp_dots(int kp, bool dots, F &&f)
     return dispatch_kp(kp, [&](auto KP) { return dots ? f(KP, std::true_type{}) : f(KP, std::false_type{}); });
 }
 
-// f(species, slots per species) of the single-factor box instantiation; inst = species * 16 + slots per species
-// (BoxDev::pad, box_plan), anything else takes the widest one
-template <class F>
-decltype(auto) dispatch_box_inst(int inst, F &&f)
-{
-    using std::integral_constant;
-    switch (inst) {
-    case 2 * 16 + 2: return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
-    case 3 * 16 + 2: return f(integral_constant<int, 3>{}, integral_constant<int, 2>{});
-    case 6 * 16 + 2: return f(integral_constant<int, 6>{}, integral_constant<int, 2>{});
-    default: return f(integral_constant<int, 6>{}, integral_constant<int, 4>{});
-    }
-}
-
-// f(bits per code, bytes per record) of the coded banded block product (k_spmm_diac, kfsp_block_diac.hip) for the four
-// forms dia_code_rule can choose.  Anything else reaches NO instantiation: the answer is a value-initialised result (a null
-// kernel pointer), and the caller keeps the plain kernel.
-template <class F>
-auto dispatch_diac(int w, int rec, F &&f) -> decltype(f(std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{}))
-{
-    using std::integral_constant;
-    using R = decltype(f(integral_constant<int, 8>{}, integral_constant<int, 8>{}));
-    if (w == 8 && rec == 8) return f(integral_constant<int, 8>{}, integral_constant<int, 8>{});
-    if (w == 8 && rec == 16) return f(integral_constant<int, 8>{}, integral_constant<int, 16>{});
-    if (w == 16 && rec == 8) return f(integral_constant<int, 16>{}, integral_constant<int, 8>{});
-    if (w == 16 && rec == 16) return f(integral_constant<int, 16>{}, integral_constant<int, 16>{});
-    return R{};
-}
-
-// Where code d of a row lies in its record (DiaCodeDev, kfsp_internal.h; coded_vals, kfsp_kernels.hip): a 64-bit record
+// Where code d of a row lies in its record (DiaCodeDev, kfsp_internal.h; coded_vals, kfsp_spmv_dev.h): a 64-bit record
 // word holds 64 / w codes of w bits, diagonal d in word d / (64 / w) at bit w (d mod 64 / w).  Plain code: the kernel
 // and tests/block_dia_code_check.cpp read the same lines.
 constexpr int diac_word(int w, int d) { return d / (64 / w); }

@@ -26,7 +26,7 @@ constexpr int K = kBlockMaxK;
 typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
 
 // Banded row r from its record: ONE load of REC bytes brings every code of the row; code d lies where diac_word /
-// diac_shift say (coded_vals, kfsp_kernels.hip, decodes the same words) and the value is dict[doff[d] + code], from the
+// diac_shift say (coded_vals, kfsp_spmv_dev.h, decodes the same words) and the value is dict[doff[d] + code], from the
 // LDS image.  d is the loop counter: word index and shift are uniform.
 template <int KP, int W, int REC>
 __device__ __forceinline__ void row_diac_blk(const DiaDev &D, const DiaCodeDev &C, const double *__restrict__ X, int64_t r,

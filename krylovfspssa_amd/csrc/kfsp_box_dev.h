@@ -1,5 +1,5 @@
 // Device pieces of the single-factor matrix-free box product (BoxFast, kfsp_internal.h) that more than one
-// translation unit needs: the single-vector kernels (kfsp_kernels.hip) and the block product (kfsp_block.hip).
+// translation unit needs: the single-vector kernels (kfsp_spmv_dev.h, kfsp_spmv_box.hip) and the block product (kfsp_block.hip).
 #pragma once
 
 #include "kfsp_internal.h"

@@ -64,7 +64,7 @@ inline bool box_tile_force(int64_t tile, int64_t plane_rows) { return tile > 0 |
 struct BoxGeom {
     bool on = false;              // the resident generator is a matrix-free box
     bool fast = false;            // the single-factor form (BoxFast) sits behind the tables
-    // format 7 (pencils along the slowest species, kfsp_kernels.hip): eligible box, rows per plane, planes, base trips
+    // format 7 (pencils along the slowest species, kfsp_spmv_box.hip): eligible box, rows per plane, planes, base trips
     // (= ceil(rows per plane / 128)) and the length of their tiled order in d_pencil_order (0 entries: ascending)
     bool pencil = false, simple = false;
     int64_t plane_rows = 0, trips = 0, order_n = 0;
@@ -262,7 +262,7 @@ inline int box_plan(int32_t ns, const int32_t *dims, int32_t nr, const int32_t *
     B.ntab = (int32_t)nimage;
     std::memcpy(image.data() + nimage, &F, sizeof(F));
     G.fast = fast;
-    // Format 7 (pencils, kfsp_kernels.hip): the instantiation's species are the model's (no padding species), the slowest
+    // Format 7 (pencils, kfsp_spmv_box.hip): the instantiation's species are the model's (no padding species), the slowest
     // species' own entries reach exactly one plane (or are unused slots), no other entry moves the slowest species, planes
     // have an even number of rows (16-byte pairs), one rank, and there are enough base trips to fill the chip.
     if (fast && ns >= 3 && ns == ns_inst && opt.single) {

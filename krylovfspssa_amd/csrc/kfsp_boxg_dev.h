@@ -1,6 +1,6 @@
 // Device pieces of the GENERIC matrix-free block product (option block_box = 2; DESIGN.md 12, "Multi-factor boxes") that
 // its two translation units share: kfsp_block_boxg.hip (Y = A X, k_spmm_boxg) and kfsp_block_adj.hip (Y = A^T X,
-// k_spmm_boxg_t).  The row is the one of row_box (kfsp_kernels.hip, kernel format 3) in its run-time form - any box
+// k_spmm_boxg_t).  The row is the one of row_box (kfsp_spmv_dev.h, kernel format 3) in its run-time form - any box
 // kfsp_set_matrix_box takes: up to 8 species, 16 reactions, 3 factors per propensity, any jump - read from the descriptor
 // BoxDev (a uniform kernel argument: every index into it below is a compile-time constant after unrolling, so its fields
 // arrive by scalar loads) and from the factor tables staged in LDS (box_lds).  What a row costs in look-ups - coordinates,

@@ -1,5 +1,5 @@
 // Private: DIAG of a coded banded generator folded into the spare bits of its 8-byte row records (option dia_code_diag;
-// kernel format 9 with FOLD, kfsp_kernels.hip; build_dia_code, kfsp_build.hip).  DIAG is the sum of all
+// kernel format 10, kfsp_spmv_dev.h; build_dia_code, kfsp_build.hip).  DIAG is the sum of all
 // propensities at the row's state and every propensity depends on one species, so DIAG is - up to rounding - a sum of
 // one table entry per mixed-radix digit of the row index.  The record keeps, in bits 48-63, the signed difference
 // between the 64-bit pattern of the stored DIAG and that of the predictor, read as integers: pattern(P) + residual is
@@ -176,7 +176,7 @@ KFSP_HD inline bool dia_diag_encode(const DiaDiagDev &G, const double *t, int64_
 }
 
 // ---- the +-1 neighbours of x from the neighbour lanes instead of from memory (option dia_code_lanes; the folded kernel only) ----
-// The banded kernel reads x[p], x[p + 1] as one 16-byte pair (ld_xpair, kfsp_kernels.hip) with p clamped to [-1, last]:
+// The banded kernel reads x[p], x[p + 1] as one 16-byte pair (ld_xpair, kfsp_spmv_dev.h) with p clamped to [-1, last]:
 // the word in front of x and the one behind row `last` are guard words every device buffer carries.
 KFSP_HD inline int64_t dia_xpair_clamp(int64_t p, int64_t last) { return p < -1 ? -1 : (p > last ? last : p); }
 
@@ -191,7 +191,7 @@ KFSP_HD inline bool dia_lanes_trip(int64_t g0, int64_t n) { return g0 >= 0 && g0
 // the x index of the word lane 0 / lane 63 of such a trip reads on its own (the other lanes read none)
 KFSP_HD inline int64_t dia_lanes_edge(int64_t g0, int lane) { return lane == 0 ? g0 - 1 : g0 + 128; }
 
-// ---- interior trips of the folded kernel (option dia_code_inner; rows_dia_inner, kfsp_kernels.hip) ----
+// ---- interior trips of the folded kernel (option dia_code_inner; rows_dia_inner, kfsp_spmv_dev.h) ----
 // With dmin <= 0 <= dmax the smallest and the largest stored offset (0, the diagonal, included) the pair indices of a trip
 // run over g0 + dmin ... g0 + 126 + dmax.  The trip is interior when the clamp of ld_xpair changes none of them
 // (g0 + dmin >= -1 and g0 + 126 + dmax <= last) and no row belongs to the padding (g0 + 127 <= last): then gq == g in
@@ -213,5 +213,37 @@ KFSP_HD inline int dia_inner_count(int nd, int nk, int w)
 }
 // the index of the first word of lane l's pair of diagonal delta in such a trip: uniform base g0 + delta, lane part 2 l
 KFSP_HD inline int64_t dia_inner_base(int64_t g0, int64_t delta) { return g0 + delta; }
+
+// ---- which coded banded kernel a product runs: the one rule (the launch, kfsp_spmv_diac.hip, and kfsp_dia_code_info) ----
+// k_spmv's coded formats, NS = bits per code, NE = bytes per row record: 9 reads DIAG from its 8-byte stream; 10 has it
+// folded into the records' spare bits (above; 8-byte records only), its tables behind the dictionaries in memory and in LDS.
+// Format 10 has two variants, at most one at a time: LANES (option dia_code_lanes), the +-1 neighbours of x from the
+// neighbour lanes (dia_lanes_trip), and INNER (option dia_code_inner, not under LANES), the generator's diagonal count,
+// 6 or 4, where it has an instantiation (dia_inner_count): interior trips (dia_inner_trip) then run rows_dia_inner.
+struct DiaCodeKernel {
+    int fmt;             // 9 or 10
+    int w, rec;          // the instantiation's bits per code and bytes per record: 8 or 16 each
+    bool lanes;
+    int inner;           // 0 (every trip runs rows_dia), 4 or 6
+    int64_t lds_bytes;   // dynamic LDS: the dictionaries and, folded, the DIAG tables
+    // kfsp_dia_code_info: where the folded product takes the +-1 pairs of x from (0 not folded, 1 loads, 2 lanes), and 1
+    // where it runs interior trips through rows_dia_inner
+    int info_neighbours() const { return fmt == 10 ? (lanes ? 2 : 1) : 0; }
+    int info_inner() const { return inner != 0 ? 1 : 0; }
+};
+// nd diagonals with w-bit codes in records of rec_bytes; nk digits and ntab table entries of the fold (nk = 0: none);
+// doff_nd entries of all dictionaries.  A fold exists on 8-byte records only (dia_diag_plan refuses any other, and
+// build_dia_code stores no other DiaDiagDev), so `nk > 0` alone says as much as the test below.
+inline DiaCodeKernel dia_code_kernel(int nd, int w, int rec_bytes, int nk, int ntab, int doff_nd, bool opt_lanes, bool opt_inner)
+{
+    DiaCodeKernel k{9, w == 8 ? 8 : 16, rec_bytes == 8 ? 8 : 16, false, 0, (int64_t)doff_nd * 8};
+    if (nk > 0 && rec_bytes == 8) {
+        k.fmt = 10;
+        k.lds_bytes += (int64_t)ntab * 8;
+        k.lanes = opt_lanes;
+        k.inner = opt_inner && !opt_lanes ? dia_inner_count(nd, nk, w) : 0;   // (4 or 6 diagonals fold with 8-bit codes only)
+    }
+    return k;
+}
 
 }   // namespace kfsp

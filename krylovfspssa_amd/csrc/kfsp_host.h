@@ -162,6 +162,13 @@ inline void dia_code_args(const kfsp_ctx *c, DiaCodeDev &C)
     C.rec_bytes = c->dia_code_rec;
 }
 
+// the kernel a product on that image runs (dia_code_kernel, kfsp_dia_diag.h); meaningful where dia_code_on
+inline DiaCodeKernel dia_code_kernel(const kfsp_ctx *c)
+{
+    return dia_code_kernel(c->nd, c->dia_code_w, c->dia_code_rec, c->dia_diag.nk, c->dia_diag.ntab, c->dia_doff[c->nd],
+                           c->opt_dia_code_lanes != 0, c->opt_dia_code_inner != 0);
+}
+
 // Option block_dia_code: the forward block product takes the coded image (k_spmm_diac, kfsp_block_diac.hip) where the
 // single-vector product takes it (coded_on = dia_code_on), the option is on, the product is not the transposed one
 // (row r of A^T needs code d of row r - delta_d: nd record loads) and the pass is not the one-launch small one (its

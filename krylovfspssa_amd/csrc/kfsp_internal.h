@@ -1,5 +1,5 @@
 // Internal declarations shared by the host side (kfsp_api.cpp) and the gfx950
-// kernels (kfsp_kernels.hip) of libkfsp_hip.  Not part of the C ABI.
+// kernels (kfsp_kernels.hip and the other .hip files) of libkfsp_hip.  Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -292,21 +292,25 @@ struct SmallBlockArgs {
 int launch_barnoldi_small(const SmallArnoldiArgs &a, const SmallBlockArgs &b, int kp, bool dia, int64_t lds_limit, hipStream_t s,
                           int *fmt, size_t *lds);
 
-// kernel launchers (kfsp_kernels.hip)
-// fmt: 0 SELL-64, 1 banded, 2 banded with group masks, 3 matrix-free box (lds_bytes = size of the factor tables),
-// 4 matrix-free box, single-factor fast path, 5 SELL-64 with dictionary-coded columns, 9 banded with dictionary-coded
-// values (a.C; the dictionaries' LDS is sized by the launcher)
-// dia_lanes: format 9 with DIAG folded takes the +-1 neighbours of x from the neighbour lanes (option dia_code_lanes)
-// dia_inner: ... runs its interior trips without clamps (option dia_code_inner; k_spmv_dia_inner where dia_inner_count admits the generator)
-void launch_spmv(int mode, int grid, const SpmvArgs &a, bool nontemporal, int fmt, hipStream_t s, size_t lds_bytes = 0, bool dia_lanes = false,
-                 bool dia_inner = false);
+// kernel launchers (kfsp_kernels.hip; the coded banded product kfsp_spmv_diac.hip, formats 6 - 8 kfsp_spmv_box.hip)
+// Which k_spmv a product runs.  fmt (product_format, kfsp_host.h): 0 SELL-64, 1 banded, 2 banded with group masks,
+// 3 matrix-free box, 4 its single-factor fast path, 5 SELL-64 with dictionary-coded columns, 9 banded with dictionary-
+// coded values (a.C, a.G): the kernel - format 9 or 10 - and its LDS are `coded` (dia_code_kernel, kfsp_dia_diag.h)
+struct ProductKernel {
+    int fmt;
+    bool nt;              // nontemporal loads of the generator's streams
+    size_t lds_bytes;     // formats 3 and 4: the size of the factor tables
+    DiaCodeKernel coded;  // format 9 only
+};
+void launch_spmv(int mode, int grid, const SpmvArgs &a, const ProductKernel &k, hipStream_t s);
+void launch_spmv_coded(int mode, int grid, const SpmvArgs &a, bool nontemporal, const DiaCodeKernel &k, hipStream_t s);
 // format 6: the single-factor matrix-free product with the near part of x staged in LDS (reach rows on either side of a
 // workgroup's 512; lds_bytes = table image + two windows)
 void launch_spmv_boxlds(int mode, int grid, const SpmvArgs &a, hipStream_t s, size_t lds_bytes, int reach);
 // format 8: a workgroup's wavefronts walk the pencils of consecutive lines of the second-slowest species in step (k_spmv_slab)
 void launch_spmv_slab(int mode, int grid, int waves, const SpmvArgs &a, hipStream_t s, size_t lds_bytes, int64_t plane_rows, int planes,
                       int64_t line_rows, int lines, int groups, int64_t lo_trips, bool simple);
-// format 7: a wavefront walks the planes of the slowest species (kfsp_kernels.hip, k_spmv_pencil)
+// format 7: a wavefront walks the planes of the slowest species (k_spmv_pencil)
 void launch_spmv_pencil(int mode, int grid, const SpmvArgs &a, hipStream_t s, size_t lds_bytes, int64_t plane_rows, int planes,
                         int64_t base_trips, const int32_t *order, bool simple);
 void launch_ortho2(int grid, const Ortho2Args &a, hipStream_t s);
