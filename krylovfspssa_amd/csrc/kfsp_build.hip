@@ -550,38 +550,36 @@ int build_from_ell_device(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, cons
     return build_from_resident_ell(ctx, n, bw, ld);
 }
 
-// the gather form from the reference arrays that are ALREADY on the device (d_ell_adj / d_ell_off / d_ell_diag, n columns
-// of leading dimension ld): what build_from_ell_device does after its upload, and all kfsp_drop_rebuild needs
+// ---- the gather form from the reference arrays ALREADY on the device (build_from_ell_device after its upload, rebuild_resident).
+// The stages: relabel, scan, then the SELL stage (speculative), or the banded store, or the sell_sigma reorder and the SELL stage.
 bool state_order_check(kfsp_ctx *ctx);
 
-// speculate (a resident FSP being rebuilt, kfsp_expand_resident / kfsp_drop_rebuild): when the last generator built
-// here was SELL, assume this one is too and run scan, chunk widths, fill and row sort WITHOUT stopping for the link
-// statistics or the slot count - the entry arrays are reserved for the bound nact * bw (a row has at most one link per
-// reaction) - then wait once and check what the slow path would have looked at first: a bad link, the banded form the
-// slow path would have chosen, a state order packed under stale ranges (state_order_check).  kRedoBuild: not held.
-int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bool speculate)
+namespace {
+
+// the reference arrays as the transpose reads them: the caller's columns, or the set relabelled to the internal order
+struct EllSrc {
+    int32_t n, bw, ld;
+    const int32_t *adj;  const double *off, *diag;
+};
+
+// relabel: columns renumbered and reordered to the internal state order into the second set of arrays
+int ell_relabel(kfsp_ctx *ctx, EllSrc &E)
+{
+    const size_t nent = (size_t)E.n * (size_t)E.ld;
+    HIP_TRY(ctx->d_ell_adj2.reserve(nent, false));
+    HIP_TRY(ctx->d_ell_off2.reserve(nent, false));
+    HIP_TRY(ctx->d_ell_diag2.reserve((size_t)E.n, false));
+    hipLaunchKernelGGL(k_ell_relabel, dim3((int)(((int64_t)E.n * E.ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, (int64_t)E.n,
+                       (int)E.bw, (int)E.ld, ctx->d_perm.p, ctx->d_iperm.p, ctx->d_ell_adj.p, ctx->d_ell_off.p,
+                       ctx->d_ell_diag.p, ctx->d_ell_adj2.p, ctx->d_ell_off2.p, ctx->d_ell_diag2.p);
+    E = EllSrc{E.n, E.bw, E.ld, ctx->d_ell_adj2.p, ctx->d_ell_off2.p, ctx->d_ell_diag2.p};
+    return 0;
+}
+
+// scan: the length of every local row (d_cnt) and the link statistics (ScanOut in d_scan); nothing waits
+int ell_scan(kfsp_ctx *ctx, const EllSrc &E, int64_t nact)
 {
     hipStream_t st = ctx->stream;
-    const int64_t row0 = ctx->row0, nloc = ctx->nloc;
-    const int64_t nchunks = (nloc + kChunk - 1) / kChunk;
-    const int64_t nact = nchunks * kChunk;
-    const size_t nent = (size_t)n * (size_t)ld;
-    const int32_t *ell_adj = ctx->d_ell_adj.p;
-    const double *ell_off = ctx->d_ell_off.p, *ell_diag = ctx->d_ell_diag.p;
-    if (ctx->perm_on) {
-        // columns renumbered and reordered to the internal state order; the
-        // transpose below then never knows about the caller's order
-        HIP_TRY(ctx->d_ell_adj2.reserve(nent, false));
-        HIP_TRY(ctx->d_ell_off2.reserve(nent, false));
-        HIP_TRY(ctx->d_ell_diag2.reserve((size_t)n, false));
-        hipLaunchKernelGGL(k_ell_relabel, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
-                           (int)bw, (int)ld, ctx->d_perm.p, ctx->d_iperm.p, ctx->d_ell_adj.p, ctx->d_ell_off.p,
-                           ctx->d_ell_diag.p, ctx->d_ell_adj2.p, ctx->d_ell_off2.p, ctx->d_ell_diag2.p);
-        ell_adj = ctx->d_ell_adj2.p;
-        ell_off = ctx->d_ell_off2.p;
-        ell_diag = ctx->d_ell_diag2.p;
-    }
-
     HIP_TRY(ctx->d_cnt.reserve((size_t)std::max<int64_t>(nact, 64), false));
     HIP_TRY(ctx->d_scan.reserve(sizeof(ScanOut), false));
     HIP_TRY(hipMemsetAsync(ctx->d_cnt.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
@@ -590,21 +588,160 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
     static_assert(sizeof(ScanOut) <= 2048, "h_build layout");
     ScanOut &init = *reinterpret_cast<ScanOut *>(ctx->h_build + kHbStatsInit);
     if (!ctx->h_build_ready) {
+        init = ScanOut{};
         for (int j = 0; j < kMaxBw; ++j) {
             init.dmin[j] = INT_MAX;
             init.dmax[j] = INT_MIN;
-            init.dcount[j] = 0;
         }
-        init.nnz_off = 0;
-        init.bad = 0;
-        init.over = 0;
         ctx->h_build_ready = true;
     }
     HIP_TRY(hipMemcpyAsync(ctx->d_scan.p, &init, sizeof(init), hipMemcpyHostToDevice, st));
-    ScanOut *dscan = reinterpret_cast<ScanOut *>(ctx->d_scan.p);
-    const int gsrc = (int)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_ell_scan, dim3(std::min(gsrc, 1024)), dim3(kBlock), 0, st, (int64_t)n, (int)bw, (int)ld, ell_adj,
-                       row0, nloc, ctx->d_cnt.p, dscan);
+    const int gsrc = (int)((E.n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_ell_scan, dim3(std::min(gsrc, 1024)), dim3(kBlock), 0, st, (int64_t)E.n, (int)E.bw, (int)E.ld, E.adj,
+                       ctx->row0, ctx->nloc, ctx->d_cnt.p, reinterpret_cast<ScanOut *>(ctx->d_scan.p));
+    return 0;
+}
+
+// banded?  every used slot is ONE constant shift (dl: source - target and the slot, nd of them), and the diagonals are
+// full enough: banded_pays (kfsp_host.h), the rule the host build shares
+bool banded_form(const kfsp_ctx *ctx, const ScanOut &res, int bw, std::pair<int, int> *dl, int &nd)
+{
+    nd = 0;
+    for (int j = 0; j < bw; ++j) {
+        if (res.dmin[j] == INT_MAX) continue;              // slot never links
+        if (res.dmin[j] != res.dmax[j]) return false;
+        dl[nd++] = {-res.dmin[j], j};
+    }
+    return banded_pays(nd, ctx->nloc, (int64_t)res.nnz_off, ctx->opt_format);
+}
+
+// SELL-64 from the row lengths: chunk widths, their offsets, the slot count into *hslots, padding, fill, row sort.
+// !wait (speculative): the entry arrays are reserved for `capacity` up front and nothing waits - *hslots (pinned) is valid
+// behind the caller's one synchronisation, ScanOut::over says that the capacity did not hold.  wait (the slow build):
+// waits for the slot count and sizes the arrays by it.
+int sell_stage(kfsp_ctx *ctx, const EllSrc &E, bool wait, int64_t capacity, int64_t *hslots)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t row0 = ctx->row0, nloc = ctx->nloc, nchunks = ctx->nchunks, nact = nchunks * kChunk;
+    int *over = &reinterpret_cast<ScanOut *>(ctx->d_scan.p)->over;
+    auto reserve_entries = [&]() -> int {
+        HIP_TRY(ctx->d_col.reserve((size_t)std::max<int64_t>(capacity, 64), false));
+        HIP_TRY(ctx->d_val.reserve((size_t)std::max<int64_t>(capacity, 64), false));
+        HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
+        HIP_TRY(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
+        return 0;
+    };
+    HIP_TRY(ctx->d_off.reserve((size_t)nchunks + 1, false));
+    if (wait) {
+        HIP_TRY(hipMemsetAsync(ctx->d_off.p, 0, sizeof(int64_t), st));
+    } else if (int rc = reserve_entries())                 // (has rows: off[0] = 0 is k_scan_offsets' own first store)
+        return rc;
+    if (nchunks > 0) {
+        hipLaunchKernelGGL(k_chunk_width, dim3((int)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, nchunks, nloc,
+                           ctx->d_cnt.p, ctx->d_off.p);
+        hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_off.p);
+    }
+    HIP_TRY(hipMemcpyAsync(hslots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (wait) {
+        HIP_TRY(hipStreamSynchronize(st));
+        capacity = *hslots;
+        if (int rc = reserve_entries()) return rc;
+    }
+    if (nchunks > 0) {
+        // (a general generator may need more than the speculative bound: the flag sends such a build to the slow path)
+        hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0, ctx->d_off.p,
+                           capacity, ctx->d_col.p, ctx->d_val.p, E.diag, ctx->d_diag.p, over);
+        hipLaunchKernelGGL(k_sell_fill, dim3((int)(((int64_t)E.n * E.ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)E.n,
+                           (int)E.bw, (int)E.ld, E.adj, E.off, row0, nloc, ctx->d_off.p, capacity, ctx->d_ticket.p, ctx->d_col.p,
+                           ctx->d_val.p, over);
+        launch_sell_sort_rows(ctx, nloc, E.bw, capacity, st);
+    }
+    return 0;
+}
+
+// banded store: the nd diagonals of dl (sorted here) into d_dia, DIAG into d_diag; waits, then masks and codes
+int dia_stage(kfsp_ctx *ctx, const EllSrc &E, std::pair<int, int> *dl, int nd, int64_t nact2)
+{
+    hipStream_t st = ctx->stream;
+    std::sort(dl, dl + nd);
+    DiaDev D;
+    D.nd = nd;
+    int slot_of[kMaxDiag];
+    for (int d = 0; d < nd; ++d) {
+        D.delta[d] = dl[d].first;
+        slot_of[d] = dl[d].second;
+    }
+    D.ld = nact2;
+    D.n = E.n;
+    D.nchunks = ctx->nchunks;
+    D.val = nullptr;
+    D.diag = nullptr;
+    HIP_TRY(ctx->d_dia.reserve((size_t)nd * (size_t)nact2, false));
+    HIP_TRY(ctx->d_slot.reserve(kMaxDiag, false));
+    HIP_TRY(hipMemcpyAsync(ctx->d_slot.p, slot_of, sizeof(int) * (size_t)nd, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ell_to_dia, dim3((int)((nact2 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)E.n,
+                       (int)E.ld, E.adj, E.off, E.diag, ctx->row0, ctx->nloc, nd, D,
+                       ctx->d_slot.p, ctx->d_dia.p, ctx->d_diag.p);
+    HIP_TRY(hipStreamSynchronize(st));
+    ctx->nd = nd;
+    ctx->dia_ld = nact2;
+    for (int d = 0; d < nd; ++d) ctx->delta[d] = D.delta[d];
+    ctx->use_dia = true;
+    if (int rc = build_dia_mask(ctx)) return rc;
+    return build_dia_code(ctx);
+}
+
+// Option sell_sigma (off by default): inside windows of sigma rows of the internal order the longest rows come first (a
+// stable sort: a row moves by less than sigma positions).  On an SSA-grown Goutsias FSP of 10^6 states the chunks' padding
+// falls from 38 % of the entries to 20 / 11 / 5 / 3 % with sigma = 128 / 256 / 512 / 1024 - and the product takes 22.1 / 23.1 /
+// 24.1 / 25.7 us instead of 22.4: a chunk's rows are no longer neighbours, so every gather touches more lines of x.  perm /
+// iperm become the composed order, the reference arrays are relabelled once more; rows are summed in the caller's column order.
+int sell_sigma_order(kfsp_ctx *ctx, EllSrc &E)
+{
+    hipStream_t st = ctx->stream;
+    const int32_t n = E.n;
+    const int64_t nact = ctx->nchunks * kChunk;
+    const int sigma = (int)ctx->opt_sell_sigma;
+    ctx->order_n = 0;                                  // (d_perm is about to stop being the lexicographic order)
+    const int grid = (int)(((int64_t)n + kBlock - 1) / kBlock);
+    HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
+    unsigned long long *kin = ctx->d_keys.p, *kout = ctx->d_keys.p + n;     // (reserved by state_order_from_coords)
+    int32_t *ord = ctx->d_ticket.p;
+    hipLaunchKernelGGL(k_sigma_keys, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, sigma, ctx->d_cnt.p, kin, ctx->d_sortidx.p);
+    int bits = 8;
+    while ((1ull << bits) < ((unsigned long long)(n / sigma) + 1ull) * 128ull) ++bits;
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
+    HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
+    // perm'[i'] = perm[ord[i']] (internal -> caller), its inverse, the row lengths in the new order
+    hipLaunchKernelGGL(k_gather_i32, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ord, ctx->d_perm.p, ctx->d_iperm.p);
+    HIP_TRY(hipMemcpyAsync(ctx->d_perm.p, ctx->d_iperm.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_invert_perm, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ctx->d_perm.p, ctx->d_iperm.p);
+    hipLaunchKernelGGL(k_gather_i32, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ord, ctx->d_cnt.p, ctx->d_sortidx.p);
+    HIP_TRY(hipMemcpyAsync(ctx->d_cnt.p, ctx->d_sortidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return ell_relabel(ctx, E);
+}
+
+}  // namespace
+
+// speculate (a resident FSP being rebuilt, rebuild_resident): when the last generator built here was SELL, assume this
+// one is too and run scan, chunk widths, fill and row sort WITHOUT stopping for the link statistics or the slot count -
+// the entry arrays are reserved for the bound nact * bw (a row has at most one link per reaction) - then wait once and
+// check what the slow path would have looked at first: a bad link, the banded form the slow path would have chosen, a
+// state order packed under stale ranges (state_order_check).  kRedoBuild: not held.
+// The caller has reset what is resident (begin_generator); a build answered with kRedoBuild has set nothing but nchunks.
+int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bool speculate)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t nloc = ctx->nloc;
+    const int64_t nchunks = (nloc + kChunk - 1) / kChunk;
+    const int64_t nact = nchunks * kChunk;
+    EllSrc E{n, bw, ld, ctx->d_ell_adj.p, ctx->d_ell_off.p, ctx->d_ell_diag.p};
+    if (ctx->perm_on)
+        if (int rc = ell_relabel(ctx, E)) return rc;
+    if (int rc = ell_scan(ctx, E, nact)) return rc;
+    const ScanOut *dscan = reinterpret_cast<const ScanOut *>(ctx->d_scan.p);
     const bool spec = speculate && ctx->last_build_sell && ctx->h_build && nloc > 0 &&
                       !(ctx->perm_on && ctx->opt_sell_sigma >= 128) && (double)nact * (double)bw * 12.0 <= 16e9;
     ScanOut res_stack;
@@ -613,174 +750,37 @@ int build_from_resident_ell(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, bo
         HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (!state_order_check(ctx)) return kRedoBuild;
-        if (res.bad) {
-            ctx->err = "adj entry exceeds n";
-            return -5;
-        }
+        if (res.bad) return fail(ctx, -5, "adj entry exceeds n");
     }
     ctx->nchunks = nchunks;
     const int64_t nact2 = round_up(nact, 2 * kChunk);      // the banded kernel works on 128-row groups
     HIP_TRY(ctx->d_diag.reserve((size_t)std::max<int64_t>(nact2, 128), false));
     ctx->last_build_sell = false;
-
-    // banded?  every used slot is one constant shift, and the diagonals are full enough
-    auto banded_form = [&](std::pair<int, int> *dl, int &nd) {
-        nd = 0;
-        bool banded = ctx->opt_format != 1 && nloc > 0;
-        for (int j = 0; j < bw && banded; ++j) {
-            if (res.dmin[j] == INT_MAX) continue;              // slot never links
-            if (res.dmin[j] != res.dmax[j]) banded = false;
-            else dl[nd++] = {-res.dmin[j], j};
-        }
-        if (nd == 0 || nd > kMaxDiag) banded = false;
-        // (8 bytes per stored diagonal entry against 12 per SELL slot, cf. maybe_upload_dia)
-        if (banded && (double)nd * (double)nloc > 1.5 * (double)res.nnz_off + 1024.0) banded = false;
-        return banded;
-    };
-    if (spec) {
-        ctx->use_dia = false;
-        ctx->dia_masked = false;
-        ctx->dia_coded = false;
-        ctx->nd = 0;
-        ctx->have_sell = false;
-        ctx->sell_coded = false;
-        ctx->sell_reach = -1;
-        const int64_t bound = nact * (int64_t)bw;
-        HIP_TRY(ctx->d_off.reserve((size_t)nchunks + 1, false));
-        HIP_TRY(ctx->d_col.reserve((size_t)std::max<int64_t>(bound, 64), false));
-        HIP_TRY(ctx->d_val.reserve((size_t)std::max<int64_t>(bound, 64), false));
-        HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
-        // (off[0] = 0 is k_scan_offsets' own first store)
-        HIP_TRY(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_chunk_width, dim3((int)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, nchunks, nloc,
-                           ctx->d_cnt.p, ctx->d_off.p);
-        hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_off.p);
-        int64_t *hslots = reinterpret_cast<int64_t *>(ctx->h_build + kHbSlots);
-        HIP_TRY(hipMemcpyAsync(hslots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        // (bound holds for an FSP; a general generator has rows of any in-degree and may need more: nothing is stored
-        // beyond it, and the flag sends such a build to the slow path, which sizes the arrays by the slot count)
-        hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0, ctx->d_off.p,
-                           bound, ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p, &dscan->over);
-        hipLaunchKernelGGL(k_sell_fill, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
-                           (int)bw, (int)ld, ell_adj, ell_off, row0, nloc, ctx->d_off.p, bound, ctx->d_ticket.p, ctx->d_col.p,
-                           ctx->d_val.p, &dscan->over);
-        launch_sell_sort_rows(ctx, nloc, bw, bound, st);
-        HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        ++ctx->spec_builds;
-        if (!state_order_check(ctx)) return kRedoBuild;
-        if (res.bad) {
-            ctx->err = "adj entry exceeds n";
-            return -5;
-        }
-        if (res.over) return kRedoBuild;                      // (rows longer than the reactions allow: not an FSP's generator)
-        std::pair<int, int> dl[kMaxBw];
-        int nd = 0;
-        if (banded_form(dl, nd)) return kRedoBuild;           // (the slow path would store diagonals: let it)
-        ctx->nnz = nloc + (int64_t)res.nnz_off;
-        ctx->slots = *hslots;
-        ctx->have_sell = true;
-        ctx->last_build_sell = true;
-        return build_sell_code(ctx);
-    }
-    ctx->nnz = nloc + (int64_t)res.nnz_off;
     std::pair<int, int> dl[kMaxBw];                        // (source - target, slot)
     int nd = 0;
-    const bool banded = banded_form(dl, nd);
-
-    ctx->use_dia = false;
-    ctx->dia_masked = false;
-    ctx->dia_coded = false;
-    ctx->nd = 0;
-    ctx->have_sell = false;
-    ctx->sell_coded = false;
-    ctx->sell_reach = -1;
-    if (banded) {
-        std::sort(dl, dl + nd);
-        DiaDev D;
-        D.nd = nd;
-        int slot_of[kMaxDiag];
-        for (int d = 0; d < nd; ++d) {
-            D.delta[d] = dl[d].first;
-            slot_of[d] = dl[d].second;
+    int64_t slots_stack = 0;
+    int64_t *hslots = spec ? reinterpret_cast<int64_t *>(ctx->h_build + kHbSlots) : &slots_stack;
+    if (spec) {
+        if (int rc = sell_stage(ctx, E, false, nact * (int64_t)bw, hslots)) return rc;
+        HIP_TRY(hipMemcpyAsync(&res, dscan, sizeof(res), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));                 // the one wait of a speculative build
+        ++ctx->spec_builds;
+        if (!state_order_check(ctx)) return kRedoBuild;
+        if (res.bad) return fail(ctx, -5, "adj entry exceeds n");
+        if (res.over) return kRedoBuild;                      // (rows longer than the reactions allow: not an FSP's generator)
+        if (banded_form(ctx, res, bw, dl, nd)) return kRedoBuild;     // (the slow path would store diagonals: let it)
+    } else {
+        if (banded_form(ctx, res, bw, dl, nd)) {
+            ctx->nnz = nloc + (int64_t)res.nnz_off;
+            return dia_stage(ctx, E, dl, nd, nact2);
         }
-        D.ld = nact2;
-        D.n = n;
-        D.nchunks = nchunks;
-        D.val = nullptr;
-        D.diag = nullptr;
-        HIP_TRY(ctx->d_dia.reserve((size_t)nd * (size_t)nact2, false));
-        HIP_TRY(ctx->d_slot.reserve(kMaxDiag, false));
-        HIP_TRY(hipMemcpyAsync(ctx->d_slot.p, slot_of, sizeof(int) * (size_t)nd, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_ell_to_dia, dim3((int)((nact2 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
-                           (int)ld, ell_adj, ell_off, ell_diag, row0, nloc, nd, D,
-                           ctx->d_slot.p, ctx->d_dia.p, ctx->d_diag.p);
+        if (ctx->perm_on && ctx->opt_sell_sigma >= 128 && nloc == n && n > ctx->opt_sell_sigma)
+            if (int rc = sell_sigma_order(ctx, E)) return rc;
+        if (int rc = sell_stage(ctx, E, true, 0, hslots)) return rc;
         HIP_TRY(hipStreamSynchronize(st));
-        ctx->nd = nd;
-        ctx->dia_ld = nact2;
-        for (int d = 0; d < nd; ++d) ctx->delta[d] = D.delta[d];
-        ctx->use_dia = true;
-        ctx->slots = 0;
-        if (int rc = build_dia_mask(ctx)) return rc;
-        return build_dia_code(ctx);
     }
-
-    // SELL-64
-    if (ctx->perm_on && ctx->opt_sell_sigma >= 128 && nloc == n && n > ctx->opt_sell_sigma) {
-        // Option sell_sigma (off by default): inside windows of sigma rows of the internal order the longest
-        // rows come first (a stable sort: equal rows stay in lexicographic order, a row moves by less than
-        // sigma positions).  On an SSA-grown Goutsias FSP of 10^6 states the padding of the 64-row chunks
-        // falls from 38 % of the entries to 20 / 11 / 5 / 3 % with sigma = 128 / 256 / 512 / 1024 - and the
-        // product takes 22.1 / 23.1 / 24.1 / 25.7 us instead of 22.4: the 64 rows of a chunk are no longer
-        // neighbours, so every gather of a slot touches more lines of x, which costs more than the padded
-        // slots (own x, zeros) did.  perm / iperm are replaced by the composed order and the reference
-        // arrays relabelled once more; rows are still summed in the caller's column order.
-        const int sigma = (int)ctx->opt_sell_sigma;
-        ctx->order_n = 0;                                  // (d_perm is about to stop being the lexicographic order)
-        const int grid = (int)(((int64_t)n + kBlock - 1) / kBlock);
-        HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
-        unsigned long long *kin = ctx->d_keys.p, *kout = ctx->d_keys.p + n;     // (reserved by state_order_from_coords)
-        int32_t *ord = ctx->d_ticket.p;
-        hipLaunchKernelGGL(k_sigma_keys, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, sigma, ctx->d_cnt.p, kin, ctx->d_sortidx.p);
-        int bits = 8;
-        while ((1ull << bits) < ((unsigned long long)(n / sigma) + 1ull) * 128ull) ++bits;
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
-        HIP_TRY(ctx->d_sorttmp.reserve(tmp_bytes + 256, false));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->d_sorttmp.p, tmp_bytes, kin, kout, ctx->d_sortidx.p, ord, (int)n, 0, bits, st));
-        // perm'[i'] = perm[ord[i']] (internal -> caller), its inverse, the row lengths in the new order
-        hipLaunchKernelGGL(k_gather_i32, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ord, ctx->d_perm.p, ctx->d_iperm.p);
-        HIP_TRY(hipMemcpyAsync(ctx->d_perm.p, ctx->d_iperm.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_invert_perm, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ctx->d_perm.p, ctx->d_iperm.p);
-        hipLaunchKernelGGL(k_gather_i32, dim3(grid), dim3(kBlock), 0, st, (int64_t)n, ord, ctx->d_cnt.p, ctx->d_sortidx.p);
-        HIP_TRY(hipMemcpyAsync(ctx->d_cnt.p, ctx->d_sortidx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_ell_relabel, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n,
-                           (int)bw, (int)ld, ctx->d_perm.p, ctx->d_iperm.p, ctx->d_ell_adj.p, ctx->d_ell_off.p,
-                           ctx->d_ell_diag.p, ctx->d_ell_adj2.p, ctx->d_ell_off2.p, ctx->d_ell_diag2.p);
-    }
-    HIP_TRY(ctx->d_off.reserve((size_t)nchunks + 1, false));
-    HIP_TRY(hipMemsetAsync(ctx->d_off.p, 0, sizeof(int64_t), st));
-    if (nchunks > 0) {
-        hipLaunchKernelGGL(k_chunk_width, dim3((int)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, nchunks,
-                           nloc, ctx->d_cnt.p, ctx->d_off.p);
-        hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, st, nchunks, ctx->d_off.p);
-    }
-    int64_t slots = 0;
-    HIP_TRY(hipMemcpyAsync(&slots, ctx->d_off.p + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    ctx->slots = slots;
-    HIP_TRY(ctx->d_col.reserve((size_t)std::max<int64_t>(slots, 64), false));
-    HIP_TRY(ctx->d_val.reserve((size_t)std::max<int64_t>(slots, 64), false));
-    HIP_TRY(ctx->d_ticket.reserve((size_t)std::max<int64_t>(nact, 64), false));
-    HIP_TRY(hipMemsetAsync(ctx->d_ticket.p, 0, (size_t)std::max<int64_t>(nact, 64) * sizeof(int32_t), st));
-    if (nchunks > 0) {
-        hipLaunchKernelGGL(k_sell_init, dim3((int)((nchunks + 3) / 4)), dim3(kBlock), 0, st, nchunks, nloc, row0,
-                           ctx->d_off.p, slots, ctx->d_col.p, ctx->d_val.p, ell_diag, ctx->d_diag.p, &dscan->over);
-        hipLaunchKernelGGL(k_sell_fill, dim3((int)(((int64_t)n * ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (int64_t)n, (int)bw, (int)ld, ell_adj,
-                           ell_off, row0, nloc, ctx->d_off.p, slots, ctx->d_ticket.p, ctx->d_col.p, ctx->d_val.p, &dscan->over);
-        launch_sell_sort_rows(ctx, nloc, bw, slots, st);
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    ctx->nnz = nloc + (int64_t)res.nnz_off;
+    ctx->slots = *hslots;
     ctx->have_sell = true;
     ctx->last_build_sell = true;
     return build_sell_code(ctx);

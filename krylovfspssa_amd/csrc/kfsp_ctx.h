@@ -140,9 +140,37 @@ using kfsp::kMaxDiag;
 
 namespace kfsp {
 struct Group;
-}
 
-struct kfsp_ctx {
+// What is resident: the scalars that say what FORM of generator the buffers hold.  One definition, one reset (reset_generator,
+// from begin_generator of kfsp_generator.cpp on every path that replaces the generator).  Not here: buffers, options, and what
+// outlives a generator by design (ell_*, coords_*, order_n, kc_*, spec_*, last_build_sell, prod_*, w_pending*, dia_code_us).
+struct GeneratorState {
+    int64_t nchunks = 0, slots = 0, nnz = 0;
+    bool use_dia = false;            // banded (DIA) form, used instead of SELL when the rows allow it
+    int nd = 0;
+    int32_t delta[kMaxDiag] = {0};
+    int64_t dia_ld = 0;
+    bool have_sell = false;
+    bool sell_coded = false;         // dictionary-coded columns of the SELL image (build_sell_code)
+    int64_t code_words = 0;          // 64-bit code words stored (all chunks)
+    int64_t coded_chunks = 0;        // chunks that use them
+    int64_t coded_slots = 0;         // entries (incl. padding) of those chunks
+    int64_t coded_tab_bytes = 0;     // bytes of their offset tables, in 64-byte lines
+    int64_t sell_reach = -1;         // max |col - row| over the local SELL rows (-1: unknown)
+    bool dia_coded = false;          // dictionary-coded values of the banded image (build_dia_code)
+    int dia_code_w = 0, dia_code_rec = 0;          // bits per code, bytes per record
+    int32_t dia_doff[kMaxDiag + 1] = {0};
+    int64_t dia_distinct[kMaxDiag] = {0};          // distinct values per diagonal as far as they were counted
+    DiaDiagDev dia_diag{};                         // DIAG folded into the records (kfsp_dia_diag.h): nk = 0 when it is a stream; tables behind the dictionaries in d_ddict
+    bool dia_masked = false;         // empty (diagonal, 128-row group) segments are skipped (build_dia_mask)
+    int64_t dia_empty_segments = 0;
+    int64_t trip_order_n = 0;        // trips of the order in d_trip_order (kfsp_set_trip_order), 0: ascending order
+    BoxGeom box;                     // matrix-free box (kfsp_set_matrix_box): what box_plan decided (kfsp_box_plan.h); else all defaults
+};
+
+}  // namespace kfsp
+
+struct kfsp_ctx : kfsp::GeneratorState {
     // a head handle over a row partition driven by ONE host thread (kfsp_create_group, kfsp_group.cpp): no device
     // resources of its own; every entry point fans out to the ranks' contexts
     kfsp::Group *group = nullptr;
@@ -183,48 +211,24 @@ struct kfsp_ctx {
     DevBuf<int64_t> d_off;
     DevBuf<int32_t> d_col;
     DevBuf<double> d_val, d_diag;
-    int64_t nchunks = 0, slots = 0, nnz = 0;
-    // banded (DIA) form, used instead of SELL when the rows allow it
-    DevBuf<double> d_dia;
-    bool use_dia = false;
-    int nd = 0;
-    int32_t delta[kMaxDiag] = {0};
-    int64_t dia_ld = 0;
-    bool have_sell = false;
+    DevBuf<double> d_dia;   // the banded (DIA) form's value streams
     // dictionary-coded columns of the SELL image (kernel format 5; kfsp_internal.h kSellCode*)
     DevBuf<int32_t> d_dtab, d_dtlen;
     DevBuf<unsigned long long> d_code;
     DevBuf<int64_t> d_codeoff;
-    bool sell_coded = false;
-    int64_t code_words = 0;          // 64-bit code words stored (all chunks)
-    int64_t coded_chunks = 0;        // chunks that use them
-    int64_t coded_slots = 0;         // entries (incl. padding) of those chunks
-    int64_t coded_tab_bytes = 0;     // bytes of their offset tables, in 64-byte lines
-    int64_t sell_reach = -1;         // max |col - row| over the local SELL rows (-1: unknown)
     // dictionary-coded values of the banded image (kernel format 9; kfsp_internal.h DiaCodeDev, kfsp_build.hip build_dia_code).
     // Valid for the image in d_dia only: every path that writes d_dia ends in build_dia_code, which drops or rebuilds it.
     DevBuf<unsigned long long> d_dcode, d_dhash;   // the records; the build's tables
     DevBuf<double> d_ddict;
-    bool dia_coded = false;
-    int dia_code_w = 0, dia_code_rec = 0;          // bits per code, bytes per record
-    int32_t dia_doff[kMaxDiag + 1] = {0};
-    int64_t dia_distinct[kMaxDiag] = {0};          // distinct values per diagonal as far as they were counted
-    kfsp::DiaDiagDev dia_diag{};                         // DIAG folded into the records (kfsp_dia_diag.h): nk = 0 when it is a stream; tables behind the dictionaries in d_ddict
-    int64_t dia_code_us = 0;                       // what the last build_dia_code took
+    int64_t dia_code_us = 0;                       // what the last build_dia_code took (a time, not a form: outside GeneratorState)
     // which 128-row groups of which diagonals hold entries at all (used when enough are empty)
     DevBuf<uint32_t> d_gmask;
     DevBuf<double> d_zero;   // 128 zeros, the stand-in for an empty segment
-    bool dia_masked = false;
     // optional order of the product's wavefront trips (kfsp_set_trip_order / the box tiling): trips of the CURRENT generator
     DevBuf<int32_t> d_trip_order;
-    int64_t trip_order_n = 0;          // 0: ascending order
-    // matrix-free box generator (kfsp_set_matrix_box): what box_plan decided about it (kfsp_box_plan.h; the descriptor is
-    // passed as a kernel argument), the table image in device memory and the pencil kernel's base-trip order.  Every
-    // generator that is not a box clears `box` whole.
-    kfsp::BoxGeom box;
+    // matrix-free box generator (kfsp_set_matrix_box): the table image in device memory and the pencil kernel's base-trip order
     DevBuf<double> d_box;
     DevBuf<int32_t> d_pencil_order;
-    int64_t dia_empty_segments = 0;   // (diagonal, 128-row group) pairs without entries
     // device-side build from the reference layout (kfsp_build.hip)
     DevBuf<int32_t> d_ell_adj, d_cnt, d_ticket;
     // columns of OFFDIAG / DIAG resident from the last reference-layout upload (0: none that may be reused)
@@ -408,6 +412,7 @@ struct kfsp_ctx {
 };
 
 namespace kfsp {
+inline void reset_generator(kfsp_ctx *ctx) { static_cast<GeneratorState &>(*ctx) = {}; }   // THE reset of what is resident
 // group contexts (kfsp_group.cpp): what each entry point of include/kfsp.h does when it is handed a head
 void comm_abort(kfsp_ctx *ctx);      // kfsp_comm.cpp: release a rank blocked in a collective (called from the group's watchdog)
 int group_selftest(int nranks, int failing_rank, int hanging_rank, int work_ms, int hang_ms, int timeout_ms, int grace_ms,
@@ -534,8 +539,14 @@ int setup_exchange(kfsp_ctx *ctx);
 // internal state order and a communicator one all-gather each, so every rank calls them in the same order
 int upload_states(kfsp_ctx *ctx, const double *host, double *dev, int64_t count);
 int download_states(kfsp_ctx *ctx, const double *dev, double *host, int64_t count);
+// full vector in the caller's order (device, n entries) -> this rank's block of a w-like vector (kfsp_api.cpp)
+int scatter_from_full(kfsp_ctx *ctx, const double *full_caller, double *dev_local);
 // (re)size everything that depends on the number of states (kfsp_api.cpp)
 int resize(kfsp_ctx *ctx, int64_t n);
+// From "the reference arrays of an FSP of n states are resident" to "its generator is ready" (kfsp_generator.cpp).  n_prev: the
+// size the resident order was made for (> n after a drop, < n after an expansion); coords: the coordinates sit in d_coords.
+int rebuild_resident(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, int32_t ns, int32_t cld, int32_t n_prev, bool want_order,
+                     bool coords, std::chrono::steady_clock::time_point t0);
 // SSA walk + one-step sweep on the resident lists (kfsp_expand.hip)
 int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, int32_t nr, const int32_t *stoich,
                           int32_t max_count, int32_t cap, int64_t *n_out, int64_t *n_ssa);

@@ -133,6 +133,20 @@ inline int vec_grid(int64_t pairs, int64_t opt_vgrid)
     return (int)std::max<int64_t>(std::min<int64_t>(g, std::min<int64_t>(opt_vgrid > 0 ? opt_vgrid : 1024, kMaxGrid)), 1);
 }
 
+// ---- banded or SELL: the one rule, for the device build (build_from_resident_ell) and the host build (maybe_upload_dia)
+// A stored diagonal entry costs 8 bytes, zero or not, a SELL slot 12: banded moves fewer bytes while nd * rows <= 1.5 *
+// (off-diagonal entries) (+ 1024 of grace).  How nd is counted is each path's own: the device build counts the used reaction
+// slots, each ONE constant shift; the host build the distinct column offsets, up to kMaxDiag + 1 (tests/generator_rule_check.cpp).
+inline bool banded_pays(int nd, int64_t nloc, int64_t nnz_off, int64_t opt_format)
+{ return opt_format != 1 && nloc > 0 && nd > 0 && nd <= kMaxDiag && (double)nd * (double)nloc <= 1.5 * (double)nnz_off + 1024.0; }
+
+// ---- whether a generator of n states gets the internal state order: sorting, relabelling and the extra upload cost what ~20
+// products (at 10^6 states) save - worth it only while generators live that long; the one being replaced is the best predictor
+inline bool want_state_order(int64_t opt_state_order, int64_t n, int64_t min_n, int64_t products, int64_t min_products)
+{ return opt_state_order != 0 && n >= min_n && products >= min_products; }
+inline bool want_state_order(const kfsp_ctx *c, int64_t n)
+{ return want_state_order(c->opt_state_order, n, c->opt_state_order_min, c->prod_count, c->opt_state_order_products); }
+
 // the generator's stored images as the kernels take them
 inline void generator_args(const kfsp_ctx *c, SellDev &A, DiaDev &D)
 {
