@@ -683,7 +683,13 @@ int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *ws
  * partitioned context, a group head, a generator that did not code, A^T, the small pass) the call runs the kernel it
  * runs without the option and refuses nothing new.  While the option is on, every block product writes v[1] = 9 and
  * v[5] = the dynamic LDS bytes of its launch when the coded kernel ran, else v[1] = v[5] = 0; with the option off
- * kfsp_block_info is unchanged. */
+ * kfsp_block_info is unchanged.
+ * Option "block_dia_code_adjoint" = 1 (default 0; read by every block call; only with "block_dia_code" = 1): under option
+ * "adjoint" the TRANSPOSED block product of such a generator takes the coded image as well - entry d of row r of A^T from
+ * the record of row r - delta_d, one 8-byte record word per diagonal, the dictionaries in LDS; DIAG from its stream.
+ * Every column stays bit-identical to the plain transposed block product.  It is then v[1] = 9 with v[6] = 1 that names
+ * the kernel.  With 0 ("block_dia_code" = 1 and "adjoint" = 1 alone) the plain transposed kernel runs and v[1] = v[5] = 0,
+ * as before; masked or partitioned contexts and generators that did not code keep their kernel; nothing new is refused. */
 int kfsp_block_info(kfsp_ctx *ctx, int64_t v[8]);
 
 /* ---- lock-step diagnostics ---------------------------------------------- */
@@ -837,7 +843,7 @@ int kfsp_add_timer(kfsp_ctx *ctx, int phase, double ms);
  * raising it and calling kfsp_arnoldi with the larger m before a new generator returns -2; kfsp_dgexpv needs the default), "box_store" (1: kfsp_set_matrix_box stores the generator as diagonals), "block_box" (1: kfsp_set_block / kfsp_spmm / kfsp_expv_block
  * take a matrix-free single-factor box, see "several vectors at once"; 2: every matrix-free box - multi-factor propensities, any jump, and any box under box_generic = 1 - through the interpreted row of format 3; 0, default: they return -12 for it), "adjoint" (1: the block calls multiply with A^T, backward solves exp(tA^T) F; see "several vectors at once"), "block_clamp" (0: the block combine does not clamp at 0, wsum is the l1 norm), "block_integral" (1: kfsp_set_block keeps J, the time integral of the block,
  * beside it and every accepted step of kfsp_expv_block adds to it; 2: the same and kfsp_get_block answers with J; 0, default: nothing changes;
- * see TIME INTEGRALS under "several vectors at once"), "block_target" (call mode of the target-set protocol: 1 kfsp_set_block installs or clears a target set, 2 kfsp_block_info reports it, 3 kfsp_block_begin is the flux into it; 0, default: the calls as ever; see TARGET SETS under "several vectors at once"), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_dia_code" (1: the forward block product reads the coded image of a banded generator where kfsp_spmv does; 0, default: the value streams; see kfsp_block_info), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
+ * see TIME INTEGRALS under "several vectors at once"), "block_target" (call mode of the target-set protocol: 1 kfsp_set_block installs or clears a target set, 2 kfsp_block_info reports it, 3 kfsp_block_begin is the flux into it; 0, default: the calls as ever; see TARGET SETS under "several vectors at once"), "block_partition" (1: the block calls run under a row partition - communicator, loop-back rank, group head; 0, default: they return -12 there; see "several vectors at once"), "block_dia_code" (1: the forward block product reads the coded image of a banded generator where kfsp_spmv does; 0, default: the value streams; see kfsp_block_info), "block_dia_code_adjoint" (1: with "block_dia_code" = 1 the transposed block product under "adjoint" reads the coded image as well; 0, default: the value streams at shifted rows; see kfsp_block_info), "block_small" (1: a block step on a generator of at most 4096 rows is three one-workgroup-per-column launches,
  * see kfsp_block_arnoldi; 0, default: the multi-launch kernels at every size), "box_pencil" (-1, default: a matrix-free box whose slowest species is
  * coupled only through its own +-1 entries is multiplied PENCIL by PENCIL - a wavefront owns 128 rows of one plane of that species and
  * walks the planes, so that those entries' sources are the lane's own previous / next elements and everything that depends on the other

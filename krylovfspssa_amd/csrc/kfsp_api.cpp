@@ -1527,6 +1527,7 @@ int kfsp_set_option(kfsp_ctx *ctx, const char *name, int64_t value)
     else if (k == "block_box") ctx->opt_block_box = value;
     else if (k == "block_small") ctx->opt_block_small = value;
     else if (k == "block_dia_code") ctx->opt_block_dia_code = value != 0;
+    else if (k == "block_dia_code_adjoint") ctx->opt_block_dia_code_adjoint = value != 0;
     else if (k == "block_partition") ctx->opt_block_partition = value != 0;
     else if (k == "adjoint") ctx->opt_adjoint = value != 0;
     else if (k == "block_clamp") ctx->opt_block_clamp = value != 0;

@@ -61,7 +61,9 @@
 // product of a banded generator whose coded image the single-vector product reads (dia_code_on, kfsp_host.h) takes
 // k_spmm_diac (kfsp_block_diac.hip) - one record per row and the dictionaries in LDS instead of nd value streams, the
 // same bits - unless the call is a transposed one or the one-launch small pass (spmm_diac_for below).  Everything else
-// keeps its kernel; with the option at 0 no launch, byte or report changes.
+// keeps its kernel; with the option at 0 no launch, byte or report changes.  Option block_dia_code_adjoint = 1 beside it
+// (OPT-IN as well; DESIGN.md 12, "Coded banded generators, backward") gives the transposed product of such a generator to
+// k_spmm_diac_t (kfsp_block_diac_t.hip; spmm_diac_t_for below), the same bits as k_spmm_t; at 0 k_spmm_t runs as ever.
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
@@ -847,7 +849,7 @@ int box_reach_check(kfsp_ctx *c, int kp)
 // Returns the grid.
 size_t staged_lds(StagedFamily fam, size_t image_bytes, int kp)
 {
-    return fam == kStagedDiac ? image_bytes : std::max<size_t>(image_bytes, (size_t)4 * kp * sizeof(double));
+    return fam == kStagedDiac || fam == kStagedDiacT ? image_bytes : std::max<size_t>(image_bytes, (size_t)4 * kp * sizeof(double));
 }
 
 template <class... Args>
@@ -884,17 +886,33 @@ int spmm_staged(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
     return launch_staged(ctx, kStagedBoxT, kp, dots, a.trips, ctx->box.lds_bytes, spmm_box_t_kernel(kp, ctx->box.dev.pad, dots), a, b);
 }
 
+// The coded banded image is what the coded block kernels walk: records for every row a trip touches, all codes of a row
+// inside its record, the dictionaries within the LDS budget.
+bool diac_image_walkable(const kfsp_ctx *c, int64_t trips)
+{
+    const int w = c->dia_code_w, rec = c->dia_code_rec, nd = c->nd;
+    if (nd < 1 || nd > kMaxDiag || w < 1 || nd * w > rec * 8 || c->dia_ld < trips * 128) return false;
+    return c->dia_doff[nd] >= 1 && (int64_t)c->dia_doff[nd] * 8 <= kDiaCodeLds;
+}
+
 // Option block_dia_code: the kernel that reads the coded banded image for this call, or null - the rule of
-// block_dia_code_path (kfsp_host.h), a form dispatch_diac knows, and an image that is what the kernel walks: records for
-// every row a trip touches, all codes of a row inside its record, the dictionaries within the LDS budget.  Null: the
-// plain kernel runs, as it always has.  Read at every block call.
+// block_dia_code_path (kfsp_host.h), a form dispatch_diac knows, and an image the kernel can walk.  Null: the plain
+// kernel runs, as it always has.  Read at every block call.
 SpmmDiacFn spmm_diac_for(const kfsp_ctx *c, int kp, bool dots, int64_t trips)
 {
     if (!block_dia_code_path(dia_code_on(c), c->opt_block_dia_code, c->opt_adjoint != 0, small_path(c))) return nullptr;
-    const int w = c->dia_code_w, rec = c->dia_code_rec, nd = c->nd;
-    if (nd < 1 || nd > kMaxDiag || w < 1 || nd * w > rec * 8 || c->dia_ld < trips * 128) return nullptr;
-    if (c->dia_doff[nd] < 1 || (int64_t)c->dia_doff[nd] * 8 > kDiaCodeLds) return nullptr;
-    return spmm_diac_kernel(kp, w, rec, dots);
+    if (!diac_image_walkable(c, trips)) return nullptr;
+    return spmm_diac_kernel(kp, c->dia_code_w, c->dia_code_rec, dots);
+}
+
+// Option block_dia_code_adjoint: the same for the transposed product - the rule of block_dia_code_t_path (kfsp_host.h),
+// the same image guards (k_spmm_diac_t reads records of rows below n only; the bound on dia_ld holds all the more).
+// Null: k_spmm_t runs, as it always has.  Read at every block call.
+SpmmDiacFn spmm_diac_t_for(const kfsp_ctx *c, int kp, bool dots, int64_t trips)
+{
+    if (!block_dia_code_t_path(dia_code_on(c), c->opt_block_dia_code, c->opt_block_dia_code_adjoint, c->opt_adjoint != 0)) return nullptr;
+    if (!diac_image_walkable(c, trips)) return nullptr;
+    return spmm_diac_t_kernel(kp, c->dia_code_w, c->dia_code_rec, dots);
 }
 
 // The reference arrays in the order the device keeps its vectors: the relabelled copies under the internal state order.
@@ -948,8 +966,21 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
         *G = gs;
         return 0;
     }
+    // a coded banded kernel of either direction: the dictionaries staged, slots 1 and 5 say so
+    auto launch_coded = [&](StagedFamily fam, SpmmDiacFn coded) {
+        DiaCodeDev C;
+        dia_code_args(ctx, C);
+        const size_t image = (size_t)C.doff[ctx->nd] * sizeof(double);
+        *G = launch_staged(ctx, fam, kp, dots, a.trips, image, coded, a, C);
+        ctx->blk_info[1] = 9;
+        ctx->blk_info[5] = (int64_t)staged_lds(fam, image, kp);
+    };
     if (ctx->opt_adjoint) {
         if (ctx->use_dia) {
+            if (const SpmmDiacFn coded = spmm_diac_t_for(ctx, kp, dots, a.trips)) {
+                launch_coded(kStagedDiacT, coded);           // "fmt 9, adjoint 1": k_spmm_diac_t
+                return 0;
+            }
             hipLaunchKernelGGL(spmm_t_kernel(kp, dots), dim3(g), dim3(kBlock), 0, st, a);
             return 0;
         }
@@ -959,12 +990,7 @@ int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, co
         return 0;
     }
     if (const SpmmDiacFn coded = spmm_diac_for(ctx, kp, dots, a.trips)) {
-        DiaCodeDev C;
-        dia_code_args(ctx, C);
-        const size_t image = (size_t)C.doff[ctx->nd] * sizeof(double);
-        *G = launch_staged(ctx, kStagedDiac, kp, dots, a.trips, image, coded, a, C);
-        ctx->blk_info[1] = 9;
-        ctx->blk_info[5] = (int64_t)staged_lds(kStagedDiac, image, kp);
+        launch_coded(kStagedDiac, coded);
         return 0;
     }
     const SpmmFn kern = spmm_kernel(kp, spmm_fmt(ctx), dots, ctx->use_comm);

@@ -30,23 +30,7 @@ namespace {
 
 constexpr int K = kBlockMaxK;
 
-// what every kernel does with a finished row: store it, add it to the two dot products
-template <int KP, bool DOTS>
-__device__ __forceinline__ void finish_row(const SpmmArgs &a, int64_t r, const double (&s)[KP], double (&da)[KP], double (&db)[KP])
-{
-    st_row<KP>(a.Y, r, s);
-    if (DOTS && r < a.rows_red) {
-        double u[KP];
-        if (a.ua) {
-            ld_row<KP>(a.ua, r, u);
-#pragma unroll
-            for (int c = 0; c < KP; ++c) da[c] = __builtin_fma(u[c], s[c], da[c]);
-        }
-        ld_row<KP>(a.ub, r, u);
-#pragma unroll
-        for (int c = 0; c < KP; ++c) db[c] = __builtin_fma(u[c], s[c], db[c]);
-    }
-}
+// (finish_row - what every kernel does with a finished row - is kfsp_block_dev.h's: k_spmm_diac_t shares it)
 
 // Banded (formats 1 and 2; a masked context reads the stored zeros of its empty segments).  Row r of A^T gathers
 // A(r - delta_d, r) = val[d ld + r - delta_d]: the value streams at shifted rows.  No read of val or X leaves [0, n).

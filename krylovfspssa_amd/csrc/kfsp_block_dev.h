@@ -1,7 +1,8 @@
 // Private: what the translation units of the block product share - kfsp_block.hip (Y = A X and everything behind
 // the product), kfsp_block_adj.hip (Y = A^T X, option adjoint), kfsp_block_boxg.hip (Y = A X on any matrix-free box,
-// option block_box = 2) and kfsp_block_diac.hip (Y = A X from the coded banded image, option block_dia_code).  The row helpers, SpmmArgs and block_sum_cols are the ones kfsp_block.hip always had; the
-// descriptors at the end belong to the transposed product and to the generic matrix-free kernels.
+// option block_box = 2), kfsp_block_diac.hip (Y = A X from the coded banded image, option block_dia_code) and
+// kfsp_block_diac_t.hip (Y = A^T X from it, option block_dia_code_adjoint).  The row helpers, SpmmArgs and block_sum_cols
+// are the ones kfsp_block.hip always had; the descriptors at the end belong to the transposed product and to the generic matrix-free kernels.
 #pragma once
 
 #include "kfsp_block.h"
@@ -47,6 +48,24 @@ constexpr int diac_word(int w, int d) { return d / (64 / w); }
 constexpr int diac_shift(int w, int d) { return (d % (64 / w)) * w; }
 constexpr unsigned diac_mask(int w) { return (1u << w) - 1u; }
 constexpr unsigned diac_code(int w, unsigned long long word, int d) { return (unsigned)(word >> diac_shift(w, d)) & diac_mask(w); }
+
+// The transposed coded product (k_spmm_diac_t, kfsp_block_diac_t.hip): entry d of row r of A^T is A(r - delta_d, r), whose
+// code lies in the record of row r - delta_d.  ok: that source is a row of the generator.  row: the source, or r itself
+// when there is none - the row whose X the fma takes and whose record may be read (its code is discarded: the entry counts
+// as 0.0).  word: the index in DiaCodeDev::rec of the ONE 64-bit word of that record that holds code d (rec_bytes / 8 words
+// per record; a code never straddles words).  For 0 <= r < n neither index leaves the rows [0, n).  Plain code: the kernel
+// and tests/block_dia_code_adjoint_check.cpp read the same lines.
+struct DiacTSrc {
+    bool ok;
+    int64_t row, word;
+};
+constexpr DiacTSrc diac_t_src(int w, int rec_bytes, int64_t r, int64_t delta, int64_t n, int d)
+{
+    const int64_t src = r - delta;
+    const bool ok = src >= 0 && src < n;
+    const int64_t row = ok ? src : r;
+    return DiacTSrc{ok, row, (int64_t)(rec_bytes / 8) * row + diac_word(w, d)};
+}
 
 #if defined(__HIPCC__)
 template <int KP>
@@ -128,9 +147,27 @@ __device__ __forceinline__ void block_sum_cols(double (&v)[KP], double *red, dou
     }
     __syncthreads();
 }
+
+// what every transposed kernel does with a finished row: store it, add it to the two dot products
+template <int KP, bool DOTS>
+__device__ __forceinline__ void finish_row(const SpmmArgs &a, int64_t r, const double (&s)[KP], double (&da)[KP], double (&db)[KP])
+{
+    st_row<KP>(a.Y, r, s);
+    if (DOTS && r < a.rows_red) {
+        double u[KP];
+        if (a.ua) {
+            ld_row<KP>(a.ua, r, u);
+#pragma unroll
+            for (int c = 0; c < KP; ++c) da[c] = __builtin_fma(u[c], s[c], da[c]);
+        }
+        ld_row<KP>(a.ub, r, u);
+#pragma unroll
+        for (int c = 0; c < KP; ++c) db[c] = __builtin_fma(u[c], s[c], db[c]);
+    }
+}
 #endif
 
-// ---- the transposed product (kfsp_block_adj.hip)
+// ---- the transposed product (kfsp_block_adj.hip, kfsp_block_diac_t.hip)
 
 // The reference arrays ADJ / OFFDIAG / DIAG as they stay on the device (kfsp_build.hip), in the order the device keeps
 // its vectors: column c holds the reactions that LEAVE state c - the gather row c of A^T.
@@ -249,6 +286,7 @@ typedef void (*SpmmBoxgFn)(BoxgArgs);
 typedef void (*SpmmDiacFn)(SpmmArgs, DiaCodeDev);
 #define KFSP_LOCAL __attribute__((visibility("hidden")))
 KFSP_LOCAL SpmmDiacFn spmm_diac_kernel(int kp, int w, int rec, bool dots);   // k_spmm_diac (kfsp_block_diac.hip); null: no such form
+KFSP_LOCAL SpmmDiacFn spmm_diac_t_kernel(int kp, int w, int rec, bool dots); // k_spmm_diac_t (kfsp_block_diac_t.hip); null: no such form
 KFSP_LOCAL SpmmFn spmm_t_kernel(int kp, bool dots);                    // k_spmm_t (kfsp_block_adj.hip)
 KFSP_LOCAL SpmmEllTFn spmm_ell_t_kernel(int kp, bool dots);            // k_spmm_ell_t
 KFSP_LOCAL SpmmBoxTFn spmm_box_t_kernel(int kp, int inst, bool dots);  // k_spmm_box_t
@@ -257,7 +295,8 @@ KFSP_LOCAL SpmmBoxgFn spmm_boxg_kernel(int kp, bool dots);             // k_spmm
 #undef KFSP_LOCAL
 
 // the kernel families that stage an image into dynamic LDS - the table image of a matrix-free box, or the dictionaries
-// of the coded banded form (option block_dia_code): first index of the occupancy cache (kfsp_ctx::blk_staged_occ)
-enum StagedFamily { kStagedBox = 0, kStagedBoxT = 1, kStagedBoxg = 2, kStagedBoxgT = 3, kStagedDiac = 4, kStagedFamilies = 5 };
+// of the coded banded form (options block_dia_code, block_dia_code_adjoint): first index of the occupancy cache
+// (kfsp_ctx::blk_staged_occ)
+enum StagedFamily { kStagedBox = 0, kStagedBoxT = 1, kStagedBoxg = 2, kStagedBoxgT = 3, kStagedDiac = 4, kStagedDiacT = 5, kStagedFamilies = 6 };
 
 }  // namespace kfsp

@@ -322,7 +322,7 @@ struct kfsp_ctx : kfsp::GeneratorState {
     int bv_kp = 0;               // width d_bv is laid out for
     int blk_begin_m = 0;         // Krylov dimension the last block_begin laid the basis out for (0: none since kfsp_set_block)
     int64_t blk_info[8] = {};    // kfsp_block_info: how the last block_begin / block_arnoldi / block_combine ran
-    int blk_staged_occ[5][4][2] = {};   // workgroups resident per CU of the kernels that stage an image into LDS (a box's tables,
+    int blk_staged_occ[6][4][2] = {};   // workgroups resident per CU of the kernels that stage an image into LDS (a box's tables,
                                         // the dictionaries of the coded banded form), by [StagedFamily][kp_index(kp)][dots]
                                         // (kfsp_block_dev.h; 0: not asked yet)
     DevBuf<double> d_bint, d_bcj;   // option block_integral: J, the time integral of the resident block (laid out like d_blk), and
@@ -395,6 +395,8 @@ struct kfsp_ctx : kfsp::GeneratorState {
                                           // 2: as 1, and every other box (or any under box_generic) through k_spmm_boxg
     int64_t opt_block_dia_code = 0;       // 1: the forward block product reads the coded banded image where the single-vector product does
                                           // (k_spmm_diac, kfsp_block_diac.hip; block_dia_code_path, kfsp_host.h); 0: the plain value streams
+    int64_t opt_block_dia_code_adjoint = 0;   // 1: with block_dia_code = 1, the TRANSPOSED block product reads the coded image as well
+                                          // (k_spmm_diac_t, kfsp_block_diac_t.hip; block_dia_code_t_path, kfsp_host.h); 0: k_spmm_t
     int64_t opt_block_small = 0;          // 1: the block path takes its one-launch kernels where the single-vector path takes k_arnoldi_small
     int64_t opt_adjoint = 0;              // 1: the block calls multiply with A^T (kfsp_block_adj.hip): backward solves exp(tA^T) F
     int64_t opt_block_partition = 0;      // 1: the block calls run under a row partition (communicator, loop-back rank, group head); 0: -12

@@ -193,6 +193,16 @@ inline bool block_dia_code_path(bool coded_on, int64_t opt_block_dia_code, bool 
     return coded_on && opt_block_dia_code != 0 && !adjoint && !small;
 }
 
+// Option block_dia_code_adjoint: beside block_dia_code, the TRANSPOSED block product takes the coded image as well
+// (k_spmm_diac_t, kfsp_block_diac_t.hip: one 8-byte record word per diagonal from the source rows' records, which the
+// neighbouring rows have just fetched, instead of nd value streams).  OPT-IN on top of the opt-in: block_dia_code = 1 with
+// adjoint = 1 alone keeps k_spmm_t.  The one-launch small pass is never taken under adjoint (small_path), so it does not
+// enter the rule.  Plain flags (tests/block_dia_code_adjoint_check.cpp).
+inline bool block_dia_code_t_path(bool coded_on, int64_t opt_block_dia_code, int64_t opt_block_dia_code_adjoint, bool adjoint)
+{
+    return coded_on && opt_block_dia_code != 0 && opt_block_dia_code_adjoint != 0 && adjoint;
+}
+
 // ---- the kernel format a WHOLE-product launch takes (run_product), from plain flags, so that a stand-alone program can
 // walk all combinations (tests/box_plan_check.cpp): 0 SELL-64, 5 with coded columns, 1 banded, 2 with group masks, 9 with
 // coded values, 3 matrix-free box, 4 its single-factor form, 8 / 7 that form in slabs / pencils (eligible box, option

@@ -775,7 +775,9 @@ class KfspContext:
         While a target set is resident: D A D X (D A^T D X), the product with the killed generator - +0.0 on the set.
         Under set_option("block_dia_code", 1) the forward product of a banded generator with a coded image
         (dia_code_info()["active"]) reads one record per row and the dictionaries in LDS instead of the value streams: the
-        same bits; block_info() tells which kernel ran."""
+        same bits; block_info() tells which kernel ran.  With set_option("block_dia_code_adjoint", 1) beside it the same holds
+        for adjoint=True: A^T X from the records of the source rows (one 8-byte record word per diagonal), bit-identical to
+        the plain transposed product, reported as fmt 9 with adjoint 1."""
         Xf, k = _block_columns(X, self.n)
         Y = np.empty((self.n, k), dtype=np.float64, order="F")
         self._with_block_options(lambda: self._chk(self._lib.kfsp_spmm(self._h, k, self.n, _p(Xf), _p(Y)), "kfsp_spmm"),
@@ -851,7 +853,9 @@ class KfspContext:
     def block_info(self):
         """how the last block calls ran (kfsp_block_info).  While option "block_dia_code" is on, every block product writes
         "fmt" and "lds_bytes": 9 and the dynamic LDS of the launch (the dictionaries) when the coded kernel ran, else 0 and 0.
-        With the option off the two slots are what they always were (the one-launch small pass fills them)."""
+        With the option off the two slots are what they always were (the one-launch small pass fills them).  Under "adjoint" the
+        coded kernel runs only with option "block_dia_code_adjoint" = 1 as well: "fmt" 9 with "adjoint" 1 is the transposed
+        coded kernel; with that option at 0 a transposed product reports 0 and 0."""
         v = np.zeros(8, dtype=np.int64)
         self._chk(self._lib.kfsp_block_info(self._h, _p(v)), "kfsp_block_info")
         return dict(zip(("one_launch", "fmt", "begin_launches", "arnoldi_launches", "combine_launches", "lds_bytes", "adjoint", "exchange"),
@@ -907,6 +911,9 @@ class KfspContext:
         2: every matrix-free box (0 and 1 keep their meaning: a multi-factor box is still refused under 1).
         "block_dia_code" = 1 (default 0, read at every block call): the forward block product reads the dictionary-coded image
         of a banded generator where the single-vector product does (option "dia_code"); every other case keeps its kernel.
+        "block_dia_code_adjoint" = 1 (default 0, read at every block call, only with "block_dia_code" = 1): under "adjoint" the
+        transposed block product of such a generator reads the coded image too - the same bits as the plain transposed
+        product; at 0 backward calls keep the plain kernel.
         "dia_code_diag" (-1, default: generators that pass "dia_code"'s size gate; 0 never; 1 always try; read when the generator
         is set): DIAG of a coded banded generator is folded into bits 48-63 of its 8-byte records - the product reads no DIAG
         stream and computes the same bits (dia_code_info()["diag_table_bytes"] > 0 says that it was taken).
