@@ -13,8 +13,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libkfsp_hip.so")
-SOURCES = ["kfsp_api.cpp", "kfsp_comm.cpp", "kfsp_group.cpp", "kfsp_padm.cpp", "kfsp_stepper.cpp", "kfsp_kernels.hip", "kfsp_build.hip", "kfsp_drop.hip", "kfsp_expand.hip", "kfsp_prop.hip", "kfsp_ssa.hip", "kfsp_block.hip", "kfsp_block_adj.hip", "kfsp_block_boxg.hip", "kfsp_block_diac.hip", "kfsp_block_diac_t.hip", "kfsp_spmv_diac.hip", "kfsp_spmv_box.hip", "kfsp_generator.cpp"]
-HEADERS = ["kfsp_internal.h", "kfsp_dia_diag.h", "kfsp_box_plan.h", "kfsp_ctx.h", "kfsp_host.h", "kfsp_block.h", "kfsp_block_integral.h", "kfsp_block_dev.h", "kfsp_box_dev.h", "kfsp_boxg_dev.h", "kfsp_prop_dev.h", "kfsp_hash_dev.h", "kfsp_dispatch.h", "kfsp_dev.h", "kfsp_spmv_dev.h", os.path.join("..", "..", "include", "kfsp.h")]
+SOURCES = ["kfsp_api.cpp", "kfsp_comm.cpp", "kfsp_group.cpp", "kfsp_padm.cpp", "kfsp_stepper.cpp", "kfsp_kernels.hip", "kfsp_build.hip", "kfsp_drop.hip", "kfsp_expand.hip", "kfsp_prop.hip", "kfsp_ssa.hip", "kfsp_block.hip", "kfsp_block_adj.hip", "kfsp_block_boxg.hip", "kfsp_block_diac.hip", "kfsp_block_diac_t.hip", "kfsp_spmv_diac.hip", "kfsp_spmv_box.hip", "kfsp_generator.cpp", "kfsp_block_host.hip"]
+HEADERS = ["kfsp_internal.h", "kfsp_dia_diag.h", "kfsp_box_plan.h", "kfsp_ctx.h", "kfsp_host.h", "kfsp_block.h", "kfsp_block_integral.h", "kfsp_block_dev.h", "kfsp_box_dev.h", "kfsp_boxg_dev.h", "kfsp_prop_dev.h", "kfsp_hash_dev.h", "kfsp_dispatch.h", "kfsp_dev.h", "kfsp_spmv_dev.h", os.path.join("..", "..", "include", "kfsp.h"), "kfsp_block_plan.h"]
 
 
 def _hipcc():

@@ -205,8 +205,7 @@ inline double *vcol(const kfsp_ctx *c, int j) { return c->d_V.p + (size_t)j * (s
 int kfsp::resize(kfsp_ctx *ctx, int64_t n)
 {
     ctx->n = n;
-    kfsp::block_release(ctx);          // a block of vectors belongs to one generator (kfsp_set_block)
-    kfsp::block_target_release(ctx);   // ... and its target set (kfsp_set_block under block_target = 1)
+    kfsp::block_reset(ctx);            // a block of vectors and its target set belong to one generator (kfsp_set_block)
     ctx->L = round_up((n + ctx->nranks - 1) / ctx->nranks, kChunk);
     if (ctx->L == 0) ctx->L = kChunk;
     ctx->row0 = (int64_t)ctx->rank * ctx->L;
@@ -435,8 +434,7 @@ int kfsp_destroy(kfsp_ctx *ctx)
     ctx->d_ell_off2.release(); ctx->d_ell_diag2.release(); ctx->d_pstage.release(); ctx->d_keys.release();
     ctx->d_sortidx.release(); ctx->d_sorttmp.release(); ctx->d_gmask.release(); ctx->d_zero.release();
     ctx->d_skeys.release(); ctx->d_skeys2.release(); ctx->d_perm2.release(); ctx->d_prop_fast_i.release(); ctx->d_prop_fast_d.release();
-    kfsp::block_release(ctx);
-    kfsp::block_target_release(ctx);
+    kfsp::block_reset(ctx);
     if (ctx->h_loop) (void)hipHostFree(ctx->h_loop);
     if (ctx->h_H) (void)hipHostFree(ctx->h_H);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
@@ -1244,8 +1242,7 @@ int kfsp_drop_compact(kfsp_ctx *ctx, int64_t *n_new)
     if (!ctx->drop_planned || ctx->drop_n != ctx->n) return fail(ctx, -1, "no drop plan for the current FSP");
     if (!n_new) return fail(ctx, -2, "null n_new");
     HIP_TRY(hipSetDevice(ctx->device));
-    kfsp::block_release(ctx);          // the FSP changes: a block of vectors belongs to the old one
-    kfsp::block_target_release(ctx);   // ... and so does its target set
+    kfsp::block_reset(ctx);            // the FSP changes: a block of vectors and its target set belong to the old one
     hipStream_t st = ctx->stream;
     const int64_t n = ctx->n;
     const double *src = ctx->d_w.p;

@@ -1,4 +1,4 @@
-// Private: what the block time loop (kfsp_expv_block, kfsp_stepper.cpp) calls in kfsp_block.hip.  Plain host arrays
+// Private: what the block time loop (kfsp_expv_block, kfsp_stepper.cpp) calls in kfsp_block_host.hip.  Plain host arrays
 // and the opaque context only, like the rest of the stepper's view of the library.
 #pragma once
 
@@ -22,8 +22,6 @@ int block_integral(kfsp_ctx *ctx, int *on);
 // u_1 = W and beta[c] = ||W_c||_2 for the kp columns (padding columns included: 0); the basis is laid out for
 // dimension m here (block_arnoldi must not ask for more)
 int block_begin(kfsp_ctx *ctx, int m, double *beta);
-// release everything of the block path (a new generator, kfsp_destroy)
-void block_release(kfsp_ctx *ctx);
 // IOP(2) Arnoldi of dimension m for every column from the u_1 of block_begin, plus the AVNORM product.
 // Out, per column c (kBlockMaxK entries each): hb[(j * 3 + t) * kBlockMaxK + c] for j = 1..m holds H(j-1,j), H(j,j),
 // H(j+1,j) (t = 0, 1, 2); nrm[j * kBlockMaxK + c] = ||u_j|| for j = 1..m+1; brk[c] = 0 (no breakdown), j (breakdown

@@ -19,62 +19,31 @@
 // launch: two runs give the same bits.  A column whose H(j+1,j) <= break_tol stops there (its coefficients become 0,
 // its H is exact); a column with beta = 0 is skipped from the start and stays exactly 0.
 //
-// Matrix-free boxes (option block_box, k_spmm_box below; DESIGN.md 12, "Matrix-free boxes"): the row of a single-factor box is rebuilt
-// once - coordinates, {sum, valid} look-ups, one LDS read per entry - and applied to all kp columns, in the operation
-// order of the single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_spmv_dev.h, kfsp_spmv_box.hip).
-// Multi-factor boxes (option block_box = 2; DESIGN.md 12, "Multi-factor boxes"): every other matrix-free box, and any box
-// under box_generic = 1, takes the interpreted row of kernel format 3 - k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t
-// (kfsp_block_adj.hip), the row code in kfsp_boxg_dev.h; box_generic_path() and spmm_staged() below.  Values 0 and 1 of the
-// option mean what they always meant.
+// Matrix-free boxes (k_spmm_box below; DESIGN.md 12, "Matrix-free boxes"): the row of a single-factor box is rebuilt once -
+// coordinates, {sum, valid} look-ups, one LDS read per entry - and applied to all kp columns, in the operation order of the
+// single-vector matrix-free kernels (k_spmv format 4 and the pencil kernel, kfsp_spmv_dev.h, kfsp_spmv_box.hip).  Every other
+// box takes the interpreted row of kernel format 3: k_spmm_boxg (kfsp_block_boxg.hip), k_spmm_boxg_t (kfsp_block_adj.hip),
+// the row code in kfsp_boxg_dev.h.
 //
-// Small generators (option block_small; DESIGN.md 12, "Small generators"): where the single-vector path takes its
-// one-launch pass (<= kSmallRows rows, a banded or plain SELL image, no partition), a block step is three launches of
-// one 1024-lane workgroup per block column: k_bbegin_small, k_barnoldi_small (kfsp_kernels.hip: the pass of
-// k_arnoldi_small, compiled from the same lines) and k_bcombine_small.
+// Small generators ("Small generators"): one 1024-lane workgroup per block column - k_bbegin_small,
+// k_barnoldi_small (kfsp_kernels.hip: the pass of k_arnoldi_small, compiled from the same lines) and k_bcombine_small.
+// Time integrals ("Time integrals"): k_bcombine_int / k_bcombine_small_int - the pass over the basis that
+// makes W also adds a second linear combination (the table behind coef, kfsp_block_integral.h) to a second block J.
+// Target sets ("Target sets").  With a set T (one byte per row of the internal order) every block call works
+// on the killed generator Q = D A D, D = diag(1 - 1_T), and no product kernel knows: the raw product's partials u . z are
+// already those of Q because every basis column is 0 on T, and the TARGET instantiations of k_bcopy_nrm / k_bortho / k_bnorm
+// put +0.0 on T before they sum; k_btarget_zero masks a column, k_bhit sums one raw product over T.
 //
-// Row partitions (option block_partition; DESIGN.md 12, "Row partitions").  OPT-IN: with the option at its default 0 a
-// context with a communicator, a loop-back rank and a group head refuse every block call with -12, as they always have
-// (existing callers and tests rely on that refusal).  With 1 the forward block product of the stored forms runs on the
-// rank's rows: k_spmm takes local rows and addresses X by global row (SpmmArgs::row0), the source column is made visible
-// before every product the way the single-vector path does it - the neighbours' strips of halo * kp doubles into the
-// column's own margins (exchange_strips with a width), or an all-gather of L * kp doubles into d_bxg - and in halo mode
-// the product is split into an interior launch beside the exchange and one boundary launch (overlapped_product, kfsp_host.h).
-// Every block-partial sum is all-reduced before the bookkeeping reads it: k_bfinal sums the rank's partials in its fixed
-// order into 2 K staging doubles, one comm_allreduce, k_bfinal again with G = 1 on the reduced sums.  The sequence of
-// collectives of a call depends on k, m, the options and the agreed exchange mode only - never on a column's beta, its
-// breakdown or the rows a rank owns.  Still refused (-12): option adjoint (the transposed banded product reads the
-// neighbour's generator rows) and matrix-free boxes; block_small is not taken (small_path excludes partitions).
-//
-// Time integrals (option block_integral; DESIGN.md 12, "Time integrals").  While the option is on kfsp_set_block keeps a
-// second block J of the block's shape (d_bint, +0.0) and block_combine takes kernels of its own, k_bcombine_int /
-// k_bcombine_small_int: the pass over the basis that makes W also adds a second linear combination (the table behind coef,
-// kfsp_block_integral.h) to J.  With the option off neither the kernels above nor any allocation or launch changes.
-//
-// Target sets (the target-set mode of kfsp_set_block; DESIGN.md 12, "Target sets").  While a set T is resident (d_btgt: one byte per row of
-// the internal order) every block call works on the killed generator Q = D A D, D = diag(1 - 1_T), and no product kernel
-// knows: the raw product's partials u . z are already those of Q because every basis column is 0 on T, and the TARGET
-// instantiations of k_bcopy_nrm / k_bortho / k_bnorm put +0.0 on T before they sum.  kfsp_set_block stores D W, kfsp_spmm
-// masks X and Y (k_btarget_zero), the flux mode of kfsp_block_begin sums one raw product over T (k_bhit + the sum stage of k_bfinal).  With no
-// set resident the false instantiations run: the code as it was, no launch and no allocation more.
-//
-// Coded banded generators (option block_dia_code; DESIGN.md 12, "Coded banded generators").  OPT-IN: with 1 the forward
-// product of a banded generator whose coded image the single-vector product reads (dia_code_on, kfsp_host.h) takes
-// k_spmm_diac (kfsp_block_diac.hip) - one record per row and the dictionaries in LDS instead of nd value streams, the
-// same bits - unless the call is a transposed one or the one-launch small pass (spmm_diac_for below).  Everything else
-// keeps its kernel; with the option at 0 no launch, byte or report changes.  Option block_dia_code_adjoint = 1 beside it
-// (OPT-IN as well; DESIGN.md 12, "Coded banded generators, backward") gives the transposed product of such a generator to
-// k_spmm_diac_t (kfsp_block_diac_t.hip; spmm_diac_t_for below), the same bits as k_spmm_t; at 0 k_spmm_t runs as ever.
+// The host side - which kernel a call runs, the launches, the buffers, the entry points - is kfsp_block_host.hip; it reaches
+// the kernels of this file through the selectors at its end (kfsp_block_dev.h).
 #pragma clang fp contract(off)
 
 #include "kfsp_block_dev.h"
 #include "kfsp_box_dev.h"
 #include "kfsp_boxg_dev.h"
-#include "kfsp_host.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstring>
 #include <type_traits>
 
 namespace kfsp {
@@ -82,19 +51,6 @@ namespace kfsp {
 namespace {
 
 constexpr int K = kBlockMaxK;
-
-// per-column scalars of a pass (d_bscal), K entries each
-constexpr int kHB = 0;                          // [(kMMax + 2) * 3][K]: H(j-1,j), H(j,j), H(j+1,j) of column j
-constexpr int kNRM = kHB + (kMMax + 2) * 3 * K; // [kMMax + 3][K]: ||u_j||
-constexpr int kCO = kNRM + (kMMax + 3) * K;     // [3][K]: the update coefficients of the column in progress
-constexpr int kGG = kCO + 3 * K;                // [K]: v_j . v_{j-1}
-constexpr int kBRK = kGG + K;                   // [K]: 0 running, j broke down after column j, -1 skipped
-constexpr int kAVN = kBRK + K;                  // [K]
-constexpr int kWS = kAVN + K;                   // [K]
-constexpr int kCMB = kWS + K;                   // [kMMax + 3][K]: combine coefficients
-constexpr int kSQ1 = kCMB + (kMMax + 3) * K;    // [K]: ||u_1||^2 (what k_barnoldi_small starts from)
-constexpr int kScal = kSQ1 + K;
-constexpr int kSmallBlock = 1024;               // lanes of a small-path workgroup
 
 // SELL-64 row (plain or dictionary-coded columns), the slot order and addresses of row_sell / row_sell_coded
 template <int KP, bool CODED>
@@ -571,8 +527,6 @@ __global__ __launch_bounds__(kBlock) void k_bunpack(int64_t n, int k, int kp, co
     }
 }
 
-enum { kFinBegin = 0, kFinDots = 1, kFinNorm = 2, kFinAvn = 3, kFinWsum = 4 };
-
 // The per-column scalar work of a pass, one workgroup: 256 / K threads per column sum the block partials of the
 // two quantities in a fixed order, then one thread per column applies the Arnoldi bookkeeping of `stage`.
 // The second quantity's partials start off1 doubles behind the first's.  sums != null (a row partition): the sum stage
@@ -730,72 +684,10 @@ __global__ __launch_bounds__(kSmallBlock) void k_bcombine_small_int(int nact, in
     if (threadIdx.x == 0) sc[kWS + c] = s0;
 }
 
-// ---- host side
-const char *const kAdjFormMsg = "several vectors at once, option adjoint: the generator is resident in no form the transposed product reads";
+}  // namespace
 
-int kp_of(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)); }
-
-int spmm_fmt(const kfsp_ctx *c) { return c->use_dia ? (c->dia_masked ? 2 : 1) : (c->sell_coded ? 5 : 0); }
-int64_t spmm_trips(const kfsp_ctx *c) { return product_trips(c->nchunks, c->use_dia); }
-// rows a product writes, and rows of a block column (margins included).  Under a row partition a column holds the
-// block length L plus one 128-row group whatever the rank owns (every rank sends L rows to an all-gather and its last
-// halo rows to a neighbour; the padded half-group of a banded rank writes rows [L, L + 64)), and margins that take the
-// neighbours' strips (block_margin: the rule of setup_exchange) - sizes every rank agrees on.
-int64_t rows_act(const kfsp_ctx *c) { return spmm_trips(c) * (c->use_dia ? 128 : 64); }
-int64_t margin_rows(const kfsp_ctx *c) { return block_margin(c->margin); }
-int64_t col_rows(const kfsp_ctx *c) { return (c->use_comm ? c->L + 2 * kChunk : rows_act(c)) + 2 * margin_rows(c); }
-// doubles of one block column, and its first row
-size_t col_len(const kfsp_ctx *c, int kp) { return (size_t)col_rows(c) * (size_t)kp; }
-double *bcol(double *base, const kfsp_ctx *c, int kp, int j) { return base + (size_t)j * col_len(c, kp) + (size_t)margin_rows(c) * kp; }
-// the gathered source block of a row partition: nranks * L rows between margins; global row 0
-size_t xg_len(const kfsp_ctx *c, int kp) { return (size_t)(c->L * c->nranks + 2 * margin_rows(c)) * (size_t)kp; }
-double *xg_row0(const kfsp_ctx *c, int kp) { return c->d_bxg.p + (size_t)margin_rows(c) * kp; }
-// the context whose block state answers for ctx: rank 0 of a group head, else ctx itself
-kfsp_ctx *lead(kfsp_ctx *c) { return c->group ? group_rank0(c) : c; }
-// 16-byte pairs the streaming kernels cover: the rows of the SELL-padded block, like act_pairs
-int64_t red_pairs(const kfsp_ctx *c, int kp) { return c->nchunks * kChunk * (int64_t)kp / 2; }
-
-int spmm_grid(const kfsp_ctx *c) { return product_grid(spmm_trips(c), c->opt_grid, 1024); }
-
-// The small path is taken where kfsp_arnoldi (qiop = 2) takes k_arnoldi_small on this context (kfsp_api.cpp), short of
-// coded SELL columns: those stay on the multi-launch path.  So does every backward pass (option adjoint): k_barnoldi_small
-// has the forward product compiled in.  And every pass under a target set (the target-set mode of kfsp_set_block): the masks live in the
-// streaming kernels of the general path.
-bool small_path(const kfsp_ctx *c)
-{
-    return c->opt_block_small != 0 && !c->blk_tgt && c->opt_adjoint == 0 && c->opt_small != 0 && c->opt_fused != 0 && !c->use_comm && !c->group && !c->box.on &&
-           c->nchunks * kChunk <= kSmallRows && (c->use_dia || (c->have_sell && !c->sell_coded)) && c->slots < (1LL << 31);
-}
-
-// grid of the streaming kernels over a block column
-int flat_grid(const kfsp_ctx *c, int kp) { return vec_grid(red_pairs(c, kp), c->opt_vgrid); }
-
-// A streaming kernel over a block column of width kp: flat_grid workgroups on the context's stream, the pairs and kp / 2
-// in front of the kernel's own arguments.  Returns the grid: that many block partials.
-template <class Kern, class... Args>
-int launch_flat(kfsp_ctx *ctx, int kp, Kern kern, Args... args)
-{
-    const int g = flat_grid(ctx, kp);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp / 2, args...);
-    return g;
-}
-
-d2 *pairs(double *p) { return reinterpret_cast<d2 *>(p); }
-const d2 *pairs(const double *p) { return reinterpret_cast<const d2 *>(p); }
-
-// grid of the pack / unpack kernels over `items` elements
-int pack_grid(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (items + kBlock - 1) / kBlock)); }
-
-// col <- D col for a block column of width kp (row 0 at col; target sets: the row of pair i is i >> kp_index(kp));
-// nothing without a set
-void target_zero(kfsp_ctx *ctx, int kp, double *col)
-{
-    if (!ctx->blk_tgt) return;
-    hipLaunchKernelGGL(k_btarget_zero, dim3(flat_grid(ctx, kp)), dim3(kBlock), 0, ctx->stream, red_pairs(ctx, kp), kp_index(kp),
-                       ctx->d_btgt.p, pairs(col));
-}
-
-// k_spmm of the stored forms (fmt: spmm_fmt; part: the launch of a rank of a row partition)
+// ---- what kfsp_block_host.hip launches, by function pointer (kfsp_block_dev.h)
+// k_spmm of the stored forms (fmt: BlockPlan::fmt; part: the launch of a rank of a row partition)
 SpmmFn spmm_kernel(int kp, int fmt, bool dots, bool part)
 {
     return dispatch_kp_dots(kp, dots, [&](auto KP, auto DOTS) {
@@ -819,839 +711,12 @@ SpmmFn spmm_box_kernel(int kp, int inst, bool dots)
     });
 }
 
-// Option block_box = 2: the generic kernels (k_spmm_boxg, kfsp_block_boxg.hip; k_spmm_boxg_t, kfsp_block_adj.hip) answer
-// for a box without the single-factor form and for any box under box_generic = 1.  Read at every block call.
-bool box_generic_path(const kfsp_ctx *c) { return c->box.on && c->opt_block_box == 2 && (!c->box.fast || c->opt_box_generic != 0); }
-
-// In the block layout a reach of delta rows is 8 kp delta bytes, and the single-factor kernels (k_spmm_box, k_spmm_box_t)
-// address X as scalar base + unsigned 32-bit lane offset: the backward plus the forward reach plus one 128-row group must
-// stay below 2^32 bytes.
-bool box_block_reach_ok(const kfsp_ctx *c, int kp)
+const BlockKernels &block_kernels()
 {
-    const int64_t back = std::max<int64_t>(0, -(int64_t)c->delta[0]), fwd = std::max<int64_t>(0, (int64_t)c->delta[c->nd - 1]);
-    return (back + fwd + 128) * 8 * (int64_t)kp < (1LL << 32);
-}
-
-// ... refused where a block of this width meets those kernels (box_generic is read at every call: a block set under the
-// generic kernels, which address X by 64-bit row index, may meet the single-factor ones later)
-int box_reach_check(kfsp_ctx *c, int kp)
-{
-    if (!c->box.on || box_generic_path(c) || box_block_reach_ok(c, kp)) return 0;
-    return fail(c, -12, "several vectors at once: the entries of this matrix-free box reach further than 2^32 bytes "
-                        "at this block width (fewer columns, or option box_store = 1)");
-}
-
-// One launch of a kernel that stages a table image of `image_bytes` into dynamic LDS.  Every workgroup copies the image
-// first, so no more workgroups are launched than are resident at once (the rule of the single-vector product,
-// run_product): the runtime says how many fit, asked once per family, width and variant (blk_staged_occ).  The
-// reductions of the box kernels reuse the image's LDS: never less than 4 kp doubles of it; the coded banded kernel keeps
-// its reduction scratch apart (static LDS) and asks for the dictionaries alone (staged_lds: the dynamic LDS of the launch).
-// Returns the grid.
-size_t staged_lds(StagedFamily fam, size_t image_bytes, int kp)
-{
-    return fam == kStagedDiac || fam == kStagedDiacT ? image_bytes : std::max<size_t>(image_bytes, (size_t)4 * kp * sizeof(double));
-}
-
-template <class... Args>
-int launch_staged(kfsp_ctx *ctx, StagedFamily fam, int kp, bool dots, int64_t trips, size_t image_bytes, void (*kern)(Args...),
-                  const Args &...args)
-{
-    const size_t lds = staged_lds(fam, image_bytes, kp);
-    int &occ = ctx->blk_staged_occ[fam][kp_index(kp)][dots ? 1 : 0];
-    if (occ == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kBlock, lds) != hipSuccess || occ < 1)) occ = 1;
-    const int g = product_grid(trips, ctx->opt_grid, std::min<int64_t>(1024, (int64_t)256 * occ));
-    hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(kBlock), lds, ctx->stream, args...);
-    return g;
-}
-
-// The block product of a matrix-free box, forward or transposed: the table pointers of `a`, then the kernel of the
-// family.  The single-factor kernels stage the whole image and read the descriptor behind it; the generic ones stage
-// the head and the factor tables only and take the box descriptor by value behind SpmmArgs (BoxgArgs).  -1: the
-// descriptor is not one the family can walk (block_supported refuses that first).
-int spmm_staged(kfsp_ctx *ctx, int kp, bool dots, bool transposed, SpmmArgs &a)
-{
-    a.box_tab = ctx->d_box.p;
-    if (box_generic_path(ctx)) {
-        a.box_ntab = box_generic_image(ctx->box.dev);
-        a.box_fast = nullptr;
-        if (a.box_ntab == 0) return -1;
-        return launch_staged(ctx, transposed ? kStagedBoxgT : kStagedBoxg, kp, dots, a.trips, (size_t)a.box_ntab * sizeof(double),
-                             transposed ? spmm_boxg_t_kernel(kp, dots) : spmm_boxg_kernel(kp, dots), BoxgArgs{a, ctx->box.dev});
-    }
-    a.box_ntab = ctx->box.dev.ntab;
-    a.box_fast = reinterpret_cast<const BoxFast *>(ctx->d_box.p + (ctx->box.lds_bytes / sizeof(double)));
-    if (!transposed) return launch_staged(ctx, kStagedBox, kp, dots, a.trips, ctx->box.lds_bytes, spmm_box_kernel(kp, ctx->box.dev.pad, dots), a);
-    BoxAdjDev b;
-    if (!box_adj_build(ctx->box.dev, b)) return -1;
-    return launch_staged(ctx, kStagedBoxT, kp, dots, a.trips, ctx->box.lds_bytes, spmm_box_t_kernel(kp, ctx->box.dev.pad, dots), a, b);
-}
-
-// The coded banded image is what the coded block kernels walk: records for every row a trip touches, all codes of a row
-// inside its record, the dictionaries within the LDS budget.
-bool diac_image_walkable(const kfsp_ctx *c, int64_t trips)
-{
-    const int w = c->dia_code_w, rec = c->dia_code_rec, nd = c->nd;
-    if (nd < 1 || nd > kMaxDiag || w < 1 || nd * w > rec * 8 || c->dia_ld < trips * 128) return false;
-    return c->dia_doff[nd] >= 1 && (int64_t)c->dia_doff[nd] * 8 <= kDiaCodeLds;
-}
-
-// Option block_dia_code: the kernel that reads the coded banded image for this call, or null - the rule of
-// block_dia_code_path (kfsp_host.h), a form dispatch_diac knows, and an image the kernel can walk.  Null: the plain
-// kernel runs, as it always has.  Read at every block call.
-SpmmDiacFn spmm_diac_for(const kfsp_ctx *c, int kp, bool dots, int64_t trips)
-{
-    if (!block_dia_code_path(dia_code_on(c), c->opt_block_dia_code, c->opt_adjoint != 0, small_path(c))) return nullptr;
-    if (!diac_image_walkable(c, trips)) return nullptr;
-    return spmm_diac_kernel(kp, c->dia_code_w, c->dia_code_rec, dots);
-}
-
-// Option block_dia_code_adjoint: the same for the transposed product - the rule of block_dia_code_t_path (kfsp_host.h),
-// the same image guards (k_spmm_diac_t reads records of rows below n only; the bound on dia_ld holds all the more).
-// Null: k_spmm_t runs, as it always has.  Read at every block call.
-SpmmDiacFn spmm_diac_t_for(const kfsp_ctx *c, int kp, bool dots, int64_t trips)
-{
-    if (!block_dia_code_t_path(dia_code_on(c), c->opt_block_dia_code, c->opt_block_dia_code_adjoint, c->opt_adjoint != 0)) return nullptr;
-    if (!diac_image_walkable(c, trips)) return nullptr;
-    return spmm_diac_t_kernel(kp, c->dia_code_w, c->dia_code_rec, dots);
-}
-
-// The reference arrays in the order the device keeps its vectors: the relabelled copies under the internal state order.
-bool ell_adj_args(const kfsp_ctx *ctx, EllAdjDev &e)
-{
-    const DevBuf<int32_t> &adj = ctx->perm_on ? ctx->d_ell_adj2 : ctx->d_ell_adj;
-    const DevBuf<double> &off = ctx->perm_on ? ctx->d_ell_off2 : ctx->d_ell_off;
-    const DevBuf<double> &diag = ctx->perm_on ? ctx->d_ell_diag2 : ctx->d_ell_diag;
-    if (!adj.p || !off.p || !diag.p || !ell_adj_resident(ctx->n, ctx->ell_cols, ctx->ell_ld, ctx->ell_bw, adj.cap, off.cap, diag.cap))
-        return false;
-    e = EllAdjDev{adj.p, off.p, diag.p, ctx->n, ctx->ell_ld, ctx->ell_bw};
-    return true;
-}
-
-// Y = A X, or A^T X under option adjoint (block columns of width kp); dots: partials of ua . Y and ub . Y in *G slots.
-// x: row 0 of the source column.  The transposed product (kfsp_block_adj.hip) takes the grid of the forward product of
-// the same form.  Under a row partition (forward stored forms only, block_supported) the source is made visible first -
-// the strips into x's own margins, or all blocks gathered into d_bxg - unless x_global says that x is row 0 of a whole
-// block every rank already holds (kfsp_spmm).  blk_info[7] records how.
-int spmm(kfsp_ctx *ctx, int kp, const double *x, double *Y, const double *ua, const double *ub, bool dots, int *G, bool x_global = false)
-{
-    SpmmArgs a;
-    generator_args(ctx, a.A, a.D);
-    a.X = x;
-    a.Y = Y;
-    a.ua = ua;
-    a.ub = ub;
-    a.part = ctx->d_bpart.p;
-    a.trips = spmm_trips(ctx);
-    a.trip_order = ctx->trip_order_n == a.trips ? ctx->d_trip_order.p : nullptr;
-    a.rows_red = ctx->nchunks * kChunk;
-    a.box_tab = nullptr;
-    a.box_ntab = 0;
-    a.box_fast = nullptr;
-    a.row0 = 0;
-    a.trip_begin = 0;
-    a.trip_end = a.trips;
-    a.trip_split = INT64_MAX;
-    a.trip_jump = 0;
-    ctx->blk_info[7] = 0;
-    // option block_dia_code: slots 1 and 5 say, product by product, whether the coded kernel ran (9, its dynamic LDS) or
-    // not (0, 0); with the option off nothing here writes them
-    if (ctx->opt_block_dia_code) ctx->blk_info[1] = ctx->blk_info[5] = 0;
-    hipStream_t st = ctx->stream;
-    const int g = spmm_grid(ctx);
-    *G = g;
-    if (ctx->box.on) {
-        if (int rc = box_reach_check(ctx, kp)) return rc;
-        const int gs = spmm_staged(ctx, kp, dots, ctx->opt_adjoint != 0, a);
-        if (gs < 0) return fail(ctx, -12, kAdjFormMsg);      // (block_supported refuses those first)
-        *G = gs;
-        return 0;
-    }
-    // a coded banded kernel of either direction: the dictionaries staged, slots 1 and 5 say so
-    auto launch_coded = [&](StagedFamily fam, SpmmDiacFn coded) {
-        DiaCodeDev C;
-        dia_code_args(ctx, C);
-        const size_t image = (size_t)C.doff[ctx->nd] * sizeof(double);
-        *G = launch_staged(ctx, fam, kp, dots, a.trips, image, coded, a, C);
-        ctx->blk_info[1] = 9;
-        ctx->blk_info[5] = (int64_t)staged_lds(fam, image, kp);
-    };
-    if (ctx->opt_adjoint) {
-        if (ctx->use_dia) {
-            if (const SpmmDiacFn coded = spmm_diac_t_for(ctx, kp, dots, a.trips)) {
-                launch_coded(kStagedDiacT, coded);           // "fmt 9, adjoint 1": k_spmm_diac_t
-                return 0;
-            }
-            hipLaunchKernelGGL(spmm_t_kernel(kp, dots), dim3(g), dim3(kBlock), 0, st, a);
-            return 0;
-        }
-        EllAdjDev e;
-        if (!ell_adj_args(ctx, e)) return fail(ctx, -12, kAdjFormMsg);
-        hipLaunchKernelGGL(spmm_ell_t_kernel(kp, dots), dim3(g), dim3(kBlock), 0, st, a, e);
-        return 0;
-    }
-    if (const SpmmDiacFn coded = spmm_diac_for(ctx, kp, dots, a.trips)) {
-        launch_coded(kStagedDiac, coded);
-        return 0;
-    }
-    const SpmmFn kern = spmm_kernel(kp, spmm_fmt(ctx), dots, ctx->use_comm);
-    auto launch = [&](int grid) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, a); };
-    if (!ctx->use_comm) {
-        launch(g);
-        return 0;
-    }
-    a.row0 = ctx->row0;
-    if (x_global) {
-        launch(g);
-        return 0;
-    }
-    if (!ctx->use_halo) {
-        if (int rc = comm_allgather(ctx, x, xg_row0(ctx, kp), (size_t)ctx->L * kp, st)) return rc;
-        a.X = xg_row0(ctx, kp);
-        ctx->blk_info[7] = 2;
-        launch(g);
-        return 0;
-    }
-    a.X = x - (size_t)ctx->row0 * kp;                        // global row g lies at x[(g - row0) * kp]
-    ctx->blk_info[7] = 1;
-    const ProductSplit ps = product_split(ctx->halo, ctx->L, a.trips, ctx->use_dia ? 128 : 64, ctx->opt_overlap);
-    if (!ps.split || ctx->comm_stream == nullptr) {
-        if (int rc = exchange_strips(ctx, x, st, kp)) return rc;
-        launch(g);
-        return 0;
-    }
-    // the strips travel on the communication stream while the interior trips run (overlapped_product, kfsp_host.h)
-    a.trip_order = nullptr;
-    auto launch_range = [&](int64_t begin, int64_t end, int64_t split, int64_t jump, int grid, int used) {
-        a.part = ctx->d_bpart.p + (size_t)used * K;
-        a.trip_begin = begin;
-        a.trip_end = end;
-        a.trip_split = split;
-        a.trip_jump = jump;
-        launch(grid);
-        return grid;
-    };
-    if (int rc = overlapped_product(ctx, ps, a.trips, x, kp, 1024, launch_range, G)) return rc;
-    ctx->blk_info[7] = 5;
-    return 0;
-}
-
-// The scalar stage behind a producer of G block partials.  One rank: one launch, as ever.  Row partition: the rank's
-// column sums in the same fixed order, one all-reduce of the 2 K sums, the bookkeeping on the reduced sums - on every
-// rank, whatever its columns did.
-int finalize(kfsp_ctx *ctx, int stage, int j, int kp, int G, double break_tol = 0.0)
-{
-    const int64_t off1 = (int64_t)kMaxGrid * K;
-    if (!ctx->use_comm) {
-        hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, G, ctx->d_bpart.p, off1, ctx->d_bscal.p, break_tol,
-                           (double *)nullptr);
-        return 0;
-    }
-    double *sums = ctx->d_bpart.p + (size_t)2 * kMaxGrid * K;
-    hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, G, ctx->d_bpart.p, off1, ctx->d_bscal.p, break_tol, sums);
-    if (int rc = comm_allreduce(ctx, sums, 2 * K, false, ctx->stream)) return rc;
-    hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, ctx->stream, stage, j, kp, 1, sums, (int64_t)K, ctx->d_bscal.p, break_tol,
-                       (double *)nullptr);
-    return 0;
-}
-
-// the scalar and partial buffers of the block path
-int ensure_scalars(kfsp_ctx *ctx)
-{
-    HIP_TRY(ctx->d_bscal.reserve(kScal, true));
-    HIP_TRY(ctx->d_bpart.reserve((size_t)2 * kMaxGrid * K + 2 * K, true));    // + the 2 K column sums a row partition all-reduces
-    return 0;
-}
-
-// `need` doubles in a buffer of block columns laid out for width kp (*laid): zeroed when allocated and whenever the
-// width changes - margins, and the rows behind n, must read 0
-int reserve_for_width(kfsp_ctx *ctx, DevBuf<double> &buf, int *laid, size_t need, int kp)
-{
-    if (need > buf.cap) {
-        buf.release();
-        HIP_TRY(buf.reserve(need, true));
-        *laid = kp;
-    }
-    if (*laid != kp) {
-        HIP_TRY(hipMemsetAsync(buf.p, 0, buf.cap * sizeof(double), ctx->stream));
-        *laid = kp;
-    }
-    return 0;
-}
-
-// ncols block columns of width kp in d_bv; under a row partition also what it exchanges block columns through - the strip
-// buffer at block width and the gathered block; and the scalars
-int ensure_basis(kfsp_ctx *ctx, int kp, int ncols)
-{
-    if (int rc = reserve_for_width(ctx, ctx->d_bv, &ctx->bv_kp, (size_t)ncols * col_len(ctx, kp), kp)) return rc;
-    if (ctx->use_comm) {
-        if (ctx->use_halo) HIP_TRY(ctx->d_strip.reserve((size_t)(2 * ctx->halo) * (size_t)(ctx->nranks + 1) * (size_t)kp, true));
-        if (int rc = reserve_for_width(ctx, ctx->d_bxg, &ctx->bxg_kp, xg_len(ctx, kp), kp)) return rc;
-    }
-    return ensure_scalars(ctx);
-}
-
-// host column-major (caller's order) -> zeroed block column dst (width kp, internal order).  One rank, and the whole
-// block every rank of a partition holds (whole: kfsp_spmm's X into d_bxg): n rows through the permutation.  A rank's
-// own rows (kfsp_set_block under a communicator): column by column the way kfsp_set_vector takes a vector
-// (upload_states: under the internal state order one all-gather per column, on every rank), then packed as they lie.
-int upload_block(kfsp_ctx *ctx, int k, int kp, int64_t ld, const double *W, double *col0, bool whole = false)
-{
-    hipStream_t st = ctx->stream;
-    if (ctx->use_comm && !whole) {
-        const int64_t nl = ctx->nloc, L = ctx->L;
-        HIP_TRY(ctx->d_bstage.reserve((size_t)L * k, false));
-        HIP_TRY(hipMemsetAsync(col0 - (size_t)margin_rows(ctx) * kp, 0, col_len(ctx, kp) * sizeof(double), st));
-        for (int c = 0; c < k; ++c)
-            if (int rc = upload_states(ctx, W ? W + (size_t)c * ld : W, ctx->d_bstage.p + (size_t)c * L, nl)) return rc;
-        hipLaunchKernelGGL(k_bpack, dim3(pack_grid(nl * kp)), dim3(kBlock), 0, st, nl, k, kp, ctx->d_bstage.p, L, (const int32_t *)nullptr, col0);
-        return 0;
-    }
-    const int64_t n = ctx->n;
-    HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
-    if (whole) HIP_TRY(hipMemsetAsync(ctx->d_bxg.p, 0, xg_len(ctx, kp) * sizeof(double), st));
-    else HIP_TRY(hipMemsetAsync(col0 - (size_t)margin_rows(ctx) * kp, 0, col_len(ctx, kp) * sizeof(double), st));
-    HIP_TRY(hipMemcpy2DAsync(ctx->d_bstage.p, (size_t)n * sizeof(double), W, (size_t)ld * sizeof(double), (size_t)n * sizeof(double),
-                             (size_t)k, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_bpack, dim3(pack_grid(n * kp)), dim3(kBlock), 0, st, n, k, kp, ctx->d_bstage.p, n, ctx->perm_on ? ctx->d_perm.p : nullptr, col0);
-    return 0;
-}
-
-// ... and back; under a communicator the rank's rows column by column through download_states (L rows staged per
-// column: that is what its all-gather sends)
-int download_block(kfsp_ctx *ctx, int k, int kp, const double *col0, int64_t ld, double *W)
-{
-    hipStream_t st = ctx->stream;
-    if (ctx->use_comm) {
-        const int64_t L = ctx->L;
-        HIP_TRY(ctx->d_bstage.reserve((size_t)L * k, false));
-        hipLaunchKernelGGL(k_bunpack, dim3(pack_grid(L * k)), dim3(kBlock), 0, st, L, k, kp, col0, (const int32_t *)nullptr, ctx->d_bstage.p, L);
-        for (int c = 0; c < k; ++c)
-            if (int rc = download_states(ctx, ctx->d_bstage.p + (size_t)c * L, W ? W + (size_t)c * ld : W, ctx->nloc)) return rc;
-        return 0;
-    }
-    const int64_t n = ctx->n;
-    HIP_TRY(ctx->d_bstage.reserve((size_t)n * k, false));
-    hipLaunchKernelGGL(k_bunpack, dim3(pack_grid(n * k)), dim3(kBlock), 0, st, n, k, kp, col0, ctx->perm_on ? ctx->d_iperm.p : nullptr, ctx->d_bstage.p, n);
-    HIP_TRY(hipMemcpy2DAsync(W, (size_t)ld * sizeof(double), ctx->d_bstage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                             (size_t)k, hipMemcpyDeviceToHost, st));
-    return 0;
-}
-
-// the block path's fence at the C boundary
-template <class F>
-int guarded(kfsp_ctx *ctx, F &&body) { return no_throw(ctx, body, "exception inside the block path"); }
-
-}  // namespace
-
-void block_release(kfsp_ctx *ctx)
-{
-    ctx->d_blk.release();
-    ctx->d_bv.release();
-    ctx->d_bstage.release();
-    ctx->d_bscal.release();
-    ctx->d_bpart.release();
-    ctx->d_bxg.release();
-    ctx->d_bint.release();
-    ctx->d_bcj.release();
-    ctx->d_bhit.release();
-    ctx->d_bhsum.release();
-    ctx->bhit_launches = 0;
-    ctx->blk_int = false;
-    ctx->blk_k = ctx->blk_kp = ctx->bv_kp = ctx->bxg_kp = ctx->blk_begin_m = 0;
-    std::memset(ctx->blk_info, 0, sizeof(ctx->blk_info));
-    std::memset(ctx->blk_staged_occ, 0, sizeof(ctx->blk_staged_occ));
-}
-
-void block_target_release(kfsp_ctx *ctx)
-{
-    ctx->d_btgt.release();
-    ctx->blk_tgt = false;
-    ctx->btgt_states = 0;
-}
-
-// Every refusal below is made from what all ranks of a partition share (options, the kind of generator), before the
-// first collective of any block call: a rank that returned alone would leave its peers waiting in one.
-int block_supported(kfsp_ctx *ctx)
-{
-    static const char *const kPartMsg = "several vectors at once: not with a row partition (communicator or group context) "
-                                        "unless option block_partition = 1";
-    if (ctx->group) {
-        kfsp_ctx *r0 = group_rank0(ctx);
-        if (!r0 || !r0->opt_block_partition) return fail(ctx, -12, kPartMsg);
-        const int rc = block_supported(r0);
-        if (rc) ctx->err = std::string(r0->err);
-        return rc;
-    }
-    if (ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm) {
-        if (!ctx->opt_block_partition) return fail(ctx, -12, kPartMsg);
-        if (!ctx->use_comm) return fail(ctx, -12, "several vectors at once: this rank's communicator carries no collectives");
-        if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
-        if (ctx->opt_adjoint)
-            return fail(ctx, -12, "several vectors at once, option adjoint: not under a row partition (the transposed banded "
-                                  "product reads the neighbour's generator rows, not only its rows of X)");
-        if (ctx->box.on)
-            return fail(ctx, -12, "several vectors at once: not for a matrix-free generator under a row partition "
-                                  "(option box_store = 1 stores it)");
-    }
-    if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
-    if (ctx->box.on) {
-        if (!ctx->opt_block_box)
-            return fail(ctx, -12, "several vectors at once: not for a matrix-free generator (option box_store = 1 stores it, "
-                                  "option block_box = 1 takes it matrix-free)");
-        if (box_generic_path(ctx)) {
-            if (box_generic_image(ctx->box.dev) == 0)
-                return fail(ctx, -12, "several vectors at once: the descriptor of this matrix-free box is not one the generic block "
-                                      "kernels can walk (option box_store = 1 stores it)");
-            return 0;
-        }
-        if (ctx->opt_box_generic)
-            return fail(ctx, -12, "several vectors at once: not for the interpreted matrix-free product (option box_generic = 1)");
-        if (!ctx->box.fast)
-            return fail(ctx, -12, "several vectors at once: this matrix-free box has no single-factor form (option box_store = 1 stores it)");
-        return 0;
-    }
-    if (!ctx->use_dia && !ctx->have_sell) return fail(ctx, -12, "several vectors at once: no stored generator");
-    EllAdjDev e;
-    if (ctx->opt_adjoint && !ctx->use_dia && !ell_adj_args(ctx, e))
-        return fail(ctx, -12, "several vectors at once, option adjoint: the transposed product of a SELL generator reads the reference "
-                              "arrays ADJ / OFFDIAG / DIAG, and none are resident for this one (kfsp_set_matrix_ell uploads them; "
-                              "option box_store = 1 stores a box as diagonals)");
-    return 0;
-}
-
-int block_shape(kfsp_ctx *ctx, int *k, int64_t *n)
-{
-    *k = lead(ctx)->blk_k;
-    *n = ctx->n;
-    return 0;
-}
-
-int block_mmax(kfsp_ctx *ctx)
-{
-    ctx = lead(ctx);
-    return (int)(ctx->v_mmax ? std::min(ctx->v_mmax, ctx->opt_mmax) : ctx->opt_mmax);
-}
-
-int block_integral(kfsp_ctx *ctx, int *on)
-{
-    const kfsp_ctx *l = lead(ctx);
-    *on = l->opt_block_integral != 0;
-    if (*on && !l->blk_int)
-        return fail(ctx, -1, "option block_integral is on but the resident block has no integral beside it: set the option "
-                             "before kfsp_set_block");
-    return 0;
-}
-
-int block_begin(kfsp_ctx *ctx, int m, double *beta)
-{
-    if (ctx->group) return group_block_begin(ctx, m, beta);
-    PhaseTimer timer(ctx, KFSP_T_BEGIN);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int kp = ctx->blk_kp;
-    if (int rc = ensure_basis(ctx, kp, m + 2)) return rc;
-    ctx->blk_begin_m = m;
-    if (small_path(ctx)) {
-        hipLaunchKernelGGL(k_bbegin_small, dim3(kp), dim3(kSmallBlock), 0, ctx->stream, (int)(ctx->nchunks * kChunk), kp,
-                           bcol(ctx->d_blk.p, ctx, kp, 0), bcol(ctx->d_bv.p, ctx, kp, 0), ctx->d_bscal.p);
-        ctx->blk_info[2] = 1;
-    } else {
-        const int g = launch_flat(ctx, kp, ctx->blk_tgt ? k_bcopy_nrm<true> : k_bcopy_nrm<false>, pairs(bcol(ctx->d_blk.p, ctx, kp, 0)),
-                                  pairs(bcol(ctx->d_bv.p, ctx, kp, 0)), ctx->d_bpart.p, ctx->d_btgt.p, kp_index(kp));
-        if (int rc = finalize(ctx, kFinBegin, 1, kp, g)) return rc;
-        ctx->blk_info[2] = 2;
-    }
-    HIP_TRY(hipMemcpyAsync(beta, ctx->d_bscal.p + kNRM + K, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int block_arnoldi(kfsp_ctx *ctx, int m, double break_tol, double *hb, double *nrm, int *brk, double *avnorm)
-{
-    if (ctx->group) return group_block_arnoldi(ctx, m, break_tol, hb, nrm, brk, avnorm);
-    PhaseTimer timer(ctx, KFSP_T_ARNOLDI);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int kp = ctx->blk_kp;
-    if (int rc = ensure_basis(ctx, kp, m + 2)) return rc;
-    hipStream_t st = ctx->stream;
-    double *V = ctx->d_bv.p;
-    auto u = [&](int j) { return bcol(V, ctx, kp, j - 1); };   // u_j, 1-based
-    const bool small = small_path(ctx);
-    // target set: the update pass and the AVNORM norm mask what the raw product wrote (null: the kernels as they were)
-    const uint8_t *tgt = ctx->blk_tgt ? ctx->d_btgt.p : nullptr;
-    const int sh = kp_index(kp);
-    ctx->blk_info[0] = small ? 1 : 0;
-    ctx->blk_info[1] = ctx->blk_info[5] = 0;
-    ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
-    ctx->blk_info[3] = small ? 1 : 4 * m + 3;
-    if (small) {
-        SmallArnoldiArgs sa;
-        generator_args(ctx, sa.A, sa.D);
-        sa.V = nullptr;
-        sa.ldv = (int64_t)col_len(ctx, kp);
-        sa.nact = ctx->nchunks * kChunk;
-        sa.m = m;
-        sa.jold = 1;
-        sa.sq = sa.gfin = sa.Hd = nullptr;
-        sa.break_tol = break_tol;
-        sa.brk_flag = nullptr;
-        sa.slots = ctx->use_dia ? 0 : ctx->slots;
-        double *sc = ctx->d_bscal.p;
-        const SmallBlockArgs sb{u(1), kp, ctx->blk_k, K, sc + kHB, sc + kNRM, sc + kBRK, sc + kAVN, sc + kSQ1};
-        int fmt = 0;
-        size_t lds = 0;
-        if (const int e = launch_barnoldi_small(sa, sb, kp, ctx->use_dia, ctx->opt_small_lds ? ctx->lds_per_block : 0, st, &fmt, &lds))
-            return hip_fail(ctx, (hipError_t)e, "hipFuncSetAttribute(k_barnoldi_small)");
-        ctx->blk_info[1] = fmt;
-        ctx->blk_info[5] = (int64_t)lds;
-    }
-    for (int j = 1; j <= m && !small; ++j) {
-        int g = 0;
-        if (int rc = spmm(ctx, kp, u(j), u(j + 1), j >= 2 ? u(j - 1) : nullptr, u(j), true, &g)) return rc;
-        if (int rc = finalize(ctx, kFinDots, j, kp, g)) return rc;
-        const int gv = launch_flat(ctx, kp, tgt ? k_bortho<true> : k_bortho<false>, pairs(u(j + 1)), pairs(j >= 2 ? u(j - 1) : nullptr),
-                                   pairs(u(j)), ctx->d_bscal.p + kCO, ctx->d_bpart.p, tgt, sh);
-        if (int rc = finalize(ctx, kFinNorm, j, kp, gv, break_tol)) return rc;
-    }
-    if (!small) {
-        // the extra product for AVNORM (:261-263) into the scratch column
-        int g = 0;
-        if (int rc = spmm(ctx, kp, u(m + 1), u(m + 2), nullptr, nullptr, false, &g)) return rc;
-        // (two launches for a const: the set's instantiation writes D z back)
-        const int gv = tgt ? launch_flat(ctx, kp, k_bnorm<true>, pairs(u(m + 2)), ctx->d_bpart.p, tgt, sh)
-                           : launch_flat(ctx, kp, k_bnorm<false>, pairs(u(m + 2)), ctx->d_bpart.p, tgt, sh);
-        if (int rc = finalize(ctx, kFinAvn, m + 1, kp, gv)) return rc;
-    }
-    std::vector<double> h((size_t)kScal);
-    HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_bscal.p, (size_t)kCMB * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::memcpy(hb, h.data() + kHB, (size_t)(kMMax + 2) * 3 * K * sizeof(double));
-    std::memcpy(nrm, h.data() + kNRM, (size_t)(kMMax + 3) * K * sizeof(double));
-    std::memcpy(avnorm, h.data() + kAVN, K * sizeof(double));
-    for (int c = 0; c < K; ++c) brk[c] = (int)h[(size_t)kBRK + c];
-    return 0;
-}
-
-int block_combine(kfsp_ctx *ctx, int mx, const double *coef, double *wsum)
-{
-    if (ctx->group) return group_block_combine(ctx, mx, coef, wsum);
-    PhaseTimer timer(ctx, KFSP_T_COMBINE);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int kp = ctx->blk_kp;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->d_bscal.p + kCMB, coef, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
-    // option block_integral: the same launches with the kernels that carry J along; rows [mx, 2 mx) of coef are J's table
-    const bool integral = ctx->opt_block_integral != 0, small = small_path(ctx);
-    if (integral) {
-        if (!ctx->blk_int) return fail(ctx, -1, "option block_integral: no integral resident (set the option before kfsp_set_block)");
-        HIP_TRY(hipMemcpyAsync(ctx->d_bcj.p, coef + (size_t)mx * K, (size_t)mx * K * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    const double *U = bcol(ctx->d_bv.p, ctx, kp, 0), *cw = ctx->d_bscal.p + kCMB, *cj = ctx->d_bcj.p;
-    double *w = bcol(ctx->d_blk.p, ctx, kp, 0), *J = integral ? bcol(ctx->d_bint.p, ctx, kp, 0) : nullptr;
-    const int64_t ldc = (int64_t)col_len(ctx, kp);
-    const int clamp = ctx->opt_block_clamp ? 1 : 0;
-    if (small) {
-        const int nact = (int)(ctx->nchunks * kChunk);
-        if (integral) hipLaunchKernelGGL(k_bcombine_small_int, dim3(kp), dim3(kSmallBlock), 0, st, nact, kp, U, ldc, mx, cw, cj, w, J, ctx->d_bscal.p, clamp);
-        else hipLaunchKernelGGL(k_bcombine_small, dim3(kp), dim3(kSmallBlock), 0, st, nact, kp, U, ldc, mx, cw, w, ctx->d_bscal.p, clamp);
-    } else {
-        const int g = integral ? launch_flat(ctx, kp, k_bcombine_int, U, ldc, mx, cw, cj, pairs(w), pairs(J), ctx->d_bpart.p, clamp)
-                               : launch_flat(ctx, kp, k_bcombine, U, ldc, mx, cw, pairs(w), ctx->d_bpart.p, clamp);
-        if (int rc = finalize(ctx, kFinWsum, 0, kp, g)) return rc;
-    }
-    ctx->blk_info[4] = small ? 1 : 2;
-    HIP_TRY(hipMemcpyAsync(wsum, ctx->d_bscal.p + kWS, K * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    static const BlockKernels k{{k_bcopy_nrm<false>, k_bcopy_nrm<true>}, {k_bortho<false>, k_bortho<true>}, k_bnorm<false>, k_bnorm<true>,
+                                k_btarget_zero, k_bhit, k_btarget_pack, k_bcombine, k_bcombine_int, k_bpack, k_bunpack, k_bfinal,
+                                k_bbegin_small, k_bcombine_small, k_bcombine_small_int};
+    return k;
 }
 
 }  // namespace kfsp
-
-using namespace kfsp;
-
-extern "C" {
-
-// Target sets travel through three existing entry points (the exported surface of the library is pinned): option
-// "block_target" is the call mode - 1: kfsp_set_block takes flags, 2: kfsp_block_info reports the set, 3: kfsp_block_begin
-// is the flux into it (include/kfsp.h, TARGET SETS).  A group head answers with the mode of its rank 0.
-static int set_block_target(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldf, const double *F);
-static int block_target_info(kfsp_ctx *ctx, int64_t *v);
-static int block_hit(kfsp_ctx *ctx, int32_t which, double *out);
-static int64_t target_mode(kfsp_ctx *ctx)
-{
-    const kfsp_ctx *l = lead(ctx);
-    return l ? l->opt_block_target : 0;
-}
-
-// what the calls on a resident block share: a context that takes blocks and holds one
-static int block_call_ok(kfsp_ctx *ctx, const char *none = "no block resident (none was set, or the generator changed since)")
-{
-    if (int rc = block_supported(ctx)) return rc;
-    if (lead(ctx)->blk_k == 0) return fail(ctx, -1, none);
-    return 0;
-}
-
-// n, ldw and W of kfsp_set_block / kfsp_get_block.  A rank's arguments are its own (a caller that gets them wrong on one
-// rank only leaves the others waiting, as in kfsp_set_vector); a rank without rows may pass no W.
-static int block_args_ok(kfsp_ctx *ctx, int64_t n, int64_t ldw, const double *W)
-{
-    if (n != (ctx->use_comm ? ctx->nloc : ctx->n))
-        return fail(ctx, -3, ctx->use_comm ? "n is not this rank's block size" : "n is not the number of states of the generator");
-    if (ldw < n) return fail(ctx, -4, "ldw < n");
-    if (!W && !(ctx->use_comm && n == 0)) return fail(ctx, -5, "null W");
-    return 0;
-}
-
-int kfsp_set_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, const double *W)
-{
-    if (!ctx) return -1;
-    if (target_mode(ctx) == 1) return set_block_target(ctx, k, n, ldw, W);
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_supported(ctx)) return rc;
-        if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
-        if (ctx->group) return group_set_block(ctx, k, n, ldw, W);
-        if (int rc = block_args_ok(ctx, n, ldw, W)) return rc;
-        HIP_TRY(hipSetDevice(ctx->device));
-        const int kp = kp_of(k);
-        if (int rc = box_reach_check(ctx, kp)) return rc;
-        ctx->blk_k = ctx->blk_begin_m = 0;
-        ctx->blk_int = false;
-        if (ctx->blk_kp != kp || ctx->d_blk.cap < col_len(ctx, kp)) {
-            ctx->d_blk.release();
-            ctx->d_bint.release();
-            HIP_TRY(ctx->d_blk.reserve(col_len(ctx, kp), false));
-        }
-        // J (option block_integral) lives and dies with the block: the same shape, +0.0 everywhere
-        if (ctx->opt_block_integral) {
-            HIP_TRY(ctx->d_bint.reserve(col_len(ctx, kp), false));
-            HIP_TRY(hipMemsetAsync(ctx->d_bint.p, 0, col_len(ctx, kp) * sizeof(double), ctx->stream));
-            HIP_TRY(ctx->d_bcj.reserve((size_t)(kMMax + 3) * K, true));
-        } else {
-            ctx->d_bint.release();
-            ctx->d_bcj.release();
-        }
-        ctx->blk_kp = kp;
-        if (int rc = upload_block(ctx, k, kp, ldw, W, bcol(ctx->d_blk.p, ctx, kp, 0))) return rc;
-        target_zero(ctx, kp, bcol(ctx->d_blk.p, ctx, kp, 0));       // a target set: the block is D W from the start
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->blk_k = k;
-        ctx->blk_int = ctx->opt_block_integral != 0;
-        return 0;
-    });
-}
-
-int kfsp_get_block(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldw, double *W)
-{
-    if (!ctx) return -1;
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_call_ok(ctx)) return rc;
-        if (k != lead(ctx)->blk_k) return fail(ctx, -2, "k is not the number of columns of the resident block");
-        // option block_integral = 2: the answer is J, by the route W takes
-        const bool want_j = lead(ctx)->opt_block_integral == 2;
-        if (want_j)
-            if (int on = 0; int rc = block_integral(ctx, &on)) return rc;
-        if (ctx->group) return group_get_block(ctx, k, n, ldw, W);
-        if (int rc = block_args_ok(ctx, n, ldw, W)) return rc;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = download_block(ctx, k, ctx->blk_kp, bcol(want_j ? ctx->d_bint.p : ctx->d_blk.p, ctx, ctx->blk_kp, 0), ldw, W)) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return 0;
-    });
-}
-
-int kfsp_spmm(kfsp_ctx *ctx, int32_t k, int64_t ld, const double *X, double *Y)
-{
-    if (!ctx) return -1;
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_supported(ctx)) return rc;
-        if (k < 1 || k > kBlockMaxK) return fail(ctx, -2, "k out of range (1 <= k <= 16)");
-        if (ld < ctx->n) return fail(ctx, -3, "ld < n");
-        if (!X) return fail(ctx, -4, "null X");
-        if (ctx->group) return group_spmm(ctx, k, ld, X, Y);
-        if (!Y && !(ctx->use_comm && ctx->nloc == 0)) return fail(ctx, -5, "null Y");
-        HIP_TRY(hipSetDevice(ctx->device));
-        const int kp = kp_of(k);
-        if (int rc = box_reach_check(ctx, kp)) return rc;
-        if (int rc = ensure_basis(ctx, kp, 2)) return rc;
-        // under a row partition X is the whole block on every rank (the kfsp_spmv convention): it goes to the gathered
-        // block buffer, global row 0 first, and no exchange follows
-        const bool whole = ctx->use_comm;
-        double *x = whole ? xg_row0(ctx, kp) : bcol(ctx->d_bv.p, ctx, kp, 0), *y = bcol(ctx->d_bv.p, ctx, kp, 1);
-        if (int rc = upload_block(ctx, k, kp, ld, X, x, whole)) return rc;
-        target_zero(ctx, kp, x);                                    // a target set: Y = D A D X
-        int g = 0;
-        if (int rc = spmm(ctx, kp, x, y, nullptr, nullptr, false, &g, whole)) return rc;
-        target_zero(ctx, kp, y);
-        ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
-        if (int rc = download_block(ctx, k, kp, y, ld, Y)) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return 0;
-    });
-}
-
-int kfsp_block_begin(kfsp_ctx *ctx, int32_t m, double *beta)
-{
-    if (!ctx) return -1;
-    if (target_mode(ctx) == 3) return block_hit(ctx, m, beta);
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_call_ok(ctx)) return rc;
-        if (m < 1 || m > kMMax) return fail(ctx, -2, "bad m (need 1 <= m <= 100)");
-        if (m > block_mmax(ctx)) return fail(ctx, -2, "m exceeds option m_max");
-        if (!beta) return fail(ctx, -3, "null beta");
-        return block_begin(ctx, m, beta);
-    });
-}
-
-int kfsp_block_arnoldi(kfsp_ctx *ctx, int32_t m, double break_tol, double *hb, double *nrm, int32_t *brk, double *avnorm)
-{
-    if (!ctx) return -1;
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_call_ok(ctx)) return rc;
-        if (m < 1 || m > kMMax) return fail(ctx, -2, "bad m (need 1 <= m <= 100)");
-        if (m > block_mmax(ctx)) return fail(ctx, -2, "m exceeds option m_max");
-        if (lead(ctx)->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
-        if (m > lead(ctx)->blk_begin_m) return fail(ctx, -2, "m exceeds the m of kfsp_block_begin (the basis is laid out for that one)");
-        if (!hb || !nrm || !brk || !avnorm) return fail(ctx, -4, "null output");
-        return block_arnoldi(ctx, m, break_tol, hb, nrm, brk, avnorm);
-    });
-}
-
-int kfsp_block_combine(kfsp_ctx *ctx, int32_t mx, const double *coef, double *wsum)
-{
-    if (!ctx) return -1;
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_call_ok(ctx)) return rc;
-        if (lead(ctx)->blk_begin_m == 0) return fail(ctx, -3, "no kfsp_block_begin since the block was set");
-        if (mx < 1 || mx > lead(ctx)->blk_begin_m + 2) return fail(ctx, -2, "bad mx (need 1 <= mx <= m + 2 of kfsp_block_begin)");
-        if (!coef) return fail(ctx, -4, "null coef");
-        if (!wsum) return fail(ctx, -5, "null wsum");
-        if (int on = 0; int rc = block_integral(ctx, &on)) return rc;
-        return block_combine(ctx, mx, coef, wsum);
-    });
-}
-
-int kfsp_block_info(kfsp_ctx *ctx, int64_t *v)
-{
-    if (!ctx) return -1;
-    if (!v) return fail(ctx, -2, "null v");
-    if (target_mode(ctx) == 2) return block_target_info(ctx, v);
-    if (ctx->group) return group_block_info(ctx, v);
-    for (int i = 0; i < 8; ++i) v[i] = ctx->blk_info[i];
-    return 0;
-}
-
-static int set_block_target(kfsp_ctx *ctx, int32_t k, int64_t n, int64_t ldf, const double *F)
-{
-    (void)ldf;                                   // one column: the leading dimension is never used
-    return guarded(ctx, [&]() -> int {
-        // refused from what every rank shares, before anything else (block_supported's rule)
-        if (ctx->group || ctx->use_comm || ctx->nranks > 1 || ctx->loop || ctx->comm)
-            return fail(ctx, -12, "kfsp_set_block under block_target = 1 (a target set): not with a row partition (communicator, loop-back rank or group context), "
-                                  "with or without option block_partition");
-        if (ctx->ldv == 0) return fail(ctx, -1, "no matrix set");
-        const bool clear = !F || n == 0;
-        if (!clear && k != 1) return fail(ctx, -2, "block_target = 1: the flags are ONE column (k = 1)");
-        if (!clear && n != ctx->n) return fail(ctx, -2, "block_target = 1: n is not the number of states of the generator");
-        HIP_TRY(hipSetDevice(ctx->device));
-        // the resident block is W, not D W (or D' W): it goes, and its J, as when the generator changes
-        block_release(ctx);
-        block_target_release(ctx);
-        if (clear) return 0;
-        const int64_t rows = ctx->nchunks * kChunk;
-        std::vector<uint8_t> flags((size_t)n);
-        int64_t cnt = 0;
-        for (int64_t i = 0; i < n; ++i) cnt += flags[(size_t)i] = F[i] != 0.0;
-        DevBuf<uint8_t> stage;
-        HIP_TRY(ctx->d_btgt.reserve((size_t)rows, true));
-        hipError_t e = stage.reserve((size_t)n, false);
-        if (e == hipSuccess) e = hipMemcpyAsync(stage.p, flags.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_btarget_pack, dim3(pack_grid(rows)), dim3(kBlock), 0, ctx->stream, n, rows, (const uint8_t *)stage.p,
-                               ctx->perm_on ? (const int32_t *)ctx->d_perm.p : nullptr, ctx->d_btgt.p);
-            e = hipStreamSynchronize(ctx->stream);
-        }
-        stage.release();
-        if (e != hipSuccess) {
-            block_target_release(ctx);
-            HIP_TRY(e);
-        }
-        ctx->blk_tgt = true;
-        ctx->btgt_states = cnt;
-        return 0;
-    });
-}
-
-static int block_target_info(kfsp_ctx *ctx, int64_t *v)
-{
-    v[0] = ctx->blk_tgt ? 1 : 0;
-    v[1] = ctx->btgt_states;
-    v[2] = ctx->bhit_launches;
-    for (int i = 3; i < 8; ++i) v[i] = 0;
-    return 0;
-}
-
-static int block_hit(kfsp_ctx *ctx, int32_t which, double *out)
-{
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_call_ok(ctx)) return rc;
-        if (!ctx->blk_tgt) return fail(ctx, -1, "block_target = 3: no target set resident (kfsp_set_block under block_target = 1)");
-        if (which != 0 && which != 1) return fail(ctx, -2, "block_target = 3: m is 0 (the flux of the block W) or 1 (of its time integral J)");
-        if (!out) return fail(ctx, -3, "null out");
-        if (ctx->opt_adjoint)
-            return fail(ctx, -12, "block_target = 3: the flux into the set is a forward quantity, not with option adjoint "
-                                  "(include/kfsp.h, TARGET SETS, has the backward recipe)");
-        if (which == 1 && !ctx->blk_int)
-            return fail(ctx, -1, "block_target = 3: no integral resident beside the block (option block_integral before kfsp_set_block)");
-        HIP_TRY(hipSetDevice(ctx->device));
-        const int kp = ctx->blk_kp;
-        hipStream_t st = ctx->stream;
-        if (int rc = ensure_scalars(ctx)) return rc;
-        // the raw product goes to a column of its own: W, J and a basis laid out by kfsp_block_begin stay as they are
-        if (ctx->d_bhit.cap < col_len(ctx, kp)) {
-            ctx->d_bhit.release();
-            HIP_TRY(ctx->d_bhit.reserve(col_len(ctx, kp), true));
-        }
-        HIP_TRY(ctx->d_bhsum.reserve((size_t)2 * K, true));
-        double *y = bcol(ctx->d_bhit.p, ctx, kp, 0);
-        int g = 0;
-        if (int rc = spmm(ctx, kp, bcol(which ? ctx->d_bint.p : ctx->d_blk.p, ctx, kp, 0), y, nullptr, nullptr, false, &g)) return rc;
-        const int gv = launch_flat(ctx, kp, k_bhit, kp_index(kp), ctx->d_btgt.p, pairs(y), ctx->d_bpart.p);
-        // the sum stage of k_bfinal alone: the block partials in its fixed order (both of its sums read the same ones)
-        hipLaunchKernelGGL(k_bfinal, dim3(1), dim3(kBlock), 0, st, (int)kFinWsum, 0, kp, gv, ctx->d_bpart.p, (int64_t)0, ctx->d_bscal.p, 0.0,
-                           ctx->d_bhsum.p);
-        ctx->bhit_launches = 3;
-        double h[K];
-        HIP_TRY(hipMemcpyAsync(h, ctx->d_bhsum.p, K * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int c = 0; c < K; ++c) out[c] = c < ctx->blk_k ? h[c] : 0.0;
-        return 0;
-    });
-}
-
-int kfsp_spmm_bench(kfsp_ctx *ctx, int reps, float *ms_total)
-{
-    if (!ctx) return -1;
-    return guarded(ctx, [&]() -> int {
-        if (int rc = block_call_ok(ctx, "no block resident")) return rc;
-        if (reps < 1) return fail(ctx, -2, "reps < 1");
-        if (!ms_total) return fail(ctx, -3, "null ms_total");
-        if (ctx->group) return group_spmm_bench(ctx, reps, ms_total);
-        HIP_TRY(hipSetDevice(ctx->device));
-        const int kp = ctx->blk_kp;
-        if (int rc = ensure_basis(ctx, kp, 1)) return rc;
-        const double *x = bcol(ctx->d_blk.p, ctx, kp, 0);
-        double *y = bcol(ctx->d_bv.p, ctx, kp, 0);
-        HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-        ctx->blk_info[6] = ctx->opt_adjoint ? 1 : 0;
-        // (under a row partition the source is exchanged before every product, as in the solver)
-        for (int r = 0; r < reps; ++r) {
-            int g = 0;
-            if (int rc = spmm(ctx, kp, x, y, nullptr, nullptr, false, &g)) return rc;
-        }
-        HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(hipEventSynchronize(ctx->ev1));
-        HIP_TRY(hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
-        return 0;
-    });
-}
-
-}  // extern "C"

@@ -1,8 +1,9 @@
-// Private: what the translation units of the block product share - kfsp_block.hip (Y = A X and everything behind
-// the product), kfsp_block_adj.hip (Y = A^T X, option adjoint), kfsp_block_boxg.hip (Y = A X on any matrix-free box,
-// option block_box = 2), kfsp_block_diac.hip (Y = A X from the coded banded image, option block_dia_code) and
-// kfsp_block_diac_t.hip (Y = A^T X from it, option block_dia_code_adjoint).  The row helpers, SpmmArgs and block_sum_cols
-// are the ones kfsp_block.hip always had; the descriptors at the end belong to the transposed product and to the generic matrix-free kernels.
+// Private: what the translation units of the block product share - kfsp_block.hip (the kernels of Y = A X and of everything
+// behind the product), kfsp_block_host.hip (the host side of all of them), kfsp_block_adj.hip (Y = A^T X, option adjoint),
+// kfsp_block_boxg.hip (Y = A X on any matrix-free box, option block_box = 2), kfsp_block_diac.hip (Y = A X from the coded
+// banded image, option block_dia_code) and kfsp_block_diac_t.hip (Y = A^T X from it, option block_dia_code_adjoint): the row
+// helpers, SpmmArgs and block_sum_cols, the layout of the per-column scalars, the descriptors of the transposed product and
+// of the generic matrix-free kernels, and the selectors through which the host file reaches every kernel.
 #pragma once
 
 #include "kfsp_block.h"
@@ -276,8 +277,23 @@ static inline bool ell_adj_resident(int64_t n, int64_t ell_cols, int32_t ell_ld,
     return cap_adj >= nent && cap_off >= nent && cap_diag >= (size_t)n;
 }
 
-// The kernels of the other translation units, by function pointer: kfsp_block.hip launches them (the grid and the LDS
-// are its business).  Hidden: the shared object exports nothing new.
+// ---- per-column scalars of a pass (d_bscal), kBlockMaxK entries each: what the kernels of kfsp_block.hip write and
+// kfsp_block_host.hip copies out
+constexpr int kHB = 0;                                            // [(kMMax + 2) * 3][K]: H(j-1,j), H(j,j), H(j+1,j) of column j
+constexpr int kNRM = kHB + (kMMax + 2) * 3 * kBlockMaxK;          // [kMMax + 3][K]: ||u_j||
+constexpr int kCO = kNRM + (kMMax + 3) * kBlockMaxK;              // [3][K]: the update coefficients of the column in progress
+constexpr int kGG = kCO + 3 * kBlockMaxK;                         // [K]: v_j . v_{j-1}
+constexpr int kBRK = kGG + kBlockMaxK;                            // [K]: 0 running, j broke down after column j, -1 skipped
+constexpr int kAVN = kBRK + kBlockMaxK;                           // [K]
+constexpr int kWS = kAVN + kBlockMaxK;                            // [K]
+constexpr int kCMB = kWS + kBlockMaxK;                            // [kMMax + 3][K]: combine coefficients
+constexpr int kSQ1 = kCMB + (kMMax + 3) * kBlockMaxK;             // [K]: ||u_1||^2 (what k_barnoldi_small starts from)
+constexpr int kScal = kSQ1 + kBlockMaxK;
+constexpr int kSmallBlock = 1024;                                 // lanes of a small-path workgroup
+enum { kFinBegin = 0, kFinDots = 1, kFinNorm = 2, kFinAvn = 3, kFinWsum = 4 };   // the stages of k_bfinal
+
+// ---- the kernels, by function pointer: kfsp_block_host.hip launches them (the grid and the LDS are its business).  Hidden:
+// the shared object exports nothing new.
 struct BoxgArgs;   // kfsp_boxg_dev.h
 typedef void (*SpmmFn)(SpmmArgs);
 typedef void (*SpmmEllTFn)(SpmmArgs, EllAdjDev);
@@ -292,6 +308,27 @@ KFSP_LOCAL SpmmEllTFn spmm_ell_t_kernel(int kp, bool dots);            // k_spmm
 KFSP_LOCAL SpmmBoxTFn spmm_box_t_kernel(int kp, int inst, bool dots);  // k_spmm_box_t
 KFSP_LOCAL SpmmBoxgFn spmm_boxg_t_kernel(int kp, bool dots);           // k_spmm_boxg_t
 KFSP_LOCAL SpmmBoxgFn spmm_boxg_kernel(int kp, bool dots);             // k_spmm_boxg (kfsp_block_boxg.hip)
+KFSP_LOCAL SpmmFn spmm_kernel(int kp, int fmt, bool dots, bool part);  // k_spmm (kfsp_block.hip)
+KFSP_LOCAL SpmmFn spmm_box_kernel(int kp, int inst, bool dots);        // k_spmm_box
+// the streaming, finishing and small kernels of kfsp_block.hip, one member each ([1]: the TARGET instantiation)
+struct BlockKernels {
+    void (*copy_nrm[2])(int64_t, int, const d2 *, d2 *, double *, const uint8_t *, int);
+    void (*ortho[2])(int64_t, int, d2 *, const d2 *, const d2 *, const double *, double *, const uint8_t *, int);
+    void (*norm)(int64_t, int, const d2 *, double *, const uint8_t *, int);
+    void (*norm_target)(int64_t, int, d2 *, double *, const uint8_t *, int);
+    void (*target_zero)(int64_t, int, const uint8_t *, d2 *);
+    void (*hit)(int64_t, int, int, const uint8_t *, const d2 *, double *);
+    void (*target_pack)(int64_t, int64_t, const uint8_t *, const int32_t *, uint8_t *);
+    void (*combine)(int64_t, int, const double *, int64_t, int, const double *, d2 *, double *, int);
+    void (*combine_int)(int64_t, int, const double *, int64_t, int, const double *, const double *, d2 *, d2 *, double *, int);
+    void (*pack)(int64_t, int, int, const double *, int64_t, const int32_t *, double *);
+    void (*unpack)(int64_t, int, int, const double *, const int32_t *, double *, int64_t);
+    void (*finish)(int, int, int, int, const double *, int64_t, double *, double, double *);
+    void (*begin_small)(int, int, const double *, double *, double *);
+    void (*combine_small)(int, int, const double *, int64_t, int, const double *, double *, double *, int);
+    void (*combine_small_int)(int, int, const double *, int64_t, int, const double *, const double *, double *, double *, double *, int);
+};
+KFSP_LOCAL const BlockKernels &block_kernels();
 #undef KFSP_LOCAL
 
 // the kernel families that stage an image into dynamic LDS - the table image of a matrix-free box, or the dictionaries

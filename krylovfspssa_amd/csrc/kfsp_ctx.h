@@ -168,9 +168,29 @@ struct GeneratorState {
     BoxGeom box;                     // matrix-free box (kfsp_set_matrix_box): what box_plan decided (kfsp_box_plan.h); else all defaults
 };
 
+// The slots of kfsp_block_info (include/kfsp.h), by the names krylovfspssa_amd/host.py gives them.
+enum BlockInfoSlot { kInfoOneLaunch = 0, kInfoFmt, kInfoBeginLaunches, kInfoArnoldiLaunches, kInfoCombineLaunches, kInfoLdsBytes,
+                     kInfoAdjoint, kInfoExchange, kInfoSlots };
+
+// What the block path (kfsp_block_host.hip) knows beside its buffers.  One definition, one reset (block_reset, on every path that
+// replaces the generator and where a target set is set or cleared).
+struct BlockState {
+    int blk_k = 0, blk_kp = 0;   // columns of the resident block (0: none) and its width
+    int bv_kp = 0, bxg_kp = 0;   // widths d_bv and d_bxg are laid out for
+    int blk_begin_m = 0;         // Krylov dimension the last block_begin laid the basis out for (0: none since kfsp_set_block)
+    int64_t blk_info[kInfoSlots] = {};   // kfsp_block_info: how the last block calls ran
+    int blk_staged_occ[6][4][2] = {};    // workgroups resident per CU of the kernels that stage an image into LDS (a box's tables,
+                                         // the dictionaries of the coded banded form), by [StagedFamily][kp_index(kp)][dots]
+                                         // (kfsp_block_dev.h; 0: not asked yet)
+    bool blk_int = false;           // J is resident beside the block (option block_integral)
+    bool blk_tgt = false;           // a target set is resident (d_btgt)
+    int64_t btgt_states = 0;        // its number of states
+    int64_t bhit_launches = 0;      // launches enqueued by the last flux call (kfsp_block_begin under block_target = 3)
+};
+
 }  // namespace kfsp
 
-struct kfsp_ctx : kfsp::GeneratorState {
+struct kfsp_ctx : kfsp::GeneratorState, kfsp::BlockState {
     // a head handle over a row partition driven by ONE host thread (kfsp_create_group, kfsp_group.cpp): no device
     // resources of its own; every entry point fans out to the ranks' contexts
     kfsp::Group *group = nullptr;
@@ -313,28 +333,17 @@ struct kfsp_ctx : kfsp::GeneratorState {
     DevBuf<double> d_wfull;  // n: the whole compacted w between kfsp_drop_compact and the next generator (communicator)
     DevBuf<uint8_t> d_flagloc;   // L * nranks: flags of the blocks in the internal order (communicator)
 
-    // several vectors at once (kfsp_block.hip): the resident block (kp doubles per row), the block basis / scratch
+    // several vectors at once (kfsp_block_host.hip): the resident block (kp doubles per row), the block basis / scratch
     // columns, the caller-layout staging area, per-column scalars and partials; all released when the generator changes
+    // (block_reset; the scalars that describe them: BlockState)
     DevBuf<double> d_blk, d_bv, d_bstage, d_bscal, d_bpart;
     DevBuf<double> d_bxg;        // row partition: the gathered source block (all-gather mode) / the whole X of kfsp_spmm, margins included
-    int bxg_kp = 0;              // width d_bxg is laid out for
-    int blk_k = 0, blk_kp = 0;   // columns of the resident block (0: none) and its width
-    int bv_kp = 0;               // width d_bv is laid out for
-    int blk_begin_m = 0;         // Krylov dimension the last block_begin laid the basis out for (0: none since kfsp_set_block)
-    int64_t blk_info[8] = {};    // kfsp_block_info: how the last block_begin / block_arnoldi / block_combine ran
-    int blk_staged_occ[6][4][2] = {};   // workgroups resident per CU of the kernels that stage an image into LDS (a box's tables,
-                                        // the dictionaries of the coded banded form), by [StagedFamily][kp_index(kp)][dots]
-                                        // (kfsp_block_dev.h; 0: not asked yet)
     DevBuf<double> d_bint, d_bcj;   // option block_integral: J, the time integral of the resident block (laid out like d_blk), and
                                     // its coefficient table; allocated by kfsp_set_block while the option is on, never otherwise
-    bool blk_int = false;           // J is resident beside the block
     // target set of the block path (kfsp_set_block under block_target = 1): one byte per row of the internal order, nchunks * kChunk of
     // them (1: the row's state is in the set; the padding rows read 0).  Lives until cleared or the generator changes
-    // (block_target_release beside every block_release of a generator change); nothing of it exists while none is set.
+    // (block_reset); nothing of it exists while none is set.
     DevBuf<uint8_t> d_btgt;
-    bool blk_tgt = false;           // a set is resident
-    int64_t btgt_states = 0;        // its number of states
-    int64_t bhit_launches = 0;      // launches enqueued by the last flux call (kfsp_block_begin under block_target = 3)
     DevBuf<double> d_bhit, d_bhsum; // the flux call: its scratch block column and the 2 K finished sums; released with the block
 
     // scalars
@@ -415,6 +424,7 @@ struct kfsp_ctx : kfsp::GeneratorState {
 
 namespace kfsp {
 inline void reset_generator(kfsp_ctx *ctx) { static_cast<GeneratorState &>(*ctx) = {}; }   // THE reset of what is resident
+inline void reset_block_state(kfsp_ctx *ctx) { static_cast<BlockState &>(*ctx) = {}; }     // ... and of the block path's scalars (block_reset, after its buffers)
 // group contexts (kfsp_group.cpp): what each entry point of include/kfsp.h does when it is handed a head
 void comm_abort(kfsp_ctx *ctx);      // kfsp_comm.cpp: release a rank blocked in a collective (called from the group's watchdog)
 int group_selftest(int nranks, int failing_rank, int hanging_rank, int work_ms, int hang_ms, int timeout_ms, int grace_ms,
@@ -553,8 +563,7 @@ int rebuild_resident(kfsp_ctx *ctx, int32_t n, int32_t bw, int32_t ld, int32_t n
 int expand_resident_lists(kfsp_ctx *ctx, double tstep, int64_t seedmix, int32_t ns, int32_t nr, const int32_t *stoich,
                           int32_t max_count, int32_t cap, int64_t *n_out, int64_t *n_ssa);
 void launch_zero_pad(int64_t n0, int64_t n1, double *w, hipStream_t st);
-// several vectors at once (kfsp_block.hip): drop the resident block and its buffers
-void block_release(kfsp_ctx *ctx);
-// ... and the target set of kfsp_set_block under block_target = 1 (a generator change calls both, kfsp_set_block under block_target = 1 the first alone)
-void block_target_release(kfsp_ctx *ctx);
+// several vectors at once (kfsp_block_host.hip): release the resident block, its target set and every buffer of the block path,
+// and put BlockState back to its defaults - whenever the generator changes, and where a target set is set or cleared
+void block_reset(kfsp_ctx *ctx);
 }  // namespace kfsp
