@@ -287,7 +287,8 @@ int kfsp_drop_flags(kfsp_ctx *ctx, int64_t n, uint8_t *dropped);
 /* Compacts the resident w by those flags (kept entries keep their order, :500-546 for W); *n_new =
  * n - n_flagged.  The context then WAITS for the generator of the compacted FSP: the next
  * kfsp_set_matrix_ell / _csr must have n_new states and makes the compacted vector its w (do not
- * call kfsp_set_vector in between, it would replace it).
+ * call kfsp_set_vector in between, it would replace it).  n_new = 0 (every state was flagged) leaves
+ * nothing to wait for: kfsp_drop_rebuild refuses (-9), and the next generator, of any size, starts from w = 0.
  * With a communicator the compacted FSP has another partition: every rank assembles the whole vector (one
  * all-gather), compacts it with the flags it holds, and takes its new block when the generator arrives. */
 int kfsp_drop_compact(kfsp_ctx *ctx, int64_t *n_new);

@@ -218,7 +218,7 @@ int kfsp::resize(kfsp_ctx *ctx, int64_t n)
     const int64_t need = round_up(ctx->L + 2 * ctx->margin, 256);
     int64_t ldv = ctx->ldv;
     if (need > ctx->ldv || ctx->relayout) {
-        if (ctx->w_pending && !ctx->use_comm && !ctx->w_pending_full)
+        if (ctx->w_pending && ctx->w_pending_n > 0 && !ctx->use_comm && !ctx->w_pending_full)
             return fail(ctx, -2, "the FSP grew between kfsp_drop_compact and the next generator");
         // (head room: half as much again, but no more than 2^24 rows - at 10^8 states 50 % would be 70 GB)
         ldv = ctx->relayout ? need : round_up(need + std::min<int64_t>(need / 2, (int64_t)1 << 24), 256);

@@ -120,8 +120,15 @@ int adopt_pending_vector(kfsp_ctx *ctx)
 {
     if (!ctx->w_pending) return 0;
     ctx->w_pending = false;
-    if (ctx->w_pending_n != ctx->n) return fail(ctx, -2, "generator size does not match the vector compacted by kfsp_drop_compact");
+    // (a compaction that dropped EVERY state leaves no vector to carry over - and no generator of 0 states could ever
+    // claim it: whatever generator comes next starts from w = 0)
+    if (ctx->w_pending_n != ctx->n && ctx->w_pending_n != 0)
+        return fail(ctx, -2, "generator size does not match the vector compacted by kfsp_drop_compact");
     HIP_TRY(hipMemsetAsync(ctx->d_w.p, 0, (size_t)ctx->ldv * sizeof(double), ctx->stream));
+    if (ctx->w_pending_n == 0) {
+        ctx->w_pending_full = false;
+        return 0;
+    }
     if (ctx->use_comm || ctx->w_pending_full) {
         ctx->w_pending_full = false;
         if (int rc = scatter_from_full(ctx, ctx->d_wfull.p, ctx->d_w.p)) return rc;

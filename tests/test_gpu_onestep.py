@@ -8,22 +8,11 @@ import numpy as np
 import pytest
 
 from tests.expand_helpers import onestep_py as _onestep_py
+from tests.expand_helpers import stoich as _stoich
 
 pytestmark = pytest.mark.gpu
 
 CASES = [("toggle", 5, 10), ("toggle", 10, 20), ("repressilator", 5, 10), ("goutsias", 5, 10), ("goutsias", 10, 16)]
-
-
-def _stoich(a):
-    """reaction vectors from a reference assembly: successor - state of any linked pair"""
-    nr = a["adj"].shape[1]
-    nu = [None] * nr
-    for i, row in enumerate(a["adj"]):
-        for r, j in enumerate(row):
-            if j > 0 and nu[r] is None:
-                nu[r] = a["state"][j - 1] - a["state"][i]
-    assert all(v is not None for v in nu)
-    return np.array(nu, dtype=np.int32)
 
 
 @pytest.mark.parametrize("name,k0,k1", CASES)
